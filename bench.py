@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- celerite log-likelihood evaluations/s on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the roofline of the timed kernel, and at N > 1 `per_rank`).  Everything
+else listed below -- the CPU baseline, the clock under load, the other configurations and workflows, the extras after
+the timed region at N > 1 -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed
+(rank 0: lnP and status of every row, and at N > 1 the all-gathered per-light-curve maxima) as DIR/<name>.npy.
 
 Workload: BASELINE.json configs[3], the Protassov posterior-predictive sweep -- L = 2000
 simulated light curves sharing one irregular sampling (N = 10 000), W = 256 walkers each,
@@ -119,7 +125,12 @@ def parse():
                     help="time box of the CPU baseline sample (0 = skip)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default=None,
                     help="default: strong when --gpus > 1 (the light curves are split over the ranks)")
-    ap.add_argument("--no-extras", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement after the timed region (CPU baseline, clock under load, other "
+                         "configurations and workflows, the multi-rank extras); default: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64 / float32)")
+    ap.add_argument("--no-extras", action="store_true", help="headline only, even with --full (profiling runs)")
     ap.add_argument("--no-workflow", action="store_true", help="skip configs[3] as a workflow (~30 s)")
     ap.add_argument("--extras-timeout", type=int, default=300,
                     help="N > 1: seconds the walker-sharded configs and the sharded workflow may take after the timed "
@@ -128,7 +139,10 @@ def parse():
                     help="N > 1: exit with code 3 when the extras after the timed region fail (default: the failure is a "
                          "field of the line, `multi_rank_extras_error`, and a message on stderr; the exit code stays 0 so "
                          "that a measured scaling number is never discarded for a side measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -459,10 +473,31 @@ def walker_sharded_configs(rank, world, local_dev, oversubscribed):
     return out
 
 
+DUMP_MAX_ROWS = 2_000_000     # lnP (8 B) + status (4 B) + row index (8 B) per row: at most 40 MB of a sampled batch
+
+
+def dump_outputs(directory, lnp, status, gathered_max=None):
+    """What the last timed step handed its caller, as DIR/<name>.npy: `loglike` (float64, -inf where rejected) and
+    `status` (float32 of the int32 codes) of every row, and at N > 1 `lightcurve_max` (float64, the all-gathered
+    per-light-curve maxima, -inf padded).  A batch of more than DUMP_MAX_ROWS rows is sampled at fixed, seeded rows,
+    written as `row_index` (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"loglike": lnp.astype(np.float64), "status": status.astype(np.float32)}
+    if lnp.shape[0] > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(20250704).choice(lnp.shape[0], DUMP_MAX_ROWS, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["row_index"] = rows.astype(np.float64)
+    if gathered_max is not None:
+        arrays["lightcurve_max"] = gathered_max.astype(np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args)    # does not return
+    run_full = args.full and not args.no_extras     # the side measurements after the timed region
     import torch
     import torch.distributed as dist
 
@@ -603,6 +638,9 @@ def main():
     n_ok = int((status == 0).sum())
     if not np.all(np.isfinite(out[status == 0])) or n_ok < B // 2:
         raise SystemExit("bench: non-finite log-likelihoods in the timed batch")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, status,
+                     d_gather.cpu().numpy().astype(np.float64) if grouped else None)
 
     extras = {}
     solve_s = float(np.mean(solve_ms)) * 1e-3
@@ -716,13 +754,13 @@ def main():
         line.setdefault("cpu_baseline", None)
         return line
 
-    if world > 1 and args.cpu_seconds > 0 and not args.no_extras:
+    if world > 1 and args.cpu_seconds > 0 and run_full:
         # the CPU port beside the GPUs in the N > 1 line as well: rank 0 times it on its own block (the first evaluations
         # of its timed batch, which it checks on the way), after the timed region; the other ranks wait at the barrier
         if rank == 0:
             extras["cpu_baseline"] = cpu_baseline(t, y, dy, kinds, theta, y_mean, args.cpu_seconds, bounds, out, status)
         dist.barrier()
-    if world > 1 and not args.no_extras:
+    if world > 1 and run_full:
         # the clock rank 0's card holds under this load (rocm-smi's first card = rank 0's), for roofline.fp64_issue_frac_at_clock
         clock = clock_under_load(lambda: [sweep() for _ in range(40)], lambda: torch.cuda.synchronize(dev)) if rank == 0 else None
         if clock:
@@ -730,7 +768,7 @@ def main():
         dist.barrier()
     if grouped:
         extras["rccl_ranks"] = {"torch_distributed_world": dist.get_world_size(), "backend": dist.get_backend()}
-        if not args.no_extras and (world > 1 or os.environ.get("MTG_SHARD_ONE_RANK") == "1"):
+        if run_full and (world > 1 or os.environ.get("MTG_SHARD_ONE_RANK") == "1"):
             # (MTG_BENCH_FORCE_DIST=1 MTG_SHARD_ONE_RANK=1 on a one-GPU box: the whole multi-rank path -- process group over
             # RCCL, broadcasts, the library's communicator, the all-gather pair of every half-step -- with one rank)
             # The timed region is over and agreed on by every rank.  What follows runs collectives that no one-GPU box
@@ -835,7 +873,7 @@ def main():
                 if rank != 0:
                     time.sleep(3.0)          # rank 0's watcher prints the line before a launcher that sees this rank die stops it
                 give_up(why)
-    if world == 1 and not args.no_extras:
+    if world == 1 and run_full:
         # (a) the same sweep through the host-pointer entry point: H2D theta + kernels + D2H lnP, status
         reps = max(3, min(args.steps, 10))
         eng.loglike(theta, lc, add_prior=True)
@@ -985,9 +1023,9 @@ def main():
 
     if rank == 0:
         line = headline_line()
-        if world == 1 and args.cpu_seconds > 0 and not args.no_extras:
+        if world == 1 and args.cpu_seconds > 0 and run_full:
             line["cpu_baseline"] = cpu_baseline(t, y, dy, kinds, theta, y_mean, args.cpu_seconds, bounds, out, status)
-        if world == 1 and not args.no_extras:
+        if world == 1 and run_full:
             # the other SURVEY 8(d) figures; a failure here fails the bench
             line["config2_raw_kernel"] = raw_kernel_config2(local_dev)
             line["other_configs"] = single_lightcurve_configs()

@@ -4,7 +4,7 @@
     python scripts/design_table.py            rewrite the block between the design_table markers of DESIGN.md
     python scripts/design_table.py --check    exit 1 if DESIGN.md does not hold what this script would write
 
-Sources, newest round first: profiles/rNN_bench_line.json (the full JSON line of `python bench.py` on one MI355X, copied
+Sources, newest round first: profiles/rNN_bench_line.json (the JSON line of `python bench.py --full` on one MI355X, copied
 from gpurun_out/ by hand when a round's numbers are final) and profiles/rNN_bench_line_{2,6}ranks_one_gpu.json (the
 multi-rank rehearsals).  Only tracked files under profiles/ are read: the driver's BENCH_rNN.json lands after the last
 commit of a round and must not be able to change what --check expects.  Everything else in a row (where it is built, what tests it) is static

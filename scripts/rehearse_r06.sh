@@ -28,9 +28,9 @@ json.dump(line, open(path, "w"))
 PY
 }
 export MASTER_ADDR=127.0.0.1
-run one_rank_rccl            env MTG_BENCH_FORCE_DIST=1 MTG_SHARD_ONE_RANK=1 python3 bench.py --steps 5 --warmup 2 --no-workflow
-run one_rank_rccl_injected   env MTG_BENCH_FORCE_DIST=1 MTG_SHARD_ONE_RANK=1 MTG_SHARD_FAIL_RCCL=all python3 bench.py --steps 5 --warmup 2 --no-workflow
-run 2ranks_one_gpu           python3 bench.py --gpus 2 --steps 5 --warmup 2
-run 2ranks_torchrun_one_gpu  python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 5 --warmup 2
-run 2ranks_failed_extras     env MTG_BENCH_FAIL_EXTRAS=1 python3 bench.py --gpus 2 --steps 5 --warmup 2
-run 6ranks_one_gpu           python3 bench.py --gpus 6 --steps 5 --warmup 2
+run one_rank_rccl            env MTG_BENCH_FORCE_DIST=1 MTG_SHARD_ONE_RANK=1 python3 bench.py --steps 5 --warmup 2 --no-workflow --full
+run one_rank_rccl_injected   env MTG_BENCH_FORCE_DIST=1 MTG_SHARD_ONE_RANK=1 MTG_SHARD_FAIL_RCCL=all python3 bench.py --steps 5 --warmup 2 --no-workflow --full
+run 2ranks_one_gpu           python3 bench.py --gpus 2 --steps 5 --warmup 2 --full
+run 2ranks_torchrun_one_gpu  python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 5 --warmup 2 --full
+run 2ranks_failed_extras     env MTG_BENCH_FAIL_EXTRAS=1 python3 bench.py --gpus 2 --steps 5 --warmup 2 --full
+run 6ranks_one_gpu           python3 bench.py --gpus 6 --steps 5 --warmup 2 --full

@@ -33,7 +33,7 @@ def test_bench_refuses_to_run_without_a_gpu():
 def test_bench_flag_table_matches_the_contract():
     res = _run("--help")
     assert res.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--extras-timeout", "--no-workflow"):
+    for flag in ("--gpus", "--steps", "--warmup", "--extras-timeout", "--no-workflow", "--full", "--dump-outputs"):
         assert flag in res.stdout
 
 
