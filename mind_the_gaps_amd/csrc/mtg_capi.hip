@@ -1246,6 +1246,8 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
     sa.sig = nullptr;
     ctx->timed = true;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
+    if (jr + jc == 0) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_white_kernel (coefficients)");
+    else snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_solve_kernel<%d,%d,0> (coefficients)", jr, jc);
     rc = sweep_launch(ctx, fn, sa, B, 0, s);
     if (rc) return rc;
     HIP_TRY(ctx, hipGetLastError());

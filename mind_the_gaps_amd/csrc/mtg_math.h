@@ -148,14 +148,34 @@ __device__ __forceinline__ void mtg_sincos_small(double r, double *s, double *c)
 // formed inside an fma, the remainder is rounded once, and the only error is that of the constant C -- the frequency
 // d moved by less than its own rounding, the same at every sample.  What is left is the rounding of x itself,
 // ulp(x) / 2 per step (7e-12 rad at x = 1e5, 6e-5 at 1e12; a random walk over the steps of a sweep) -- against
-// ulp(d t_n) / 2 at EVERY sample for a phase evaluated at the elapsed time, as the libm variant of the sweep does
-// (and celerite, at the absolute time): n times larger at sample n.  Accuracy therefore never argues for the libm
-// variants; they are kept for what the mantissa trick cannot hold.  (Until round 3 the limit was 1e5, a left-over of
+// ulp(d t_n) / 2 at EVERY sample for celerite's phase at the absolute time: n times larger at sample n
+// (tests/test_accuracy_vs_quad_gpu.py holds the table-phase kernels to that, d max(dx) in [1e4, 1e12]).  The libm
+// variants reduce the exact elapsed phase modulo 2 pi before rounding it (mtg_elapsed_sincos) and are the more
+// accurate; they are kept for what the mantissa trick cannot hold, the table for its speed.  (Until round 3 the limit was 1e5, a left-over of
 // a two-constant reduction.  A sampler's walkers at the top of the prior box -- omega_0 ~ e^10 per day, gaps of
 // days -- crossed it, and ONE such lane sends its whole wave through libm: 25 % of the configs[3] refits' time.)
 #ifndef MTG_TRIG_FAST_MAX
 #define MTG_TRIG_FAST_MAX 1.0e12
 #endif
+
+// (sin, cos) of d (t - t0) for the libm variants, with the phase reduced modulo 2 pi before it is rounded: t - t0
+// exactly as th + tl (two-sum), d th exactly as p + pe (fma), k = rint(p / 2 pi), p - k C1 exact in one fma (C1 the
+// double nearest 2 pi: for |p| < 2^52 the difference is a multiple of ulp(C1) below 2^2), then the second part C2 of
+// 2 pi and the low parts pe + d tl.  The argument handed to sincos is then good to ~1e-15 rad for phases below 2^52, and
+// to 4e-14 rad up to 1e18 (checked against __float128).  Formed plainly, d * fl(t - t0) is rounded at the phase's own magnitude, ulp(d t) / 2 -- 8e-3 rad at
+// d t ~ 1e14 (tests/test_accuracy_vs_quad_gpu.py, phase/j3 at 9e11 rad per step: 16 x celerite's own error there).
+__device__ __forceinline__ void mtg_elapsed_sincos(double d, double t, double t0, double *s, double *c)
+{
+#pragma clang fp contract(off)
+    const double th = t - t0, tb = th - t;
+    const double tl = (t - (th - tb)) + (-t0 - tb);
+    const double p = d * th;
+    const double low = __builtin_fma(d, tl, __builtin_fma(d, th, -p));
+    const double k = __builtin_rint(p * 0x1.45f306dc9c883p-3);                   // p / 2 pi
+    const double r1 = __builtin_fma(-k, 0x1.921fb54442d18p+2, p);               // C1 = fl(2 pi)
+    const double r = __builtin_fma(-k, 0x1.1a62633145c07p-52, r1) + low;        // C2 = 2 pi - C1
+    sincos(r, s, c);
+}
 
 // ---------------------------------------------------------------------------
 // Every VALU instruction costs the wave the same 4-cycle issue slot, FP64 or not,

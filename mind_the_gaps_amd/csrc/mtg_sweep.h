@@ -103,7 +103,7 @@ __device__ __forceinline__ void mtg_sweep(MtgLane<NR, NC> &L, const MtgSolveArgs
                 // does at the absolute one.  (Rotating the previous pair by sincos(d dx) instead
                 // lets the pair drift by ~1e-16 per step, which an ill-conditioned covariance --
                 // amplitude >> noise -- amplifies far beyond celerite's own error.)
-                sincos(L.dc[k] * (tc - t0), &sn, &cn);
+                mtg_elapsed_sincos(L.dc[k], tc, t0, &sn, &cn);
             }
             if (k >= NC - NB0) {
                 U[NR + 2 * k] = L.ac[k] * cn;

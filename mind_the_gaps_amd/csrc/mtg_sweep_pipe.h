@@ -128,7 +128,7 @@ __device__ __forceinline__ void mtg_pipe_produce(const MtgSolveArgs &a, int64_t 
             v[NR + k] = mtg_exp_cdx(ncc[k], cc64[k], dxc, tab);
             double cn, sn;
             if (FAST) mtg_phase_step(dc[k], dxc, pr[k], pm[k], &sn, &cn, tab);
-            else sincos(dc[k] * (tc - t0), &sn, &cn);
+            else mtg_elapsed_sincos(dc[k], tc, t0, &sn, &cn);
             v[NT + 2 * k] = cn;
             v[NT + 2 * k + 1] = sn;
         }

@@ -7,6 +7,9 @@ celerite>=0.4.2 solver it calls):
 * ``oracle.dense``    -- dense-covariance definition (numpy float64 / mpmath)
 * ``oracle.celerite`` -- ctypes view of oracle/celerite_ref.c (the celerite
   semiseparable recurrences in plain C)
+* ``oracle.quad``     -- ctypes view of oracle/celerite_quad.c: the one-sweep recurrence
+  in __float128 (libquadmath), the quad-precision truth of tests/test_quad_oracle.py and
+  tests/golden/quad_golden.json; built on first use (``make -C oracle liboracle_quad.so``)
 
 PARITY STATUS: "parity unpinned" at the lnL boundary for values of kernels with J > 0 (see
 the file headers).  What the reference's notebooks print from celerite is reproduced in

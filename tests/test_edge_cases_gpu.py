@@ -74,8 +74,9 @@ def test_phase_increments_beyond_the_table_range_take_the_ocml_sweep(engine):
     finally:
         engine.set_time_parallel(2)
     assert np.all(st0 == 0) and np.all(st1[:40] == 0)
-    # the OCML variant evaluates d (t_n - t_0) at the elapsed time, ~6e8 rad behind the gap: ulp / 2 = 6e-8 rad of phase
-    # noise per sample where the table variant has ~1e-16 -- which is what the difference shows
+    # the OCML variant reduces the exact elapsed phase d (t_n - t_0) modulo 2 pi (mtg_elapsed_sincos): ~1e-15 rad; the
+    # table variant's step across the gap, d dx ~ 6e8 rad, is rounded once to ulp / 2 = 6e-8 rad and carried to every
+    # later sample -- which is what the difference shows
     assert np.max(np.abs(mixed[:40] - alone) / np.abs(alone)) < 1e-7
     assert np.any(mixed[:40] != alone)                       # (really another variant: not bit for bit)
 
