@@ -16,6 +16,7 @@
 // pure function of (seed, iteration, purpose, ensemble, walker) -- reproducible and
 // independent of launch geometry; tests/test_device_sampler_gpu.py replays the same
 // stream on the host.
+#include "mtg_math.h"
 #include "mtg_sampler_dev.h"
 
 __global__ void __launch_bounds__(1024)
@@ -178,11 +179,18 @@ void mtg_launch_initial_best(int E, int W, int P, const double *coords, const do
 #define MTG_PJ MTG_MAX_J
 
 
+// a row that is not evaluated (outside the prior, or not positive definite) reads back NaN: the host copies every
+// row of the device buffers, whose other contents are left over from earlier work
+__device__ static void mtg_predict_nan_row(const MtgPredictArgs &a, int64_t e)
+{
+    for (int64_t n = 0; n < a.N; ++n) { a.mu[e * a.N + n] = NAN; a.var[e * a.N + n] = NAN; }
+}
+
 __global__ void __launch_bounds__(64) mtg_predict_kernel(MtgPredictArgs a)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.B) return;
-    if (a.status_in[e] != MTG_ST_OK) { a.status[e] = a.status_in[e]; return; }
+    if (a.status_in[e] != MTG_ST_OK) { a.status[e] = a.status_in[e]; mtg_predict_nan_row(a, e); return; }
     const int NR = a.nr0 + 2 * a.sig[e], NC = a.nc0 - a.sig[e], J = NR + 2 * NC;
     const double *cf = a.coef + e;
     const int64_t cs = a.cstride;
@@ -212,9 +220,10 @@ __global__ void __launch_bounds__(64) mtg_predict_kernel(MtgPredictArgs a)
         for (int k = 0; k < NC; ++k) {
             const double p = exp(-cc[k] * dx);
             // at the elapsed time, as celerite does at the absolute one: a (cos, sin) pair rotated
-            // step by step drifts, and an ill-conditioned covariance amplifies the drift
+            // step by step drifts, and an ill-conditioned covariance amplifies the drift.  The phase is
+            // reduced modulo 2 pi before it is rounded (mtg_math.h): d * fl(t - t_first) is not
             double sn, cn;
-            sincos(dc[k] * (t - t_first), &sn, &cn);
+            mtg_elapsed_sincos(dc[k], t, t_first, &sn, &cn);
             ph[NR + 2 * k] = ph[NR + 2 * k + 1] = p;
             U[NR + 2 * k] = ac[k] * cn + bc[k] * sn; U[NR + 2 * k + 1] = ac[k] * sn - bc[k] * cn;
             V[NR + 2 * k] = cn; V[NR + 2 * k + 1] = sn;
@@ -238,7 +247,7 @@ __global__ void __launch_bounds__(64) mtg_predict_kernel(MtgPredictArgs a)
         w[3 * J] = D; w[3 * J + 1] = z;
         Dp = D; zp = z;
     }
-    if (bad) { a.status[e] = MTG_ST_NOTPD; return; }
+    if (bad) { a.status[e] = MTG_ST_NOTPD; mtg_predict_nan_row(a, e); return; }
 
     // ---- backward sweep: alpha = L^-T D^-1 z and diag(K^-1) -------------------------
     double g[MTG_PJ], G[MTG_PJ][MTG_PJ];

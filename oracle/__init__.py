@@ -10,6 +10,9 @@ celerite>=0.4.2 solver it calls):
 * ``oracle.quad``     -- ctypes view of oracle/celerite_quad.c: the one-sweep recurrence
   in __float128 (libquadmath), the quad-precision truth of tests/test_quad_oracle.py and
   tests/golden/quad_golden.json; built on first use (``make -C oracle liboracle_quad.so``)
+* ``oracle.predict``  -- the prediction / solve recurrences of oracle/predict_sweep.h (K^-1 b,
+  diag(K^-1), the conditional mean and variance, new times) in quad through celerite_quad.c,
+  or in float64 through celerite_ref.c: the truth of tests/golden/predict_golden.npz
 
 PARITY STATUS: "parity unpinned" at the lnL boundary for values of kernels with J > 0 (see
 the file headers).  What the reference's notebooks print from celerite is reproduced in

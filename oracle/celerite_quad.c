@@ -288,3 +288,16 @@ ORACLE_API int oracle_quad_build_coeffs(int nterms, const int *kinds, const doub
     *jr_out = k.jr; *jc_out = k.jc; *jitter_out = (double)k.jitter;
     return 0;
 }
+
+/* the prediction and solve recurrences in quad (oracle/predict_sweep.h): oracle_quad_predict_batch,
+ * oracle_quad_apply_inverse, oracle_quad_predict_at -- the truth of tests/golden/predict_golden.npz */
+#define R Q
+#define PS_API ORACLE_API
+#define PS_EXP expq
+#define PS_FABS fabsq
+#define PS_SINCOS sincosq
+#define PS_COEFFS qcoeffs
+#define PS_BUILD build_coeffs_q
+#define PS_NPARAMS nparams
+#define PS_ENTRY(name) oracle_quad_##name
+#include "predict_sweep.h"

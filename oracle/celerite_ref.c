@@ -428,3 +428,35 @@ ORACLE_API int oracle_max_threads(void)
     return 1;
 #endif
 }
+
+/*
+ * The prediction and solve recurrences in float64 (oracle/predict_sweep.h, "c64"): oracle_predict_batch,
+ * oracle_apply_inverse, oracle_predict_at.  The phase is formed as celerite forms it, cos(d t) and sin(d t) at the
+ * absolute time; only tests/ call these.
+ */
+typedef struct {
+    int jr, jc;
+    double ar[32], cr[32], ac[16], bc[16], cc[16], dc[16], jitter;
+} dcoeffs;
+
+static int build_d(int nterms, const int *kinds, const double *extra, const double *p, dcoeffs *k)
+{
+    int jmax = 0;
+    for (int i = 0; i < nterms; ++i) jmax += kinds[i] == K_LORENTZIAN ? 3 : 2;
+    if (jmax > 32) return -1;
+    return oracle_build_coeffs(nterms, kinds, extra, p, &k->jr, k->ar, k->cr, &k->jc, k->ac, k->bc, k->cc, k->dc,
+                               &k->jitter) != 0 ? -1 : 0;
+}
+
+static void sincos_c64(double x, double *s, double *c) { *c = cos(x); *s = sin(x); }
+
+#define R double
+#define PS_API ORACLE_API
+#define PS_EXP exp
+#define PS_FABS fabs
+#define PS_SINCOS sincos_c64
+#define PS_COEFFS dcoeffs
+#define PS_BUILD build_d
+#define PS_NPARAMS oracle_term_nparams
+#define PS_ENTRY(name) oracle_##name
+#include "predict_sweep.h"

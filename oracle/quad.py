@@ -21,8 +21,8 @@ _ip = ctypes.POINTER(ctypes.c_int)
 
 
 def build(force=False):
-    src = os.path.join(_HERE, "celerite_quad.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
+    srcs = [os.path.join(_HERE, f) for f in ("celerite_quad.c", "predict_sweep.h")]
+    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(map(os.path.getmtime, srcs)):
         subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle_quad.so"], stdout=subprocess.DEVNULL)
     return _SO
 

@@ -1,5 +1,6 @@
-"""Loaders for tests/golden/loglike_golden.{json,npz} (made by tests/golden/make_golden.py) and the light curves of
-tests/golden/quad_golden.json (made by tests/golden/make_quad_golden.py)."""
+"""Loaders for tests/golden/loglike_golden.{json,npz} (made by tests/golden/make_golden.py), the light curves of
+tests/golden/quad_golden.json (made by tests/golden/make_quad_golden.py) and the right-hand sides and new times of
+tests/golden/predict_golden.npz (made by tests/golden/make_predict_golden.py)."""
 import hashlib
 import json
 import os
@@ -51,3 +52,39 @@ def lightcurve_sha256(t, y, dy):
     for a in (t, y, dy):
         h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
     return h.hexdigest()
+
+
+def fp32_column(v):
+    """v rounded to float32 (and back): a libm or SIMD path that differs in the last bit of a double gives the same
+    column"""
+    return np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def col_sha(b):
+    return hashlib.sha256(np.ascontiguousarray(b, dtype=np.float64).tobytes()).hexdigest()
+
+
+def apply_columns(t, y, mean_kind, full, nk, kinds, seed):
+    """predict_golden.npz's three right-hand sides [N][3] of a row: the residual y - mean, a standard-normal column and
+    the column k(t_* - t) of K_*^T at t_* inside the largest gap (the last two float32-rounded)"""
+    from oracle import dense
+    N = len(t)
+    mean = full[nk] * t + full[nk + 1] if mean_kind == 1 else np.full(N, full[nk])
+    g = int(np.argmax(np.diff(t)))
+    ts = t[g] + 0.375 * (t[g + 1] - t[g])
+    kcol = fp32_column(dense.kernel_value(dense.build_coeffs(kinds, full[:nk]), ts - t))
+    normal = fp32_column(np.random.default_rng(seed).standard_normal(N))
+    return np.column_stack([y - mean, normal, kcol])
+
+
+def new_times(t, seed):
+    """predict_golden.npz's 48 new times: 24 between samples, 12 on samples, 6 before the first and 6 after the last"""
+    rng = np.random.default_rng(seed)
+    N = len(t)
+    span = t[-1] - t[0]
+    i = rng.choice(N - 1, 24, replace=False)
+    between = t[i] + rng.uniform(0.1, 0.9, 24) * (t[i + 1] - t[i])
+    on = t[rng.choice(N, 12, replace=False)]
+    before = t[0] - span * np.array([1e-4, 1e-3, 1e-2, 0.05, 0.2, 1.0])
+    after = t[-1] + span * np.array([1e-4, 1e-3, 1e-2, 0.05, 0.2, 1.0])
+    return np.sort(np.concatenate([between, on, before, after]))
