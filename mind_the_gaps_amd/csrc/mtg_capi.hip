@@ -1,6 +1,7 @@
 // mtg_capi.hip -- host side of the C-ABI declared in include/mtg.h.
 // One context = one MI355X + resident light curves + model + workspaces.
 #include "mtg_device.h"
+#include "mtg_solve_plan.h"
 #include "mtg_tp_scan.h"
 #include "mtg_trace.h"
 
@@ -445,13 +446,6 @@ int run_model_batch(mtg_ctx *ctx, int64_t B, const double *d_theta, const int32_
     return MTG_OK;
 }
 
-// MTG_SWEEP_MULTI=0 (MTG_MEASURE builds only): one launch per structure even where the one-launch kernel exists
-bool sweep_multi_enabled()
-{
-    static const bool on = !(mtg_measure_env("MTG_SWEEP_MULTI") && atoi(mtg_measure_env("MTG_SWEEP_MULTI")) == 0);
-    return on;
-}
-
 // A pipelined half-step of a paired context (MtgPair): *paired = 1 when its rows went out -- or will go out, ordered
 // before anything that follows on `s` -- in a launch shared with the partner's; 0: the caller launches alone.
 int pair_launch(mtg_ctx *ctx, const MtgSolveArgs &sa, int64_t B, const MtgPipeShapeId &shape, hipStream_t s, int *paired)
@@ -525,9 +519,6 @@ int pair_launch(mtg_ctx *ctx, const MtgSolveArgs &sa, int64_t B, const MtgPipeSh
     return MTG_OK;
 }
 
-// Launch the solver(s) for B prepared evaluations living in ctx->coef (lists / counts filled).
-// may_sort: the caller's order is arbitrary (mtg_loglike_batch[_device]); the device sampler's batches are grouped
-// by ensemble, hence by light curve, by construction.
 // What every solver launch of B prepared evaluations takes: the resident light curves, the coefficient columns, the
 // context's tables (made at the first call).
 int solve_args_base(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out, int32_t *d_status, hipStream_t s, MtgSolveArgs &sa)
@@ -567,6 +558,95 @@ int solve_args_base(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out,
     return MTG_OK;
 }
 
+// an MTG_MEASURE knob's value (shipped builds, or the variable not set: `unset`)
+long measure_knob(const char *name, long unset)
+{
+    const char *v = mtg_measure_env(name);
+    return v ? atol(v) : unset;
+}
+
+// the compiled shapes, as the planner asks for them
+const MtgCatalogue g_catalogue = {
+    [](int nr, int nc, int b0) { return mtg_find_solver(nr, nc, b0) != nullptr; },
+    mtg_solver_uses_b0,
+    [](int nr, int nc) { return mtg_find_tp_solver(nr, nc) != nullptr; },
+    [](int nr, int nc) { return mtg_find_tp_wide_solver(nr, nc) != nullptr; },
+    [](int nr0, int nc0, int nsig, int lanes) { return mtg_find_tp_fused_solver(nr0, nc0, nsig, lanes) != nullptr; },
+    [](int nr0, int nc0, int nsig, int b0) { return mtg_find_pipe_solver(nr0, nc0, nsig, b0) != nullptr; },
+    [](int nr0, int nc0, int nsig, int b0) { return mtg_find_multi_solver(nr0, nc0, nsig, b0) != nullptr; },
+};
+
+// what the planner sees of B prepared evaluations (may_sort: see solve_prepared)
+MtgPlanIn plan_input(const mtg_ctx *ctx, int64_t B, bool may_sort, const MtgSolveArgs &sa)
+{
+    const MtgModel &m = ctx->model;
+    MtgPlanIn in;
+    in.N = ctx->N; in.B = B; in.L = ctx->L;
+    in.Bw = ctx->live_rows > 0 ? ctx->live_rows : B;
+    in.nr0 = m.nr0; in.nc0 = m.nc0; in.nsig = m.nsho + 1; in.last_b0 = m.last_b0;
+    in.tp_mode = ctx->tp_mode; in.pipe_mode = ctx->pipe_mode; in.sort_mode = ctx->sort_mode;
+    in.may_sort = may_sort;
+    in.lc_grouped_hint = ctx->lc_grouped_hint != 0;
+    in.no_prior_batch = ctx->no_prior_batch;
+    for (int i = 0; i < m.nterms; ++i) in.free_b = in.free_b || m.kinds[i] == MTG_TERM_COMPLEX4 || m.kinds[i] == MTG_TERM_BPL;
+    in.in_window = sa.yv_bytes <= sa.window_bytes;
+    in.cus = ctx->cus;
+    in.sweep_multi = measure_knob("MTG_SWEEP_MULTI", 1) != 0;
+    in.sweep_fan_out = measure_knob("MTG_SWEEP_FANOUT", 1) != 0;
+    in.tp_gsize = (int)measure_knob("MTG_TP_GSIZE", 0);
+    in.tp_chunk_target = measure_knob("MTG_TP_CHUNK_TARGET", 0);
+    return in;
+}
+
+// The structures of an MTG_SOLVE_STRUCTURES plan, each on the stream the plan gives it, joined on `s`.  The side
+// streams first: their (usually few) waves are resident before the common structure's launch fills every slot its
+// registers allow (J = 6: two waves of 204 VGPRs leave no room for a third of 166).
+int launch_structures(mtg_ctx *ctx, const MtgSolvePlan &plan, MtgSolveArgs &sa, const int *sorted, int64_t B, hipStream_t s)
+{
+    const MtgModel &m = ctx->model;
+    const int nsig = m.nsho + 1;
+    if (plan.fan_out) {
+        if (!ctx->fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming));
+        int prio_low = 0, prio_high = 0;
+        HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
+        for (int k = 0; k + 1 < nsig; ++k) {
+            // (above the caller's stream: the few rows of a rare structure should not queue behind the common one)
+            if (!ctx->side[k]) HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->side[k], hipStreamNonBlocking, prio_high));
+            if (!ctx->side_done[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->side_done[k], hipEventDisableTiming));
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->fork, s));
+    }
+    for (int kk = 0; kk < nsig; ++kk) {
+        const int k = plan.fan_out ? nsig - 1 - kk : kk;
+        const int nr = m.nr0 + 2 * k, nc = m.nc0 - k;
+        if (plan.kernel[k] == MTG_STRUCT_NONE) continue;
+        sa.list = nsig > 1 ? bank_lists(ctx) + (int64_t)k * ctx->cstride : nullptr;
+        sa.count_ptr = nsig > 1 ? bank_counts(ctx) + k : nullptr;
+        sa.seg_counts = nullptr; sa.seg_k = 0;
+        if (sorted && plan.kernel[k] == MTG_STRUCT_SWEEP) {  // the k-th segment of the sorted order
+            sa.list = sorted;
+            sa.seg_counts = nsig > 1 ? bank_counts(ctx) : nullptr;
+            sa.seg_k = k;
+        }
+        const hipStream_t sk = plan.side[k] < 0 ? s : ctx->side[plan.side[k]];
+        if (sk != s) HIP_TRY(ctx, hipStreamWaitEvent(sk, ctx->fork, 0));
+        if (plan.kernel[k] == MTG_STRUCT_SWEEP) {
+            const int rc = sweep_launch(ctx, mtg_find_solver(nr, nc, m.last_b0), sa, B, k, sk);
+            if (rc) return rc;
+        } else {
+            sa.solo = 0; sa.left_list = nullptr; sa.left_count = nullptr;
+            (plan.kernel[k] == MTG_STRUCT_TP_WIDE ? mtg_find_tp_wide_solver(nr, nc) : mtg_find_tp_solver(nr, nc))(sa, B, sk);
+        }
+        if (sk != s) HIP_TRY(ctx, hipEventRecord(ctx->side_done[plan.side[k]], sk));
+    }
+    for (int k = 1; k < nsig; ++k)
+        if (plan.side[k] >= 0 && plan.kernel[k] != MTG_STRUCT_NONE) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->side_done[plan.side[k]], 0));
+    return MTG_OK;
+}
+
+// Launch the solver(s) for B prepared evaluations living in ctx->coef (lists / counts filled), as mtg_plan_solve
+// (mtg_solve_plan.h) decides.  may_sort: the caller's order is arbitrary (mtg_loglike_batch[_device]); the device
+// sampler's batches are grouped by ensemble, hence by light curve, by construction.
 int solve_prepared(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out, int32_t *d_status, hipStream_t s, bool may_sort)
 {
     const MtgModel &m = ctx->model;
@@ -576,95 +656,21 @@ int solve_prepared(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out, 
         const int rc = solve_args_base(ctx, B, d_lc, d_out, d_status, s, sa);
         if (rc) return rc;
     }
-    // A small batch of long light curves leaves a one-lane-per-evaluation launch idle for N serial
-    // steps: give every evaluation a whole wave (or four) instead (mtg_timeparallel.hip); the rank-10
-    // structures get as many chunks per evaluation as fill the GPU (mtg_tp_big.h).
-    // Measured crossovers: J <= 6 (one workgroup per evaluation) pays up to several thousand evaluations -- the serial
-    // sweep runs one wave per 64 evaluations, latency bound, on a fraction of the SIMDs until ~10^5 of them; the J = 10
-    // path costs ~3 x the serial sweep's work per sample, spread over every SIMD instead of B / 64 of
-    // them, against ~1.05 us x N for the serial sweep whatever B <= 65 536 is.
-    const int Jmodel = m.nr0 + 2 * m.nc0;
-    // rows that do work: a walker-sharded half-step skips the rows of the other ranks (MTG_ST_REMOTE)
-    const int64_t Bw = ctx->live_rows > 0 ? ctx->live_rows : B;
-    bool pays;
-    // (scripts/crossover_probe.py, serial sweep / time-parallel in ms: N = 1e4, J = 5: 3.4 / 0.35 at 1024 evaluations,
-    // 3.4 / 1.0 at 4096, 3.4 / 1.8 at 8192, equal at 16 384; N = 1e3, J = 5: 0.36 / 0.29 at 4096, 0.36 / 0.51 at 8192)
-    // (round 4, against the pipelined sweep that now takes over beyond: scripts/pipe_probe.py, N = 1e4, time-parallel / pipeline
-    // in ms: J = 3: 0.82 / 1.37 at 8192 rows, 1.20 / 1.39 at 12 288, 1.51 / 1.40 at 16 000; J = 5: 1.85 / 2.40 at 8192, 2.73 / 2.46 at 12 288)
-    if (Jmodel <= 6) pays = ctx->N >= 256 && Bw <= (ctx->N >= 4096 ? (Jmodel <= 3 ? 12288 : 8192) : 4096);
-    else pays = ctx->N >= 1024 && Bw <= 8192;
-    // A term with a free b (ComplexTerm with four parameters, BendingPowerlaw) has a power spectrum that goes negative
-    // where b d > a c -- which is exactly what those terms' own log_prior forbids, so a batch expanded WITH the prior never
-    // solves such a row.  Without it (the optimiser's -lnL, gpmodelling.py:155-169) it may, and there the state-space form
-    // the time-parallel kernels work in has an indefinite stationary covariance: their filter pass was found 1e-7 off on
-    // such a row (tests/test_fuzz_gpu.py at MTG_FUZZ_OFFSET=112000, case 70; scripts/fuzz_case.py) where celerite's own
-    // recursion -- the sweep -- is exact to rounding.  Those batches keep the sweep.
-    bool free_b = false;
-    for (int i = 0; i < m.nterms; ++i) free_b = free_b || m.kinds[i] == MTG_TERM_COMPLEX4 || m.kinds[i] == MTG_TERM_BPL;
-    const bool tp_allowed = !(free_b && ctx->no_prior_batch);
-    const bool small = tp_allowed && (ctx->tp_mode == 1 || ctx->tp_mode == 3 || (ctx->tp_mode == 2 && pays));
+    const MtgPlanIn in = plan_input(ctx, B, may_sort && d_lc, sa);
+    MtgSolvePlan plan = mtg_plan_solve(in, g_catalogue);
     sa.tp_ws = nullptr;
-    sa.tp_chunks = 0;
-    sa.tp_gsize = 0;
+    sa.tp_chunks = plan.tp_chunks;
+    sa.tp_gsize = plan.tp_gsize;
     sa.tp_direct = ctx->tp_direct;
     sa.tp_nr0 = m.nr0; sa.tp_nc0 = m.nc0;
     sa.sig = ctx->sig.as<int32_t>();
-    bool small_ok = small;
-    // mode 3 promises bits that do not depend on the batch; the rank-10 path sizes its chunks and scan groups by the
-    // batch (mtg_tp_big_chunks), so under mode 3 such a model keeps the serial sweep
-    if (ctx->tp_mode == 3 && Jmodel > 6) small_ok = false;
-    if (Jmodel == 0) small_ok = false;  // a white kernel: nothing to parallelise over time (mtg_white_kernel)
-    if (small_ok && Jmodel > 6) {
-        for (int k = 0; k < nsig; ++k)
-            if (!mtg_find_tp_solver(m.nr0 + 2 * k, m.nc0 - k)) small_ok = false;
-        const int C = mtg_tp_big_chunks(ctx->N, Bw);
-        int g = mtg_tp_big_gsize(Bw, C);
-        if (const char *env = mtg_measure_env("MTG_TP_GSIZE")) {  // MTG_MEASURE builds only
-            const int v = atoi(env);
-            if (v == 4 || v == 8 || v == 16) g = v;
-        }
-        const size_t need = (size_t)mtg_tp_big_plan(Jmodel, B, C, g).total * sizeof(double);
-        if (B > 65535 || need > ((size_t)16 << 30)) small_ok = false;  // grid / workspace limits: the serial sweep
-        if (small_ok) {
-            HIP_TRY(ctx, ctx->tp_ws.reserve(need));
-            sa.tp_ws = ctx->tp_ws.as<double>();
-            sa.tp_chunks = C;
-            sa.tp_gsize = g;
-        }
-    }
-    // four waves per evaluation: while every evaluation's workgroup is resident at once (rank <= 3: two per CU, their
-    // elements take 68 KB of LDS; above: one)
-    // (scripts/spec_probe.py, J = 3, N = 1e4: 384 rows 70.9 us against 96.0 us with one wave each, 512 rows 77.4 / 97.2)
-    // (mode 3: the one-wave kernel whatever the batch, so that a row's bits do not depend on how many rows travel with it)
-    const bool wide = ctx->tp_mode != 3 && Bw <= (Jmodel <= 3 ? 512 : 256) && ctx->N >= 4096;
-    // two waves per evaluation between 257 and 512 rows of rank 4 or 5: half a CU's LDS each, all resident at once
-    // (scripts/spec_probe.py, J = 5, N = 1e4, 384 rows: see DESIGN.md)
-    const bool mid = ctx->tp_mode != 3 && !wide && Bw <= 512 && ctx->N >= 4096 && (Jmodel == 4 || Jmodel == 5);
-    // Between the time-parallel kernels' range and ~one wave per SIMD the serial sweep is one lone wave per 64 rows on
-    // a fraction of the SIMDs, N dependent steps of ~166 instructions: the pipelined form puts the generators of those
-    // rows on a second wave (mtg_kernels_pipe.hip) -- one workgroup of 128 rows per CU, all resident at once.
-    mtg_solve_launcher pipe = nullptr;
-    if (!small_ok && ctx->pipe_mode != 0 && ctx->N >= 64 && sa.yv_bytes <= sa.window_bytes &&
-        (ctx->pipe_mode == 1 || (ctx->N >= 256 && B <= (int64_t)MTG_PIPE_ROWS_PER_CU * ctx->cus)))
-        pipe = mtg_find_pipe_solver(m.nr0, m.nc0, nsig, m.last_b0);
-    mtg_solve_launcher fused = nullptr;
-    int fused_lanes = 64;
-    if (small_ok && nsig > 1) {
-        if (wide && (fused = mtg_find_tp_fused_solver(m.nr0, m.nc0, nsig, 256))) fused_lanes = 256;
-        if (!fused && mid && (fused = mtg_find_tp_fused_solver(m.nr0, m.nc0, nsig, 128))) fused_lanes = 128;
-        if (!fused) fused = mtg_find_tp_fused_solver(m.nr0, m.nc0, nsig, 64);
+    if (plan.tp_ws_bytes) {
+        HIP_TRY(ctx, ctx->tp_ws.reserve(plan.tp_ws_bytes));
+        sa.tp_ws = ctx->tp_ws.as<double>();
     }
     sa.solo = 0; sa.left_list = nullptr; sa.left_count = nullptr;
-    // The serial sweep reads each lane's own light curve: sort the evaluations by (structure, light curve) unless the
-    // caller's order is known to be grouped (mtg_sort.hip).  One light curve, or no index at all: nothing to sort.
-    // More than one structure: the per-structure lists are appended to with one atomic per wave, so their order -- which
-    // rows share a wave -- changes from run to run, and a row's last bits may depend on its wave (a lane with a huge
-    // d dx sends the whole wave through the libm sincos).  A seeded chain has to be reproducible: the stable sort gives
-    // the lanes of every structure the caller's order, whatever the arrival order of the waves was.
     const int *sorted = nullptr;
-    const bool for_order = may_sort && d_lc && ctx->L > 1 && (ctx->sort_mode == 1 || (ctx->sort_mode == 2 && !ctx->lc_grouped_hint));
-    const bool for_determinism = nsig > 1 && ctx->sort_mode != 0;
-    if ((for_order || for_determinism) && !small_ok && B > 64 && (uint64_t)ctx->L * (uint64_t)nsig < 0x7fffffffull) {
+    if (plan.sort) {
         mtg_trace::Range range("mtg:sort (evaluations by structure, light curve)");
         const size_t tmp = mtg_sort_temp_bytes(B, mtg_sort_key_bits(ctx->L, nsig));
         HIP_TRY(ctx, ctx->sort_keys.reserve((size_t)B * 4));
@@ -676,102 +682,45 @@ int solve_prepared(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out, 
                                                    ctx->sort_order.as<int>(), ctx->sort_tmp.p, tmp, s));
         sorted = ctx->sort_order.as<int>();
     }
-    if (small_ok && Jmodel > 6) {  // rank 10: every structure in one sequence of launches (mtg_tp_big.h)
+    switch (plan.family) {
+    case MTG_SOLVE_TP_BIG:
         sa.list = nullptr;
         sa.count_ptr = nullptr;
-        snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_tpb_compose4q_kernel (+ mtg_tpb_reduce_kernel<10>, C = %d)",
-                 sa.tp_chunks);
         mtg_launch_tp_big(sa, B, s);
-    } else if (fused) {  // every signature in one launch
+        break;
+    case MTG_SOLVE_TP_FUSED:
         sa.list = bank_lists(ctx);
         sa.count_ptr = bank_counts(ctx);
-        snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_tp_fused_kernel<%d,%d,%d,%d>", m.nr0, m.nc0, nsig, fused_lanes);
-        fused(sa, B, s);
-    } else if (pipe && (nsig == 1 || sorted)) {
+        mtg_find_tp_fused_solver(m.nr0, m.nc0, nsig, plan.fused_lanes)(sa, B, s);
+        break;
+    case MTG_SOLVE_PIPE: {
         sa.list = sorted;            // nsig == 1: the sorted order, or NULL = the caller's
         sa.count_ptr = nullptr;
         sa.seg_counts = nsig > 1 ? bank_counts(ctx) : nullptr;
         sa.seg_k = 0;
-        const MtgPipeShapeId shape{m.nr0, m.nc0, nsig, m.last_b0 ? 1 : 0};
         int paired = 0;
         if (std::atomic_load(&ctx->pair)) {
-            const int rc = pair_launch(ctx, sa, B, shape, s, &paired);
+            const int rc = pair_launch(ctx, sa, B, MtgPipeShapeId{m.nr0, m.nc0, nsig, m.last_b0 ? 1 : 0}, s, &paired);
             if (rc) return rc;
         }
-        if (paired) {
-            snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_pipe_pair_kernel (this model: <%d,%d,%d,%d>)", m.nr0, m.nc0, nsig, m.last_b0 ? 1 : 0);
-        } else {
-            snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_pipe_kernel<%d,%d,%d,%d>", m.nr0, m.nc0, nsig, m.last_b0 ? 1 : 0);
-            pipe(sa, B, s);
-        }
-    } else if (mtg_solve_launcher multi = sorted && nsig > 1 && sa.yv_bytes <= sa.window_bytes && sweep_multi_enabled()
-                                              ? mtg_find_multi_solver(m.nr0, m.nc0, nsig, m.last_b0) : nullptr) {
-        // every structure of the sorted order in one launch of identical workgroups (mtg_kernels_multi.hip)
+        if (paired) mtg_plan_name_paired(plan, in);
+        else mtg_find_pipe_solver(m.nr0, m.nc0, nsig, m.last_b0)(sa, B, s);
+        break;
+    }
+    case MTG_SOLVE_MULTI:
         sa.list = sorted;
         sa.count_ptr = nullptr;
         sa.seg_counts = bank_counts(ctx);
         sa.seg_k = 0;
-        snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_solve_kernel_multi<%d,%d,%d,%d>", m.nr0, m.nc0, nsig, m.last_b0 ? 1 : 0);
-        multi(sa, B, s);
-    } else {
-        // A time-parallel launch is latency bound: a structure holding three evaluations takes as long
-        // as one holding 250 (J = 10: ~10 ms each), and one after the other on the same stream they
-        // add up.  The structures work on disjoint evaluations, so each gets its own stream: forked
-        // after the expansion, joined before whatever follows on `s`.
-        // The serial sweep is latency bound in the same way -- N dependent steps, ~0.4 us each, whatever the number of
-        // rows -- and a sampler's half-step of 256 000 walkers with a handful of them over-damped paid 14.9 ms for
-        // the first structure and 3.2-4.3 ms more for those few (profiles/r03_c3_halfstep_trace.txt).  On their own
-        // stream they take wave slots as the big launch frees them and finish under it.
-        static const bool sweep_fan_out = !(mtg_measure_env("MTG_SWEEP_FANOUT") && atoi(mtg_measure_env("MTG_SWEEP_FANOUT")) == 0);
-        const bool fan_out = (small_ok || sweep_fan_out) && nsig > 1 && nsig - 1 <= MTG_MAX_J / 2;
-        if (fan_out) {
-            if (!ctx->fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming));
-            int prio_low = 0, prio_high = 0;
-            HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
-            for (int k = 0; k + 1 < nsig; ++k) {
-                // (above the caller's stream: the few rows of a rare structure should not queue behind the common one)
-                if (!ctx->side[k]) HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->side[k], hipStreamNonBlocking, prio_high));
-                if (!ctx->side_done[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->side_done[k], hipEventDisableTiming));
-            }
-            HIP_TRY(ctx, hipEventRecord(ctx->fork, s));
-        }
-        // the side streams first: their (usually few) waves are resident before the common structure's launch fills
-        // every slot its registers allow (J = 6: two waves of 204 VGPRs leave no room for a third of 166)
-        for (int kk = 0; kk < nsig; ++kk) {
-            const int k = fan_out ? nsig - 1 - kk : kk;
-            const int nr = m.nr0 + 2 * k, nc = m.nc0 - k;
-            mtg_solve_launcher fn = mtg_find_solver(nr, nc, m.last_b0);
-            if (!fn) continue;
-            mtg_solve_launcher tp = small_ok ? mtg_find_tp_solver(nr, nc) : nullptr;
-            if (tp && wide && mtg_find_tp_wide_solver(nr, nc)) tp = mtg_find_tp_wide_solver(nr, nc);
-            sa.list = nsig > 1 ? bank_lists(ctx) + (int64_t)k * ctx->cstride : nullptr;
-            sa.count_ptr = nsig > 1 ? bank_counts(ctx) + k : nullptr;
-            sa.seg_counts = nullptr; sa.seg_k = 0;
-            if (sorted && !tp) {  // the k-th segment of the sorted order
-                sa.list = sorted;
-                sa.seg_counts = nsig > 1 ? bank_counts(ctx) : nullptr;
-                sa.seg_k = k;
-            }
-            if (k == 0) {
-                if (tp) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_tp_kernel<%d,%d,%d>", nr, nc, tp == mtg_find_tp_solver(nr, nc) ? 64 : 256);
-                else if (nr + nc == 0) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_white_kernel");
-                else snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_solve_kernel<%d,%d,%d>", nr, nc, mtg_solver_uses_b0(nr, nc, m.last_b0));
-            }
-            hipStream_t sk = fan_out && k > 0 ? ctx->side[k - 1] : s;
-            if (sk != s) HIP_TRY(ctx, hipStreamWaitEvent(sk, ctx->fork, 0));
-            if (tp) {
-                sa.solo = 0; sa.left_list = nullptr; sa.left_count = nullptr;
-                tp(sa, B, sk);
-            } else {
-                const int rc = sweep_launch(ctx, fn, sa, B, k, sk);
-                if (rc) return rc;
-            }
-            if (sk != s) HIP_TRY(ctx, hipEventRecord(ctx->side_done[k - 1], sk));
-        }
-        if (fan_out)
-            for (int k = 1; k < nsig; ++k)
-                if (mtg_find_solver(m.nr0 + 2 * k, m.nc0 - k, m.last_b0)) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->side_done[k - 1], 0));
+        mtg_find_multi_solver(m.nr0, m.nc0, nsig, m.last_b0)(sa, B, s);
+        break;
+    case MTG_SOLVE_STRUCTURES: {
+        const int rc = launch_structures(ctx, plan, sa, sorted, B, s);
+        if (rc) return rc;
+        break;
     }
+    }
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "%s", plan.name);
     HIP_TRY(ctx, hipGetLastError());
     return MTG_OK;
 }
@@ -1246,8 +1195,7 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
     sa.sig = nullptr;
     ctx->timed = true;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    if (jr + jc == 0) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_white_kernel (coefficients)");
-    else snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_solve_kernel<%d,%d,0> (coefficients)", jr, jc);
+    mtg_struct_kernel_name(ctx->last_solver, sizeof ctx->last_solver, MTG_STRUCT_SWEEP, jr, jc, 0, " (coefficients)");
     rc = sweep_launch(ctx, fn, sa, B, 0, s);
     if (rc) return rc;
     HIP_TRY(ctx, hipGetLastError());
@@ -1627,10 +1575,9 @@ MTG_API int mtg_ensemble_run(mtg_ctx *ctx, int steps, double *chain, double *lnp
     // with every row on a workgroup of its own in one occupancy round -- 256 workgroups of four waves for long light
     // curves (one per CU: their elements fill the LDS; two per CU up to rank 3, and for ranks 4 and 5 with two waves
     // each), 1024 single-wave ones for short.  Same chain either way where both forms run the same kernel.
-    const int Jmodel = ctx->model.nr0 + 2 * ctx->model.nc0;
     const int64_t rows3 = 3 * EH;
-    const bool spec = steps > 0 && ctx->spec_mode != 0 && !sharded && ctx->tp_mode != 0 && Jmodel <= 6 && ctx->N >= 256 &&
-                      rows3 <= (ctx->N >= 4096 ? (Jmodel <= 5 ? 512 : 256) : 1024);
+    const bool spec = steps > 0 && ctx->spec_mode != 0 && !sharded &&
+                      mtg_plan_speculate(ctx->tp_mode, ctx->model.nr0 + 2 * ctx->model.nc0, ctx->N, rows3);
     if (spec) {
         rc = check_model_workspace(ctx, rows3);
         if (rc) return rc;

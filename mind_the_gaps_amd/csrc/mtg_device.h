@@ -170,7 +170,6 @@ mtg_solve_launcher mtg_find_multi_solver(int nr0, int nc0, int nsig, int last_b0
 // leave the one-lane-per-evaluation launch a single wave on half of the SIMDs; nsig = 1: list / count_ptr as for
 // mtg_find_solver's kernels, nsig > 1: the sorted order and seg_counts as for mtg_find_multi_solver's
 mtg_solve_launcher mtg_find_pipe_solver(int nr0, int nc0, int nsig, int last_b0);
-#define MTG_PIPE_ROWS_PER_CU 128
 // two models' pipelined sweeps in ONE launch (mtg_kernels_pipe_pair.hip): a workgroup of eight waves runs a quartet of
 // each, two waves per SIMD sharing one table set; shapes as for mtg_find_pipe_solver; NULL = this pair is not compiled
 struct MtgPipeShapeId { int nr0, nc0, nsig, last_b0; };

@@ -31,82 +31,9 @@
 //   state:   m[J] | P[J][J]                                   MTG_TPB_STATE(J) doubles
 #pragma once
 #include "mtg_device.h"
+#include "mtg_solve_plan.h"   // MtgTpBigPlan and the chunk / group sizes of the rank-10 path
 
-#include <stdlib.h>
-
-#define MTG_TPB_ELEM(J) (3 * (J) * (J) + 2 * (J))
-#define MTG_TPB_STATE(J) ((J) * (J) + (J))
 #define MTG_TPB_LANES 16    /* lanes per lane group */
-#define MTG_TPB_MAX_LEVELS 8
-
-// Workspace of the big-J path, in doubles from a.tp_ws: element and state arrays per scan level,
-// per-chunk partial sums of the final filter pass, per-evaluation head (sample 0).
-#define MTG_TPB_TOP 4        /* elements per evaluation at the top level */
-struct MtgTpBigPlan {
-    int C;                         // chunks per evaluation (a power of two >= 64)
-    int g;                         // elements per scan group (4 or 16), fewer where a level has less than 4 g
-    int nlev;                      // scan levels; level 0 = the chunks, level nlev - 1 has MTG_TPB_TOP elements
-    int n[MTG_TPB_MAX_LEVELS];     // elements per evaluation at each level
-    int gl[MTG_TPB_MAX_LEVELS];    // group size that takes level l to level l + 1
-    int64_t elem_off[MTG_TPB_MAX_LEVELS], state_off[MTG_TPB_MAX_LEVELS];
-    int64_t rec_off[MTG_TPB_MAX_LEVELS];   // likelihood records of the levels >= 1 (level 0: the parts array)
-    int64_t part_off, head_off, redo_off, total;
-};
-
-static inline MtgTpBigPlan mtg_tp_big_plan(int J, int64_t B, int C, int g)
-{
-    MtgTpBigPlan p;
-    p.C = C;
-    p.g = g;
-    p.nlev = 0;
-    int64_t off = 0;
-    for (int n = C;;) {
-        const int l = p.nlev++;
-        p.n[l] = n;
-        p.elem_off[l] = off; off += B * n * MTG_TPB_ELEM(J);
-        p.state_off[l] = off; off += B * n * MTG_TPB_STATE(J);
-        p.rec_off[l] = off; off += l > 0 ? B * n * 4 : 0;
-        p.gl[l] = 0;
-        if (n <= MTG_TPB_TOP || p.nlev == MTG_TPB_MAX_LEVELS) break;
-        p.gl[l] = g < n / MTG_TPB_TOP ? g : n / MTG_TPB_TOP;   // (C is a power of two >= 64: ends on exactly four)
-        n /= p.gl[l];
-    }
-    p.part_off = off; off += B * C * 4;
-    p.head_off = off; off += B * 4;
-    // evaluations sent back through the filter pass (mtg_tp_big.h): int list + counter
-    p.redo_off = off; off += (B + 16) / 2 + 1;
-    p.total = off;
-    return p;
-}
-
-// chunks per evaluation: enough (chunk, evaluation) pairs to fill the GPU ONCE -- the composition kernel gives 64
-// chunks to a workgroup of two waves, one per SIMD, two workgroups to a CU: 512 x 64 = 32 768 chunks in flight --, at
-// least 64, at most 4096, and no chunk shorter than ~24 samples.  (Round 2 asked for 65 536: two rounds of
-// workgroups with chunks half as long take the composition exactly as long, and leave the scan twice the elements.)
-static inline int mtg_tp_big_chunks(int64_t N, int64_t B)
-{
-    // chunks over the whole batch: two waves per SIMD in the composition (32 768), one for the smallest batches, whose up-sweep
-    // is then half as long (scripts/c5_chunk_target.sh, N = 2e5, ms per half-step at 32 768 / 16 384: 8 rows 0.311 / 0.265,
-    // 16 rows 0.385 / 0.349, 32 rows 0.540 / 0.534, 64 rows 0.843 / 0.876, 256 rows 2.66 / 2.87)
-    int64_t target = B <= 16 ? 16384 : 32768;
-    if (const char *env = mtg_measure_env("MTG_TP_CHUNK_TARGET")) {  // MTG_MEASURE builds only: the chunk count decides a result's bits
-        const long v = atol(env);
-        if (v >= 64) target = v;
-    }
-    int C = 64;
-    while (C < 4096 && (int64_t)C * B < target && (int64_t)C * 2 * 24 <= N) C *= 2;
-    return C;
-}
-
-// elements per scan group.  A group is one wave's chain of g - 1 dependent combinations (6.5 us each when the wave
-// has a SIMD to itself, ~1 us of LDS traffic per CU when the GPU is full): the number of combinations of the whole
-// scan is the number of elements whatever g is, so the short chains of g = 4 cost nothing but a launch per level
-// (~5 us) and cut the depth from 15 to 3 combinations per level.
-static inline int mtg_tp_big_gsize(int64_t B, int C)
-{
-    (void)B; (void)C;
-    return 4;
-}
 
 // up-sweep; kappa != 0: every group (the last one's total too) and the likelihood records; zero_me: an int the first
 // level's first workgroup clears (the redo counter), or NULL

@@ -1,6 +1,7 @@
 """Loaders for tests/golden/loglike_golden.{json,npz} (made by tests/golden/make_golden.py), the light curves of
-tests/golden/quad_golden.json (made by tests/golden/make_quad_golden.py) and the right-hand sides and new times of
-tests/golden/predict_golden.npz (made by tests/golden/make_predict_golden.py)."""
+tests/golden/quad_golden.json (made by tests/golden/make_quad_golden.py), the right-hand sides and new times of
+tests/golden/predict_golden.npz (made by tests/golden/make_predict_golden.py) and the calls of
+tests/golden/solve_dispatch.json (made by tests/golden/make_solve_dispatch_golden.py)."""
 import hashlib
 import json
 import os
@@ -75,6 +76,45 @@ def apply_columns(t, y, mean_kind, full, nk, kinds, seed):
     kcol = fp32_column(dense.kernel_value(dense.build_coeffs(kinds, full[:nk]), ts - t))
     normal = fp32_column(np.random.default_rng(seed).standard_normal(N))
     return np.column_stack([y - mean, normal, kcol])
+
+
+FULL_WINDOW = 0xFFFFFFFF   # mtg_set_window_bytes' default
+
+
+def dispatch_case(eng, case):
+    """One call of a solve_dispatch.json case on ``eng``; returns eng.last_solver.  Only the shapes, the modes and the
+    order of lc_index decide the kernel, so the values are whatever synthetic.py draws."""
+    from mind_the_gaps_amd import synthetic as synth
+    N, L, B = case["N"], case["L"], case["B"]
+    t, y, dy = synth.make_lightcurves(N, L, seed=N + L)
+    rng = np.random.default_rng(B)
+    lc = {"random": lambda: rng.integers(0, L, B).astype(np.int32),
+          "grouped": lambda: np.sort(rng.integers(0, L, B)).astype(np.int32),
+          "none": lambda: None}[case["lc"]]()
+    eng.set_window_bytes(FULL_WINDOW)
+    eng.set_lightcurves(t, y, dy + 1e-12)
+    eng.set_time_parallel(case["tp"])
+    eng.set_pipeline(case["pipe"])
+    eng.set_sort(case["sort"])
+    try:
+        if case.get("window"):
+            eng.set_window_bytes(case["window"])
+        if case["op"] == "coeffs":
+            jr, jc = case["jr"], case["jc"]
+            eng.loglike_coeffs(np.full((B, jr), 2.0), np.full((B, jr), 0.3), np.full((B, jc), 1.5), np.zeros((B, jc)),
+                               np.full((B, jc), 0.2), np.full((B, jc), 0.9), jitter=np.full(B, 0.5),
+                               mean_params=np.full((B, 1), 100.0), lc_index=lc)
+        else:
+            kinds = case["kinds"]
+            full, free, bounds = synth.model_spec(kinds, y)
+            eng.set_model(kinds, full, free, bounds)
+            eng.loglike(synth.draw_thetas(kinds, B, seed=B, percent=0.05), lc, add_prior=case["add_prior"])
+        return eng.last_solver
+    finally:
+        eng.set_window_bytes(FULL_WINDOW)
+        eng.set_time_parallel(2)
+        eng.set_pipeline(2)
+        eng.set_sort(2)
 
 
 def new_times(t, seed):

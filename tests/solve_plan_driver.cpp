@@ -1,0 +1,79 @@
+// Runs the solve planner (mind_the_gaps_amd/csrc/mtg_solve_plan.h) on the host for tests/test_solve_plan_cpu.py: one
+// case per line of standard input as key=value tokens, one line of the plan's decisions per case.  The catalogue is a
+// stub with the compiled ranges of the library; `no=<shape>` takes one kind of kernel out of it.
+#include "mtg_solve_plan.h"
+
+#include <iostream>
+#include <sstream>
+#include <string>
+
+namespace {
+
+std::string g_missing;   // the kernels a case takes out of the catalogue
+bool missing(const char *what) { return g_missing.find(what) != std::string::npos; }
+
+bool sweep(int nr, int nc, int) { return nr + 2 * nc <= MTG_MAX_J && !(missing("sweep1") && nc == 1); }
+int uses_b0(int nr, int nc, int b0) { return b0 && nc > 0 && nr < 5 && nc < 4 && nr + 2 * nc <= 6; }
+bool tp(int nr, int nc) { return !missing("tp") && ((nr + nc > 0 && nr + 2 * nc <= 6) || (nr + 2 * nc == 10 && nr % 2 == 0)); }
+bool tp_wide(int nr, int nc) { return !missing("wide") && nr + nc > 0 && nr + 2 * nc <= 5; }
+bool tp_fused(int, int nc0, int, int lanes) { return nc0 >= 1 && nc0 <= 3 && !missing(("fused" + std::to_string(lanes)).c_str()); }
+bool pipe(int nr0, int nc0, int nsig, int) { return !missing("pipe") && nr0 <= 4 && nc0 >= 1 && nc0 <= 3 && nsig <= 3; }
+bool multi(int nr0, int nc0, int nsig, int) { return !missing("multi") && nr0 <= 4 && nc0 >= 1 && nc0 <= 3 && nsig >= 2 && nsig <= 3; }
+const MtgCatalogue g_cat = {sweep, uses_b0, tp, tp_wide, tp_fused, pipe, multi};
+
+const char *const g_family[] = {"tp_big", "tp_fused", "pipe", "multi", "structures"};
+const char *const g_kernel[] = {"none", "sweep", "tp", "tp_wide"};
+
+}  // namespace
+
+int main()
+{
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        MtgPlanIn in;
+        bool spec = false;
+        g_missing.clear();
+        std::istringstream tokens(line);
+        std::string tok;
+        while (tokens >> tok) {
+            const size_t eq = tok.find('=');
+            const std::string k = tok.substr(0, eq), v = tok.substr(eq + 1);
+            if (k == "no") { g_missing = v; continue; }
+            const long long x = std::stoll(v);
+            if (k == "N") in.N = x;
+            else if (k == "B") in.B = x;
+            else if (k == "Bw") in.Bw = x;
+            else if (k == "L") in.L = x;
+            else if (k == "nr0") in.nr0 = (int)x;
+            else if (k == "nc0") in.nc0 = (int)x;
+            else if (k == "nsig") in.nsig = (int)x;
+            else if (k == "b0") in.last_b0 = (int)x;
+            else if (k == "tp") in.tp_mode = (int)x;
+            else if (k == "pipe") in.pipe_mode = (int)x;
+            else if (k == "sort") in.sort_mode = (int)x;
+            else if (k == "may_sort") in.may_sort = x != 0;
+            else if (k == "grouped") in.lc_grouped_hint = x != 0;
+            else if (k == "no_prior") in.no_prior_batch = x != 0;
+            else if (k == "free_b") in.free_b = x != 0;
+            else if (k == "in_window") in.in_window = x != 0;
+            else if (k == "cus") in.cus = (int)x;
+            else if (k == "multi_knob") in.sweep_multi = x != 0;
+            else if (k == "fan_out_knob") in.sweep_fan_out = x != 0;
+            else if (k == "gsize") in.tp_gsize = (int)x;
+            else if (k == "chunk_target") in.tp_chunk_target = x;
+            else if (k == "spec") spec = x != 0;
+            else { std::cerr << "unknown key " << k << "\n"; return 2; }
+        }
+        if (in.Bw == 0) in.Bw = in.B;
+        if (spec) {
+            std::cout << "spec=" << mtg_plan_speculate(in.tp_mode, in.nr0 + 2 * in.nc0, in.N, in.B) << "\n";
+            continue;
+        }
+        const MtgSolvePlan p = mtg_plan_solve(in, g_cat);
+        std::cout << "family=" << g_family[p.family] << " sort=" << p.sort << " fan_out=" << p.fan_out << " C=" << p.tp_chunks
+                  << " g=" << p.tp_gsize << " lanes=" << p.fused_lanes << " kernels=";
+        for (int k = 0; k < in.nsig; ++k) std::cout << (k ? "," : "") << g_kernel[p.kernel[k]] << ":" << p.side[k];
+        std::cout << " name=" << p.name << "\n";
+    }
+    return 0;
+}
