@@ -489,12 +489,28 @@ MTG_API int mtg_predict(mtg_ctx *ctx, int64_t B, const double *theta, const int3
  * celerite.GP.apply_inverse(y) / CholeskySolver.solve: x <- K^-1 x for M right-hand sides,
  * x[N][M] (row n = sample n of every right-hand side), K the covariance of light curve
  * `lc_index` at parameter vector `theta`, in O(N J^2 + N J M) from the same factorisation
- * mtg_predict uses.  It is what celerite's predict at NEW times is made of (mean
- * K_* K^-1 r, covariance K_** - K_* K^-1 K_*^T); the host side assembles those.
+ * mtg_predict uses.  It is what the full covariance of celerite's predict at NEW times is
+ * made of (K_** - K_* K^-1 K_*^T, a dense M x M object by definition; the host side assembles
+ * it); the mean and the variance at new times come from mtg_predict_at without K_*.
  * *status: MTG_ST_* of the parameter vector (nothing is written to x unless MTG_ST_OK).
  */
 MTG_API int mtg_apply_inverse(mtg_ctx *ctx, const double *theta, int32_t lc_index, int64_t M, double *x,
                               int32_t *status);
+
+/*
+ * celerite.GP.predict(y, t=ts, return_var=True) at M new times ts[M] (any order, duplicates
+ * allowed, shared by all rows; a non-finite one is MTG_E_ARG) for B parameter vectors:
+ * conditional mean mu[b][m] (WITHOUT the per-light-curve y_offset, as mtg_predict; a fitted
+ * linear mean is included) and celerite's noise-free variance var[b][m] = k(0) - k_*^T K^-1 k_*
+ * (var == NULL: mean only).  celerite forms the dense cross-covariance K_* [M][N] and solves
+ * with it; here the factorisation's forward and backward recurrences are checkpointed every
+ * 64 samples and each new time replays at most 64 stored steps on either side:
+ * O((N + 64 M) J^2) per vector, device memory O(B (N J + N J^2 / 64 + M)), nothing of size
+ * N x M on either side.  Large batches are processed in slabs of rows.  Rows outside the prior
+ * or with a non positive-definite covariance get their status and read back NaN.
+ */
+MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index,
+                           int64_t M, const double *ts, double *mu, double *var, int32_t *status);
 
 /*
  * Accuracy probe of the device elementary functions the recurrence uses

@@ -14,7 +14,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <memory>
 #include <chrono>
@@ -2282,6 +2284,109 @@ MTG_API int mtg_predict(mtg_ctx *ctx, int64_t B, const double *theta, const int3
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     work.release(); d_mu.release(); d_var.release(); d_sig.release();
     if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_predict: %s", hipGetErrorString(e));
+    return MTG_OK;
+}
+
+// device workspace of one slab of mtg_predict_at: rows whose stored generators (3 J + 3 doubles per sample) stay below this
+#define MTG_PAT_SLAB_BYTES ((size_t)1 << 30)
+
+MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int64_t M,
+                           const double *ts, double *mu, double *var, int32_t *status)
+{
+    int rc = check_ready(ctx, true);
+    if (rc) return rc;
+    if (B <= 0 || M <= 0 || !ts || !mu || !status || (!theta && ctx->model.P > 0))
+        return fail(ctx, MTG_E_ARG, "mtg_predict_at: bad arguments");
+    if (lc_index)
+        for (int64_t b = 0; b < B; ++b)
+            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
+                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b, lc_index[b],
+                            (long long)ctx->L);
+    bool ascending = true;
+    for (int64_t m = 0; m < M; ++m) {
+        if (!std::isfinite(ts[m])) return fail(ctx, MTG_E_ARG, "mtg_predict_at: ts[%lld] is not finite", (long long)m);
+        if (m > 0 && ts[m] < ts[m - 1]) ascending = false;
+    }
+    // lanes of a wave take neighbouring times so that they replay the same stored samples: the times are visited in
+    // ascending order and each result is stored where its time was given
+    std::vector<int64_t> order;
+    if (!ascending) {
+        order.resize((size_t)M);
+        for (int64_t m = 0; m < M; ++m) order[(size_t)m] = m;
+        std::sort(order.begin(), order.end(), [ts](int64_t i, int64_t j) { return ts[i] < ts[j] || (ts[i] == ts[j] && i < j); });
+    }
+    rc = use_device(ctx);
+    if (rc) return rc;
+    const MtgModel &m = ctx->model;
+    const int P = m.P, J = m.nr0 + 2 * m.nc0;
+    const int64_t N = ctx->N;
+    if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_predict_at: rank %d > %d", J, MTG_MAX_J);
+    MtgCoefLayout lay{m.nr_max, m.nc_max};
+    rc = reserve_workspace(ctx, B, lay.nslots(), 1);
+    if (rc) return rc;
+    CTX_STREAM(ctx, s);
+    // rows per slab: the stored generators within MTG_PAT_SLAB_BYTES, and the grid of the second stage within 2^30 blocks
+    const size_t row_bytes = (size_t)N * (3 * J + 3) * 8;
+    int64_t Bs = (int64_t)(MTG_PAT_SLAB_BYTES / row_bytes);
+    const int64_t mblocks = (M + 63) / 64;
+    if (Bs > ((int64_t)1 << 30) / mblocks) Bs = ((int64_t)1 << 30) / mblocks;
+    if (Bs < 1) Bs = 1;
+    if (Bs > B) Bs = B;
+    if (mblocks > ((int64_t)1 << 30)) return fail(ctx, MTG_E_ARG, "mtg_predict_at: M = %lld is too large", (long long)M);
+    const int64_t nck = (N + MTG_PAT_C - 1) / MTG_PAT_C;
+    const size_t ck_bytes = (size_t)nck * (J * (J + 1) / 2 + J) * 8;
+    DevBuf work, ckf, ckb, ckr, d_mu, d_var, d_sig, d_ts, d_order;
+    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
+    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
+    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
+    hipError_t e = work.reserve((size_t)Bs * row_bytes + 8);
+    if (e == hipSuccess) e = ckf.reserve((size_t)Bs * ck_bytes + 8);
+    if (e == hipSuccess) e = ckb.reserve((size_t)Bs * ck_bytes + 8);
+    if (e == hipSuccess) e = ckr.reserve((size_t)Bs * (J * (J + 1) / 2) * 8 + 8);
+    if (e == hipSuccess) e = d_mu.reserve((size_t)Bs * M * 8);
+    if (e == hipSuccess && var) e = d_var.reserve((size_t)Bs * M * 8);
+    if (e == hipSuccess) e = d_sig.reserve((size_t)B * 4);
+    if (e == hipSuccess) e = d_ts.reserve((size_t)M * 8);
+    if (e == hipSuccess && !ascending) e = d_order.reserve((size_t)M * 8);
+    const int32_t *d_lc = nullptr;
+    if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_ts.p, ts, (size_t)M * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !ascending) e = hipMemcpyAsync(d_order.p, order.data(), (size_t)M * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && lc_index) {
+        e = ctx->lc.reserve((size_t)B * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s);
+        d_lc = ctx->lc.as<int32_t>();
+    }
+    if (e == hipSuccess) {
+        MtgPrepArgs pa;
+        pa.model = m; pa.theta = ctx->theta.as<double>(); pa.B = B; pa.add_prior = 1;
+        pa.coef = ctx->coef.as<double>(); pa.cstride = ctx->cstride; pa.nsig = 1;
+        pa.lists = ctx->lists.as<int>(); pa.counts = ctx->counts.as<int>();
+        pa.out = ctx->out.as<double>(); pa.status = ctx->status.as<int32_t>(); pa.sig = d_sig.as<int32_t>();
+        mtg_launch_prepare(pa, s);
+        e = hipGetLastError();
+    }
+    for (int64_t row0 = 0; e == hipSuccess && row0 < B; row0 += Bs) {
+        MtgPredictAtArgs qa;
+        qa.coef = ctx->coef.as<double>(); qa.cstride = ctx->cstride; qa.lay = lay;
+        qa.nr0 = m.nr0; qa.nc0 = m.nc0; qa.sig = d_sig.as<int32_t>();
+        qa.row0 = row0; qa.B = B - row0 < Bs ? B - row0 : Bs; qa.lc_index = d_lc;
+        qa.status = ctx->status.as<int32_t>(); qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
+        qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.work = work.as<double>();
+        qa.nck = nck; qa.ckf = ckf.as<double>(); qa.ckb = ckb.as<double>(); qa.ckr = ckr.as<double>(); qa.want_var = var ? 1 : 0;
+        qa.M = M; qa.ts = d_ts.as<double>(); qa.order = ascending ? nullptr : d_order.as<int64_t>();
+        qa.mu = d_mu.as<double>(); qa.var = var ? d_var.as<double>() : nullptr;
+        if (!mtg_launch_predict_at(qa, s)) { e = hipErrorInvalidValue; break; }
+        e = hipGetLastError();
+        // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
+        if (e == hipSuccess) e = hipMemcpyAsync(mu + row0 * M, d_mu.p, (size_t)qa.B * M * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && var) e = hipMemcpyAsync(var + row0 * M, d_var.p, (size_t)qa.B * M * 8, hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    else (void)hipStreamSynchronize(s);
+    work.release(); ckf.release(); ckb.release(); ckr.release(); d_mu.release(); d_var.release(); d_sig.release(); d_ts.release(); d_order.release();
+    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_predict_at: %s", hipGetErrorString(e));
     return MTG_OK;
 }
 

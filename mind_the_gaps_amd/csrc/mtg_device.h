@@ -145,6 +145,36 @@ struct MtgPredictArgs {
     int32_t *status;        // [B]
 };
 
+// samples between two checkpoints of the new-time prediction (mtg_predict_at.hip): a new time replays at most this
+// many stored steps in each direction; the checkpoints take N J^2 / C doubles per row
+#ifndef MTG_PAT_C
+#define MTG_PAT_C 64
+#endif
+
+struct MtgPredictAtArgs {
+    const double *coef;     // SoA coefficient workspace (mtg_prepare_kernel), indexed by the row of the batch
+    int64_t cstride;
+    MtgCoefLayout lay;
+    int nr0, nc0;           // structure with no over-damped SHO term
+    const int32_t *sig;     // [batch] over-damped SHO terms of each evaluation
+    int64_t row0, B;        // this launch takes rows [row0, row0 + B) of the batch (a slab)
+    const int32_t *lc_index;
+    int32_t *status;        // [batch] prior verdict from prepare on entry; MTG_ST_NOTPD added by the factorisation
+    const double2 *dxt, *yv;
+    int64_t N, t_stride;
+    double *work;           // [B][N][3 J + 3]: U, W, phi (per slot), D, z, x = (K^-1 r)_n
+    int64_t nck;            // checkpoints per row: ceil(N / MTG_PAT_C)
+    double *ckf, *ckb;      // [B][nck][J (J + 1) / 2 + J]: (S_n, f_n) and (G_n, g_n) at n = k MTG_PAT_C
+    double *ckr;            // [B][J (J + 1) / 2]: S + D W W^T after the first sample of the time-reversed factorisation
+    int want_var;           // 0: mean only (G is neither swept nor stored)
+    int64_t M;
+    const double *ts;       // [M] new times
+    const int64_t *order;   // [M] ts in ascending order (indices into ts), or NULL: ts is ascending as given
+    double *mu, *var;       // [B][M]
+};
+// both stages of the new-time prediction for one slab; 0 = rank outside 0 .. MTG_MAX_J
+int mtg_launch_predict_at(const MtgPredictAtArgs &, hipStream_t);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

@@ -1,0 +1,498 @@
+// mtg_predict_at.hip -- conditional mean / variance at NEW times from the semiseparable factorisation
+// (celerite.GP.predict(y, t=ts, return_var=True)), in O((N + M C) J^2) per parameter vector and with no object of
+// size N x M anywhere: celerite, and this project until now, form the dense cross-covariance K_* [M][N].
+//
+// Notation of mtg_predict_kernel (mtg_sampler.hip; W normalised by D):
+//   forward    S_n = phi_n phi_n^T o (S_{n-1} + D_{n-1} W_{n-1} W_{n-1}^T),  f_n = phi_n o (f_{n-1} + W_{n-1} z_{n-1})
+//              W_n = (V_n - S_n U_n) / D_n,  D_n = d_n + k(0) - U_n^T S_n U_n,  z_n = r_n - U_n^T f_n
+//   backward   g_n = phi_{n+1} o (g_{n+1} + U_{n+1} x_{n+1}),  x_n = z_n / D_n - W_n^T g_n            (x = K^-1 r)
+//              G_n = U_n U_n^T / D_n + (I - U_n W_n^T) X_n (I - W_n U_n^T),  X_n = phi_{n+1} phi_{n+1}^T o G_{n+1}
+// For a new time t* with n0 the last sample at or before it (-1: before the first one):
+//   phi* = exp(-c (t* - t_n0)),     S* = phi* phi*^T o (S_n0 + D_n0 W_n0 W_n0^T),  f* = phi* o (f_n0 + W_n0 z_n0)
+//   psi  = exp(-c (t_{n0+1} - t*)), X* = psi psi^T o G_{n0+1},                     g* = psi o (g_{n0+1} + U_{n0+1} x_{n0+1})
+//   q = S* U*,  Wt = V* - q        (U*, V* the generators at t*; S*, f* = 0 for n0 = -1; X*, g* = 0 for n0 = N - 1)
+//   mu*  = mean(t*) + U*^T f* + Wt^T g*
+//   var* = k(0) - U*^T q - Wt^T X* Wt
+// k_*^T K^-1 b = sum_n z*_n z^b_n / D_n with z* = L^-1 k_*: up to n0 the row k_* continues the lower triangle, which
+// sums to U*^T S* U* and U*^T f*; beyond n0 the forward substitution's error vector starts at Wt and is carried by
+// phi o (I - W U^T), which is what G and g accumulate from the other end.  The factors are those of the unchanged K.
+// tests/predict_at_replay.py is the same in numpy.
+//
+// Two stages:
+//   mtg_predict_at_factor_kernel   one lane per parameter vector (as mtg_predict_kernel): both sweeps, leaving U, W, phi,
+//                                  D, z, x of every sample in the workspace and a checkpoint of (S, f) and of (G, g) at
+//                                  every MTG_PAT_C-th sample (symmetric: J (J + 1) / 2 + J doubles each); a third sweep,
+//                                  of the time-reversed series, for the variance before the first sample
+//   mtg_predict_at_eval_kernel     one lane per (parameter vector, new time): binary search of t* among the light curve's
+//                                  times, at most MTG_PAT_C stored steps replayed forward from the checkpoint at or
+//                                  before n0 and backward from the one at or after n0 + 1 (no transcendental in the
+//                                  replay), then the exp / sincos of the two partial steps and the J^2 combinations.
+// Lanes of a wave work on one parameter vector and, the times being handed over in ascending order, on neighbouring
+// t*: they replay the same stored rows, which the vector memory path serves as one broadcast access.
+// Both are templates on J so that S, G and the generators live in registers (no scratch; the generic-J
+// mtg_predict_kernel spills by design).  The replay uses the very step functions of the factorisation, so the S and G it
+// rebuilds are bit for bit those the stored W, D, x were made from; each (row, t*) is a lane of its own, so its
+// result does not depend on the batch, on M or on the order of ts.
+#include "mtg_math.h"
+#include "mtg_device.h"
+
+template <int J>
+struct PatCoef {
+    double a[J], b[J], c[J], d[J];   // per slot: real j: (a_j, -, c_j, -); complex k: both slots (a_k, b_k, c_k, d_k)
+    double k0, slope, icpt, asum;
+    int NR;
+};
+
+__host__ __device__ constexpr int pat_sy(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+
+template <int J>
+__device__ __forceinline__ void pat_load_coef(const MtgPredictAtArgs &a, int64_t e, PatCoef<J> &k)
+{
+#pragma clang fp contract(off)
+    const int NR = a.nr0 + 2 * a.sig[e];
+    const double *cf = a.coef + e;
+    const int64_t cs = a.cstride;
+    k.NR = NR;
+    double k0 = 0.0;
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+        if (i < NR) {
+            k.a[i] = cf[a.lay.ar(i) * cs]; k.c[i] = cf[a.lay.cr(i) * cs]; k.b[i] = 0.0; k.d[i] = 0.0;
+            k0 += k.a[i];
+        } else {
+            const int q = (i - NR) >> 1;
+            k.a[i] = cf[a.lay.ac(q) * cs]; k.b[i] = cf[a.lay.bc(q) * cs];
+            k.c[i] = cf[a.lay.cc(q) * cs]; k.d[i] = cf[a.lay.dc(q) * cs];
+            if (((i - NR) & 1) == 0) k0 += k.a[i];
+        }
+    }
+    k.k0 = k0;
+    k.asum = cf[a.lay.asum() * cs];
+    k.slope = cf[a.lay.mean(0) * cs];
+    k.icpt = cf[a.lay.mean(1) * cs];
+}
+
+// generators at time t: the phase at the elapsed time, reduced modulo 2 pi before it is rounded (mtg_math.h)
+template <int J>
+__device__ __forceinline__ void pat_generators(const PatCoef<J> &k, double t, double t_first, double *U, double *V)
+{
+#pragma clang fp contract(off)
+    double sn = 0.0, cn = 1.0;
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+        if (i < k.NR) { U[i] = k.a[i]; V[i] = 1.0; }
+        else if (((i - k.NR) & 1) == 0) {
+            mtg_elapsed_sincos(k.d[i], t, t_first, &sn, &cn);
+            U[i] = k.a[i] * cn + k.b[i] * sn; V[i] = cn;
+        } else { U[i] = k.a[i] * sn - k.b[i] * cn; V[i] = sn; }
+    }
+}
+
+// exp(-c dx) per slot (dx >= 0), one exp per term
+template <int J>
+__device__ __forceinline__ void pat_decay(const PatCoef<J> &k, double dx, double *ph)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+        if (i < k.NR || ((i - k.NR) & 1) == 0) ph[i] = exp(-k.c[i] * dx);
+        else ph[i] = ph[i > 0 ? i - 1 : 0];
+    }
+}
+
+// S <- phi phi^T o (S + Dp Wp Wp^T),  f <- phi o (f + Wp zp)
+template <int J>
+__device__ __forceinline__ void pat_fwd_step(double *S, double *f, const double *ph, const double *Wp, double Dp, double zp)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) S[pat_sy(i, j)] = ph[i] * ph[j] * (S[pat_sy(i, j)] + Dp * Wp[i] * Wp[j]);
+        f[i] = ph[i] * (f[i] + Wp[i] * zp);
+    }
+}
+
+// g <- phn o (g + Un xn): g_n from g_{n+1} and sample n + 1
+template <int J>
+__device__ __forceinline__ void pat_bwd_g(double *g, const double *phn, const double *Un, double xn)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < J; ++i) g[i] = phn[i] * (g[i] + Un[i] * xn);
+}
+
+// G <- U U^T / D + (I - U W^T) X (I - W U^T),  X = phn phn^T o G: G_n from G_{n+1} and sample n
+// (forming A = I - U W^T explicitly and the product A X with it was tried: J^3 instead of J^2, and no more accurate --
+// 0.78 of the bound on `signatures` against 0.013)
+template <int J>
+__device__ __forceinline__ void pat_bwd_G(double *G, const double *phn, const double *U, const double *W, double D)
+{
+#pragma clang fp contract(off)
+    double XW[J], wxw = 0.0;
+#pragma unroll
+    for (int i = 0; i < J; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) G[pat_sy(i, j)] = phn[i] * phn[j] * G[pat_sy(i, j)];
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < J; ++j) s += G[pat_sy(i, j)] * W[j];
+        XW[i] = s;
+    }
+#pragma unroll
+    for (int i = 0; i < J; ++i) wxw += W[i] * XW[i];
+    const double h = wxw + 1.0 / D;
+#pragma unroll
+    for (int i = 0; i < J; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j)
+            G[pat_sy(i, j)] = G[pat_sy(i, j)] - U[i] * XW[j] - XW[i] * U[j] + U[i] * U[j] * h;
+}
+
+template <int J>
+__global__ void __launch_bounds__(64) mtg_predict_at_factor_kernel(MtgPredictAtArgs a)
+{
+#pragma clang fp contract(off)
+    constexpr int SY = J * (J + 1) / 2, CK = SY + J, stride = 3 * J + 3;
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // row of this slab
+    if (r >= a.B) return;
+    const int64_t e = a.row0 + r;                                       // row of the batch
+    if (a.status[e] != MTG_ST_OK) return;
+    PatCoef<J> k;
+    pat_load_coef<J>(a, e, k);
+    const int64_t lc = a.lc_index ? a.lc_index[e] : 0;
+    const int64_t N = a.N;
+    const double2 *yv = a.yv + lc * N, *dxt = a.dxt + lc * a.t_stride;
+    double *wk = a.work + r * N * stride;
+    double *ckf = a.ckf + r * a.nck * CK, *ckb = a.ckb + r * a.nck * CK;
+
+    double S[SY], f[J], Wp[J], U[J], V[J], ph[J];
+    const double t_first = dxt[0].y;
+#pragma unroll
+    for (int i = 0; i < SY; ++i) S[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < J; ++i) { f[i] = 0.0; Wp[i] = 0.0; }
+    double Dp = 1.0, zp = 0.0;
+    bool bad = false;
+    for (int64_t n = 0; n < N; ++n) {
+        const double dx = dxt[n].x, t = dxt[n].y;
+        pat_decay<J>(k, dx, ph);
+        pat_generators<J>(k, t, t_first, U, V);
+        pat_fwd_step<J>(S, f, ph, Wp, Dp, zp);
+        if (n % MTG_PAT_C == 0) {
+            double *c = ckf + (n / MTG_PAT_C) * CK;
+#pragma unroll
+            for (int i = 0; i < SY; ++i) c[i] = S[i];
+#pragma unroll
+            for (int i = 0; i < J; ++i) c[SY + i] = f[i];
+        }
+        double D = yv[n].y + k.asum, z = yv[n].x - (k.slope * t + k.icpt);
+        double Wn[J];
+#pragma unroll
+        for (int i = 0; i < J; ++i) {
+            double q = 0.0;
+#pragma unroll
+            for (int j = 0; j < J; ++j) q += S[pat_sy(i, j)] * U[j];
+            Wn[i] = V[i] - q;
+            D -= U[i] * q;
+            z -= U[i] * f[i];
+        }
+        bad = bad || !(D > 0.0);
+        double *w = wk + n * stride;
+#pragma unroll
+        for (int i = 0; i < J; ++i) { Wn[i] /= D; w[i] = U[i]; w[J + i] = Wn[i]; w[2 * J + i] = ph[i]; Wp[i] = Wn[i]; }
+        w[3 * J] = D; w[3 * J + 1] = z;
+        Dp = D; zp = z;
+    }
+    if (bad) { a.status[e] = MTG_ST_NOTPD; return; }
+
+    double g[J], Un[J], phn[J];
+    double *G = S;
+#pragma unroll
+    for (int i = 0; i < SY; ++i) G[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < J; ++i) { g[i] = 0.0; Un[i] = 0.0; phn[i] = 0.0; }
+    double xn = 0.0;
+    for (int64_t n = N - 1; n >= 0; --n) {
+        double *w = wk + n * stride;
+        double Wn[J];
+#pragma unroll
+        for (int i = 0; i < J; ++i) { U[i] = w[i]; Wn[i] = w[J + i]; }
+        const double D = w[3 * J];
+        pat_bwd_g<J>(g, phn, Un, xn);
+        double x = w[3 * J + 1] / D;
+#pragma unroll
+        for (int i = 0; i < J; ++i) x -= Wn[i] * g[i];
+        w[3 * J + 2] = x;
+        if (a.want_var) pat_bwd_G<J>(G, phn, U, Wn, D);
+        if (n % MTG_PAT_C == 0) {
+            double *c = ckb + (n / MTG_PAT_C) * CK;
+            if (a.want_var) {
+#pragma unroll
+                for (int i = 0; i < SY; ++i) c[i] = G[i];
+            }
+#pragma unroll
+            for (int i = 0; i < J; ++i) c[SY + i] = g[i];
+        }
+#pragma unroll
+        for (int i = 0; i < J; ++i) { Un[i] = U[i]; phn[i] = w[2 * J + i]; }
+        xn = x;
+    }
+    if (!a.want_var) return;
+
+    // ---- the factorisation of the time-reversed series, for the variance BEFORE the first sample ----------------
+    // There Wt = V* meets G_0 unreduced: var* = k(0) - V*^T X* V* cancels from |G|, whose own recurrence subtracts, and
+    // a long-memory kernel (k(0) / d ~ 1e9) is left with 2.5e-9 k(0) of error, 1400 times its bound.  Seen from the other
+    // end the same time lies AFTER the last sample, where var* = k(0) - U*^T S* U* comes from the S recurrence, a sum of
+    // positive terms.  One more forward sweep, last sample first, phases at the time elapsed from the last sample
+    // backwards; kept: S + D W W^T after the first sample, J (J + 1) / 2 doubles per row.
+    const double t_last = dxt[N - 1].y;
+#pragma unroll
+    for (int i = 0; i < SY; ++i) S[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < J; ++i) { f[i] = 0.0; Wp[i] = 0.0; }
+    Dp = 1.0;
+    for (int64_t n = N - 1; n >= 0; --n) {
+        const double dx = n < N - 1 ? dxt[n + 1].x : 0.0;
+        pat_decay<J>(k, dx, ph);
+        pat_generators<J>(k, t_last, dxt[n].y, U, V);
+        pat_fwd_step<J>(S, f, ph, Wp, Dp, 0.0);
+        double D = yv[n].y + k.asum;
+#pragma unroll
+        for (int i = 0; i < J; ++i) {
+            double q = 0.0;
+#pragma unroll
+            for (int j = 0; j < J; ++j) q += S[pat_sy(i, j)] * U[j];
+            Wp[i] = V[i] - q;
+            D -= U[i] * q;
+        }
+#pragma unroll
+        for (int i = 0; i < J; ++i) Wp[i] /= D;
+        Dp = D;
+    }
+    double *c = a.ckr + r * SY;
+#pragma unroll
+    for (int i = 0; i < J; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) c[pat_sy(i, j)] = S[pat_sy(i, j)] + Dp * Wp[i] * Wp[j];
+}
+
+template <int J>
+__global__ void __launch_bounds__(64) mtg_predict_at_eval_kernel(MtgPredictAtArgs a)
+{
+#pragma clang fp contract(off)
+    constexpr int SY = J * (J + 1) / 2, CK = SY + J, stride = 3 * J + 3;
+    const int64_t mblocks = (a.M + 63) / 64;
+    const int64_t r = (int64_t)blockIdx.x / mblocks;
+    const int64_t m = ((int64_t)blockIdx.x % mblocks) * 64 + threadIdx.x;
+    if (r >= a.B || m >= a.M) return;
+    const int64_t e = a.row0 + r;
+    const int64_t slot = a.order ? a.order[m] : m;     // the times are visited in ascending order, stored where they were given
+    if (a.status[e] != MTG_ST_OK) {
+        a.mu[r * a.M + slot] = NAN;
+        if (a.want_var) a.var[r * a.M + slot] = NAN;
+        return;
+    }
+    PatCoef<J> k;
+    pat_load_coef<J>(a, e, k);
+    const int64_t lc = a.lc_index ? a.lc_index[e] : 0;
+    const int64_t N = a.N;
+    const double2 *dxt = a.dxt + lc * a.t_stride;
+    const double *wk = a.work + r * N * stride;
+    const double *ckf = a.ckf + r * a.nck * CK, *ckb = a.ckb + r * a.nck * CK;
+    const double ts = a.ts[slot];
+
+    // n0: the last sample with t_n <= t* (-1: none)
+    int64_t lo = 0, hi = N;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (dxt[mid].y <= ts) lo = mid + 1; else hi = mid;
+    }
+    const int64_t n0 = lo - 1;
+
+    double Us[J], Wt[J], ph[J], T[SY], v[J];
+    {
+        double Vs[J];
+        pat_generators<J>(k, ts, dxt[0].y, Us, Vs);
+#pragma unroll
+        for (int i = 0; i < J; ++i) Wt[i] = Vs[i];
+    }
+    double mu = k.slope * ts + k.icpt, var = k.k0;
+    if (n0 >= 0) {
+        // (S, f) of the checkpoint at or before n0, the stored steps up to n0, then the partial step to t*
+        const int64_t c0 = n0 / MTG_PAT_C;
+        const double *c = ckf + c0 * CK;
+#pragma unroll
+        for (int i = 0; i < SY; ++i) T[i] = c[i];
+#pragma unroll
+        for (int i = 0; i < J; ++i) v[i] = c[SY + i];
+        double phs[J];
+        pat_decay<J>(k, ts - dxt[n0].y, phs);
+        for (int64_t n = c0 * MTG_PAT_C; n <= n0; ++n) {
+            const double *w = wk + n * stride;
+            double Wn[J];
+#pragma unroll
+            for (int i = 0; i < J; ++i) Wn[i] = w[J + i];
+            if (n < n0) {
+#pragma unroll
+                for (int i = 0; i < J; ++i) ph[i] = w[stride + 2 * J + i];
+            } else {
+#pragma unroll
+                for (int i = 0; i < J; ++i) ph[i] = phs[i];
+            }
+            pat_fwd_step<J>(T, v, ph, Wn, w[3 * J], w[3 * J + 1]);
+        }
+        double uq = 0.0, uf = 0.0;
+#pragma unroll
+        for (int i = 0; i < J; ++i) {
+            double q = 0.0;
+#pragma unroll
+            for (int j = 0; j < J; ++j) q += T[pat_sy(i, j)] * Us[j];
+            Wt[i] -= q;
+            uq += Us[i] * q;
+            uf += Us[i] * v[i];
+        }
+        mu += uf;
+        var -= uq;
+    }
+    const bool use_G = a.want_var && n0 >= 0;      // before the first sample the variance comes from the reversed sweep
+    if (n0 < N - 1) {
+        // (G, g) of the checkpoint at or after n0 + 1 (beyond the last sample: zero), the stored steps down to n0 + 1,
+        // then the partial step to t*
+        const int64_t n1 = n0 + 1;
+        int64_t p = (n1 + MTG_PAT_C - 1) / MTG_PAT_C * MTG_PAT_C;
+        if (p < N) {
+            const double *c = ckb + (p / MTG_PAT_C) * CK;
+            if (use_G) {
+#pragma unroll
+                for (int i = 0; i < SY; ++i) T[i] = c[i];
+            }
+#pragma unroll
+            for (int i = 0; i < J; ++i) v[i] = c[SY + i];
+        } else {
+            p = N;
+#pragma unroll
+            for (int i = 0; i < SY; ++i) T[i] = 0.0;
+#pragma unroll
+            for (int i = 0; i < J; ++i) v[i] = 0.0;
+        }
+        double Un[J];
+        for (int64_t n = p - 1; n >= n1; --n) {
+            const double *w = wk + n * stride;
+            double xn = 0.0;
+            if (n + 1 < N) {
+#pragma unroll
+                for (int i = 0; i < J; ++i) { Un[i] = w[stride + i]; ph[i] = w[stride + 2 * J + i]; }
+                xn = w[stride + 3 * J + 2];
+            } else {
+#pragma unroll
+                for (int i = 0; i < J; ++i) { Un[i] = 0.0; ph[i] = 0.0; }
+            }
+            pat_bwd_g<J>(v, ph, Un, xn);
+            if (use_G) {
+                double Um[J], Wm[J];
+#pragma unroll
+                for (int i = 0; i < J; ++i) { Um[i] = w[i]; Wm[i] = w[J + i]; }
+                pat_bwd_G<J>(T, ph, Um, Wm, w[3 * J]);
+            }
+        }
+        const double *w = wk + n1 * stride;
+        pat_decay<J>(k, dxt[n1].y - ts, ph);
+#pragma unroll
+        for (int i = 0; i < J; ++i) Un[i] = w[i];
+        pat_bwd_g<J>(v, ph, Un, w[3 * J + 2]);
+        double wg = 0.0;
+#pragma unroll
+        for (int i = 0; i < J; ++i) wg += Wt[i] * v[i];
+        mu += wg;
+        if (use_G) {
+            double wxw = 0.0;
+#pragma unroll
+            for (int i = 0; i < J; ++i) {
+                double s = 0.0;
+#pragma unroll
+                for (int j = 0; j < J; ++j) s += ph[i] * ph[j] * T[pat_sy(i, j)] * Wt[j];
+                wxw += Wt[i] * s;
+            }
+            var -= wxw;
+        }
+    }
+    if (a.want_var && n0 < 0) {
+        // seen from the other end t* lies after the last sample of the reversed series: var* = k(0) - U'^T S' U'
+        const double *c = a.ckr + r * SY;
+        pat_decay<J>(k, dxt[0].y - ts, ph);
+        double Ur[J], Vr[J], usu = 0.0;
+        pat_generators<J>(k, dxt[N - 1].y, ts, Ur, Vr);
+#pragma unroll
+        for (int i = 0; i < J; ++i) {
+            double q = 0.0;
+#pragma unroll
+            for (int j = 0; j < J; ++j) q += ph[i] * ph[j] * c[pat_sy(i, j)] * Ur[j];
+            usu += Ur[i] * q;
+        }
+        var -= usu;
+    }
+    a.mu[r * a.M + slot] = mu;
+    if (a.want_var) a.var[r * a.M + slot] = var;
+}
+
+// a model without a celerite term (white noise only, J = 0): K is diagonal, the prediction is the mean and the
+// noise-free variance is 0; one lane per row checks the pivots, one per (row, t*) writes
+__global__ void __launch_bounds__(64) mtg_predict_at_white_factor_kernel(MtgPredictAtArgs a)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.B) return;
+    const int64_t e = a.row0 + r;
+    if (a.status[e] != MTG_ST_OK) return;
+    const double2 *yv = a.yv + (a.lc_index ? a.lc_index[e] : 0) * a.N;
+    const double asum = a.coef[a.lay.asum() * a.cstride + e];
+    bool bad = false;
+    for (int64_t n = 0; n < a.N; ++n) bad = bad || !(yv[n].y + asum > 0.0);
+    if (bad) a.status[e] = MTG_ST_NOTPD;
+}
+
+__global__ void __launch_bounds__(64) mtg_predict_at_white_eval_kernel(MtgPredictAtArgs a)
+{
+#pragma clang fp contract(off)
+    const int64_t mblocks = (a.M + 63) / 64;
+    const int64_t r = (int64_t)blockIdx.x / mblocks;
+    const int64_t m = ((int64_t)blockIdx.x % mblocks) * 64 + threadIdx.x;
+    if (r >= a.B || m >= a.M) return;
+    const int64_t e = a.row0 + r;
+    const bool ok = a.status[e] == MTG_ST_OK;
+    const double slope = a.coef[a.lay.mean(0) * a.cstride + e], icpt = a.coef[a.lay.mean(1) * a.cstride + e];
+    a.mu[r * a.M + m] = ok ? slope * a.ts[m] + icpt : NAN;
+    if (a.want_var) a.var[r * a.M + m] = ok ? 0.0 : NAN;
+}
+
+template <int J>
+static void pat_launch(const MtgPredictAtArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(mtg_predict_at_factor_kernel<J>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(mtg_predict_at_eval_kernel<J>, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
+}
+
+// both stages for rows [row0, row0 + B) of the batch; J = nr0 + 2 nc0 in 0 .. MTG_MAX_J (returns 0 otherwise)
+int mtg_launch_predict_at(const MtgPredictAtArgs &a, hipStream_t s)
+{
+    switch (a.nr0 + 2 * a.nc0) {
+    case 0:
+        hipLaunchKernelGGL(mtg_predict_at_white_factor_kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(mtg_predict_at_white_eval_kernel, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
+        break;
+    case 1: pat_launch<1>(a, s); break;
+    case 2: pat_launch<2>(a, s); break;
+    case 3: pat_launch<3>(a, s); break;
+    case 4: pat_launch<4>(a, s); break;
+    case 5: pat_launch<5>(a, s); break;
+    case 6: pat_launch<6>(a, s); break;
+    case 7: pat_launch<7>(a, s); break;
+    case 8: pat_launch<8>(a, s); break;
+    case 9: pat_launch<9>(a, s); break;
+    case 10: pat_launch<10>(a, s); break;
+    default: return 0;
+    }
+    return 1;
+}

@@ -36,6 +36,7 @@ EXPORTS = (
     "mtg_chain_autocorr", "mtg_fft_warmup", "mtg_simulate_plan", "mtg_ensemble_restore", "mtg_set_sort", "mtg_set_pipeline", "mtg_set_stream_base", "mtg_set_speculation", "mtg_last_solver", "mtg_pair_contexts", "mtg_unpair_contexts", "mtg_pair_stats", "mtg_set_simulate_pairs", "mtg_set_simulate_transform", "mtg_set_simulate_pdf", "mtg_set_simulate_kraft", "mtg_set_simulate_pdf_draws", "mtg_simulate_pdf_report", "mtg_set_pair_patience", "mtg_chain_autocorr_plans_built",
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
+    "mtg_predict_at",
 )
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
@@ -310,6 +311,8 @@ def load_library():
     lib.mtg_set_window_bytes.argtypes = [c_vp, ctypes.c_uint64]
     lib.mtg_predict.restype = c_int
     lib.mtg_predict.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, _ip]
+    lib.mtg_predict_at.restype = c_int
+    lib.mtg_predict_at.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, _dp, _dp, _ip]
     lib.mtg_math_probe.restype = c_int
     lib.mtg_math_probe.argtypes = [c_vp, c_i64, _dp, _dp, _dp, _dp, _dp]
     lib.mtg_structure_supported.restype = c_int
@@ -738,6 +741,21 @@ class Engine:
                                           _iptr(status)))
         return mu, var, status
 
+    def predict_at(self, theta, ts, lc_index=None, return_var=True):
+        """Conditional mean / variance at new times ``ts`` [M] (any order) -> (mu[B][M], var[B][M] or None,
+        status[B]); mu excludes the per-light-curve y_offset, var is the noise-free variance.  Linear in N and M:
+        no cross-covariance is formed (mtg_predict_at)."""
+        theta = np.atleast_2d(_f64(theta))
+        ts = _f64(np.atleast_1d(ts)).ravel()
+        B, M = theta.shape[0], len(ts)
+        lc = None if lc_index is None else np.ascontiguousarray(lc_index, dtype=np.int32)
+        mu = np.full((B, M), np.nan)
+        var = np.full((B, M), np.nan) if return_var else None
+        status = np.empty(B, dtype=np.int32)
+        self._check(self._lib.mtg_predict_at(self._ctx, B, _ptr(theta), _iptr(lc), M, _ptr(ts), _ptr(mu), _ptr(var),
+                                             _iptr(status)))
+        return mu, var, status
+
     def apply_inverse(self, theta, rhs, lc_index=0):
         """K^-1 rhs for rhs[N] or rhs[N][M] at parameter vector ``theta`` -> (x, status)."""
         rhs = _f64(rhs)
@@ -880,6 +898,6 @@ class Engine:
 
 for _name in ("set_lightcurves", "set_lightcurves_device", "set_model", "loglike", "loglike_device", "loglike_coeffs",
               "ensemble_init", "ensemble_run", "ensemble_restore", "ensemble_state", "chain_autocorr", "simulate_tk95",
-              "tk95_observe_series", "predict", "apply_inverse", "math_probe"):
+              "tk95_observe_series", "predict", "predict_at", "apply_inverse", "math_probe"):
     setattr(Engine, _name, _one_thread_at_a_time(getattr(Engine, _name)))
 del _name

@@ -364,29 +364,31 @@ class GP(ModelSet):
 
         At the training times (``t=None``) with ``return_var=True`` -- the reference's call,
         gpmodelling.py:366 -- mean and variance both come from the O(N J^2) factorisation on the
-        device (celerite forms the dense N x N cross-covariance for the variance).  At other times,
-        or for the full covariance, celerite's own expressions ``mu = mean(t) + K_* K^-1 r``,
-        ``cov = K_** - K_* K^-1 K_*^T`` are assembled on the host from ``apply_inverse`` (one
-        device call with 1 + N_* right-hand sides).  Like celerite's, the variances are those of
-        the noise-free process (no jitter, no measurement errors)."""
+        device (celerite forms the dense N x N cross-covariance for the variance).  At other times the
+        mean and the variance come from the same factorisation, checkpointed along the light curve
+        (``Engine.predict_at``: linear in N and in the number of new times, no cross-covariance
+        ``K_*`` is formed -- celerite's is dense, N_* x N).  Only the full covariance, a dense
+        N_* x N_* object by definition, is assembled on the host from celerite's own expression
+        ``cov = K_** - K_* K^-1 K_*^T`` over ``apply_inverse`` (one device call with 1 + N_*
+        right-hand sides).  Like celerite's, the variances are those of the noise-free process (no
+        jitter, no measurement errors)."""
+        eng, model = self._bound_engine(y)
         if t is None and (return_var or not return_cov):
-            eng, model = self._bound_engine(y)
             mu, var, status = eng.predict(model.full[model.free_index][None, :])
             self._raise_for(status[0])
             mu = mu[0] + (model.y_offset or 0.0)
             return (mu, var[0]) if return_var else mu
-        eng, model = self._bound_engine(y)
+        if return_var or not return_cov:
+            xs = np.atleast_1d(np.asarray(t, dtype=np.float64))
+            mu, var, status = eng.predict_at(model.full[model.free_index][None, :], xs, return_var=return_var)
+            self._raise_for(status[0])
+            mu = mu[0] + (model.y_offset or 0.0)
+            return (mu, var[0]) if return_var else mu
         y = np.asarray(y, dtype=np.float64)
         xs = self._t if t is None else np.atleast_1d(np.asarray(t, dtype=np.float64))
         resid = y - self.mean.get_value(self._t)
-        if not (return_cov or return_var):
-            alpha, status = eng.apply_inverse(model.full[model.free_index], resid)
-            self._raise_for(status)
-            return self.mean.get_value(xs) + self.kernel.get_value(xs[:, None] - self._t[None, :]) @ alpha
         kxs = self.kernel.get_value(xs[:, None] - self._t[None, :])                # [N_*][N]
         sol, status = eng.apply_inverse(model.full[model.free_index], np.column_stack([resid, kxs.T]))
         self._raise_for(status)
         mu = self.mean.get_value(xs) + kxs @ sol[:, 0]
-        if return_var:
-            return mu, self.kernel.get_value(0.0) - np.sum(kxs.T * sol[:, 1:], axis=0)
         return mu, self.kernel.get_value(xs[:, None] - xs[None, :]) - kxs @ sol[:, 1:]

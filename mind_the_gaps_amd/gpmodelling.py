@@ -306,6 +306,33 @@ class GPModelling:
             pred_var += self.gp.kernel.jitter
         return (self._lightcurve.y - pred_mean) / np.sqrt(pred_var)
 
+    def predict_at(self, times, parameters=None, include_noise: bool = False):
+        """Model curve and its variance at ``times`` [M] (new; celerite users loop ``gp.predict(y, t, return_var=True)``
+        over posterior samples): conditional mean and variance of the process given the light curve, from the
+        factorisation in time linear in N and M (``Engine.predict_at``).  ``parameters``: None -- the
+        maximum-posterior sample if posteriors were derived, else the GP's current vector -- or one vector [P], or
+        [B][P] posterior samples, evaluated in one launch.  Returns ``(mu, var)`` of shape [M] or [B][M]; the variance
+        is that of the noise-free process unless ``include_noise`` adds each vector's ``kernel.jitter``, as
+        ``standarized_residuals`` does."""
+        if parameters is None:
+            parameters = self.max_parameters if self._mcmc_samples is not None else self.gp.get_parameter_vector()
+        parameters = np.asarray(parameters, dtype=np.float64)
+        theta = np.atleast_2d(parameters)
+        eng, model = self.gp._bound_engine(self._lightcurve.y)
+        mu, var, status = eng.predict_at(theta, times)
+        for st in status:
+            self.gp._raise_for(st)
+        mu += model.y_offset or 0.0
+        if include_noise:
+            saved = self.gp.get_parameter_vector()
+            try:
+                for b in range(len(theta)):
+                    self.gp.set_parameter_vector(theta[b])
+                    var[b] += self.gp.kernel.jitter
+            finally:
+                self.gp.set_parameter_vector(saved)
+        return (mu[0], var[0]) if parameters.ndim == 1 else (mu, var)
+
     def get_rstat(self, burnin: int = None):
         """Gelman-Rubin-like statistic as the reference computes it
         (gpmodelling.py:373-403): within-chain over total variance."""

@@ -133,8 +133,12 @@ def rows():
          "the E13 flux-PDF adjustment on the device = the numpy loop to 10⁻¹² from the same white series; Kraft noise on the device = `add_noise` epoch by epoch), "
          "`test_simulator_reference_cases` (the reference's known answers, incl. its `test_pdf_lognormal / _uniform` at their own 10⁶ points through the device adjustment), `test_psd_models`, `test_ppp_gpu` (block invariance; a lognormal Protassov test that never enters the host loop)",
          "%d × %s-point simulations in %.2f s inside the workflow" % (wf["nsims"], sci(wf["fft_points_per_simulation"]), wf["seconds"]["simulate"])),
-        ("f3 predict", "`mtg_predict_kernel`, `mtg_apply_inverse_kernel`, `GP.predict`, `standarized_residuals`",
-         "`test_gpmodelling_gpu` (dense algebra)", "O(N·J²) instead of celerite's dense N × N"),
+        ("f3 predict", "`mtg_predict_kernel`, `mtg_apply_inverse_kernel`, `csrc/mtg_predict_at.hip` (new times), `GP.predict`, "
+         "`GPModelling.predict_at`, `standarized_residuals`",
+         "`test_gpmodelling_gpu` (dense algebra), `test_predict_vs_quad_gpu`, `test_predict_at_vs_quad_gpu` (quad truth, every group; "
+         "bit-for-bit invariance; 10⁶ times on N = 2·10⁵), `test_predict_at_cpu`",
+         "O(N·J²) instead of celerite's dense N × N; new times O((N + 64 M)·J²) instead of its dense M × N "
+         "(`profiles/predict_at_probe.txt`)"),
         ("f4 LRT / IO", "`stats.py`, `lightcurves.py`, `ppp.protassov_test`",
          "`test_stats_io` (bit for bit vs reference `stats.py` outputs), `test_ppp_gpu`, `test_distributed`",
          "configs[3] as a workflow: **%.1f s** (observed chains %.2f, simulation %.2f, refits %.1f + %.1f), p = %.6f, %s refit "
