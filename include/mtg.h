@@ -513,6 +513,25 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
                            int64_t M, const double *ts, double *mu, double *var, int32_t *status);
 
 /*
+ * celerite.GP.sample(size) -> solver.dot_L: B realisations of the process itself, y[b] ~ N(mean, K(theta[b])) on the
+ * sampling and error bars of light curve lc_index[b] (NULL = all 0), K = k(t_i - t_j) + diag(sigma^2 + jitter) as in
+ * the likelihood -- a draw is a noisy light curve, as celerite's is.  With the factorisation K = L diag(D) L^T the
+ * draw is y = mean + L sqrt(D) q, q ~ N(0, I): the forward sweep of mtg_predict driven by one normal per sample,
+ * O(N J^2) per draw, exact for any sampling (no FFT, no regular grid: what mtg_simulate_tk95 approximates).  The data
+ * y of the resident light curves are not read.  y[b][n] includes a fitted constant or linear mean and EXCLUDES the
+ * per-light-curve y_offset, which the caller adds back (as for mtg_predict).
+ *   normals  [B][N] standard normals of the caller (host), or NULL: drawn on the device from Philox4x32-10 keyed by
+ *            `seed`, counter (n / 2, 12, low word, high word of first_index + b) with first_index that of
+ *            mtg_set_stream_base; one block gives the Box-Muller pair q[2k], q[2k + 1].  Draw b therefore depends on
+ *            (seed, first_index + b, theta[b], its light curve) alone: not on B, nor on how a job is cut over calls
+ *            or GPUs.  seed is not used with the caller's normals.
+ * Large batches are processed in slabs of rows (device memory O(slab N)).  Rows outside the prior or with a non
+ * positive-definite covariance get their status and read back NaN.
+ */
+MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, uint64_t seed,
+                        const double *normals /* [B][N] or NULL: Philox */, double *y /* [B][N] */, int32_t *status);
+
+/*
  * Accuracy probe of the device elementary functions the recurrence uses
  * (tests only): exp_neg[i] = exp(-x[i]), sin/cos(x[i]), rcp_x[i] = 1 / x[i] for
  * n host values x >= 0.

@@ -2390,6 +2390,84 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
     return MTG_OK;
 }
 
+// device memory of one slab of mtg_gp_draw: rows (a multiple of 64) whose draws stay below this, and as much again for
+// the caller's normals
+#define MTG_DRAW_SLAB_BYTES ((size_t)1 << 28)
+
+MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, uint64_t seed,
+                        const double *normals, double *y, int32_t *status)
+{
+    int rc = check_ready(ctx, true);
+    if (rc) return rc;
+    if (B <= 0 || !y || !status || (!theta && ctx->model.P > 0))
+        return fail(ctx, MTG_E_ARG, "mtg_gp_draw: bad arguments");
+    if (lc_index)
+        for (int64_t b = 0; b < B; ++b)
+            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
+                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b, lc_index[b],
+                            (long long)ctx->L);
+    rc = use_device(ctx);
+    if (rc) return rc;
+    const MtgModel &m = ctx->model;
+    const int P = m.P, J = m.nr0 + 2 * m.nc0;
+    const int64_t N = ctx->N;
+    if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_gp_draw: rank %d > %d", J, MTG_MAX_J);
+    MtgCoefLayout lay{m.nr_max, m.nc_max};
+    rc = reserve_workspace(ctx, B, lay.nslots(), 1);
+    if (rc) return rc;
+    CTX_STREAM(ctx, s);
+    const size_t row_bytes = (size_t)N * 8;
+    int64_t Bs = (int64_t)(MTG_DRAW_SLAB_BYTES / row_bytes) / 64 * 64;
+    if (Bs < 64) Bs = 64;
+    if (Bs > B) Bs = B;
+    DevBuf d_y, d_q, d_sig;
+    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
+    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
+    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
+    hipError_t e = d_y.reserve((size_t)Bs * row_bytes);
+    if (e == hipSuccess && normals) e = d_q.reserve((size_t)Bs * row_bytes);
+    if (e == hipSuccess) e = d_sig.reserve((size_t)B * 4);
+    const int32_t *d_lc = nullptr;
+    if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && lc_index) {
+        e = ctx->lc.reserve((size_t)B * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s);
+        d_lc = ctx->lc.as<int32_t>();
+    }
+    if (e == hipSuccess) {
+        MtgPrepArgs pa;
+        pa.model = m; pa.theta = ctx->theta.as<double>(); pa.B = B; pa.add_prior = 1;
+        pa.coef = ctx->coef.as<double>(); pa.cstride = ctx->cstride; pa.nsig = 1;
+        pa.lists = ctx->lists.as<int>(); pa.counts = ctx->counts.as<int>();
+        pa.out = ctx->out.as<double>(); pa.status = ctx->status.as<int32_t>(); pa.sig = d_sig.as<int32_t>();
+        mtg_launch_prepare(pa, s);
+        e = hipGetLastError();
+    }
+    for (int64_t row0 = 0; e == hipSuccess && row0 < B; row0 += Bs) {
+        MtgGpDrawArgs qa;
+        qa.coef = ctx->coef.as<double>(); qa.cstride = ctx->cstride; qa.lay = lay;
+        qa.nr0 = m.nr0; qa.nc0 = m.nc0; qa.sig = d_sig.as<int32_t>();
+        qa.row0 = row0; qa.B = B - row0 < Bs ? B - row0 : Bs; qa.lc_index = d_lc;
+        qa.status = ctx->status.as<int32_t>(); qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
+        qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0;
+        qa.normals = normals ? d_q.as<double>() : nullptr;
+        qa.seed_lo = (uint32_t)seed; qa.seed_hi = (uint32_t)(seed >> 32); qa.draw0 = ctx->stream_base;
+        qa.y = d_y.as<double>();
+        // (the copies are ordered on the stream: the next slab's upload and kernel touch the buffers only after them)
+        if (normals) e = hipMemcpyAsync(d_q.p, normals + row0 * N, (size_t)qa.B * row_bytes, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) break;
+        if (!mtg_launch_gp_draw(qa, s)) { e = hipErrorInvalidValue; break; }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(y + row0 * N, d_y.p, (size_t)qa.B * row_bytes, hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    else (void)hipStreamSynchronize(s);
+    d_y.release(); d_q.release(); d_sig.release();
+    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_gp_draw: %s", hipGetErrorString(e));
+    return MTG_OK;
+}
+
 MTG_API int mtg_apply_inverse(mtg_ctx *ctx, const double *theta, int32_t lc_index, int64_t M, double *x,
                               int32_t *status)
 {

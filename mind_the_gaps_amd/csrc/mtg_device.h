@@ -175,6 +175,30 @@ struct MtgPredictAtArgs {
 // both stages of the new-time prediction for one slab; 0 = rank outside 0 .. MTG_MAX_J
 int mtg_launch_predict_at(const MtgPredictAtArgs &, hipStream_t);
 
+// samples per LDS tile of the GP draw (mtg_gp_draw.hip): 64 rows x MTG_DRAW_T samples, row stride MTG_DRAW_T + 1 doubles
+#ifndef MTG_DRAW_T
+#define MTG_DRAW_T 32
+#endif
+
+struct MtgGpDrawArgs {
+    const double *coef;     // SoA coefficient workspace (mtg_prepare_kernel), indexed by the row of the batch
+    int64_t cstride;
+    MtgCoefLayout lay;
+    int nr0, nc0;           // structure with no over-damped SHO term
+    const int32_t *sig;     // [batch] over-damped SHO terms of each evaluation
+    int64_t row0, B;        // this launch takes rows [row0, row0 + B) of the batch (a slab)
+    const int32_t *lc_index;
+    int32_t *status;        // [batch] prior verdict from prepare on entry; MTG_ST_NOTPD added by the sweep
+    const double2 *dxt, *yv;   // of yv only the sigma^2 half is read
+    int64_t N, t_stride;
+    const double *normals;  // [B][N] standard normals of this slab, or NULL: Philox on the device
+    uint32_t seed_lo, seed_hi;
+    int64_t draw0;          // global index of row 0 of the batch (mtg_set_stream_base): random counters only
+    double *y;              // [B][N] of this slab
+};
+// one slab of draws; 0 = rank outside 0 .. MTG_MAX_J
+int mtg_launch_gp_draw(const MtgGpDrawArgs &, hipStream_t);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

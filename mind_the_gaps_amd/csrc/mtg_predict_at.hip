@@ -35,84 +35,7 @@
 // result does not depend on the batch, on M or on the order of ts.
 #include "mtg_math.h"
 #include "mtg_device.h"
-
-template <int J>
-struct PatCoef {
-    double a[J], b[J], c[J], d[J];   // per slot: real j: (a_j, -, c_j, -); complex k: both slots (a_k, b_k, c_k, d_k)
-    double k0, slope, icpt, asum;
-    int NR;
-};
-
-__host__ __device__ constexpr int pat_sy(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
-
-template <int J>
-__device__ __forceinline__ void pat_load_coef(const MtgPredictAtArgs &a, int64_t e, PatCoef<J> &k)
-{
-#pragma clang fp contract(off)
-    const int NR = a.nr0 + 2 * a.sig[e];
-    const double *cf = a.coef + e;
-    const int64_t cs = a.cstride;
-    k.NR = NR;
-    double k0 = 0.0;
-#pragma unroll
-    for (int i = 0; i < J; ++i) {
-        if (i < NR) {
-            k.a[i] = cf[a.lay.ar(i) * cs]; k.c[i] = cf[a.lay.cr(i) * cs]; k.b[i] = 0.0; k.d[i] = 0.0;
-            k0 += k.a[i];
-        } else {
-            const int q = (i - NR) >> 1;
-            k.a[i] = cf[a.lay.ac(q) * cs]; k.b[i] = cf[a.lay.bc(q) * cs];
-            k.c[i] = cf[a.lay.cc(q) * cs]; k.d[i] = cf[a.lay.dc(q) * cs];
-            if (((i - NR) & 1) == 0) k0 += k.a[i];
-        }
-    }
-    k.k0 = k0;
-    k.asum = cf[a.lay.asum() * cs];
-    k.slope = cf[a.lay.mean(0) * cs];
-    k.icpt = cf[a.lay.mean(1) * cs];
-}
-
-// generators at time t: the phase at the elapsed time, reduced modulo 2 pi before it is rounded (mtg_math.h)
-template <int J>
-__device__ __forceinline__ void pat_generators(const PatCoef<J> &k, double t, double t_first, double *U, double *V)
-{
-#pragma clang fp contract(off)
-    double sn = 0.0, cn = 1.0;
-#pragma unroll
-    for (int i = 0; i < J; ++i) {
-        if (i < k.NR) { U[i] = k.a[i]; V[i] = 1.0; }
-        else if (((i - k.NR) & 1) == 0) {
-            mtg_elapsed_sincos(k.d[i], t, t_first, &sn, &cn);
-            U[i] = k.a[i] * cn + k.b[i] * sn; V[i] = cn;
-        } else { U[i] = k.a[i] * sn - k.b[i] * cn; V[i] = sn; }
-    }
-}
-
-// exp(-c dx) per slot (dx >= 0), one exp per term
-template <int J>
-__device__ __forceinline__ void pat_decay(const PatCoef<J> &k, double dx, double *ph)
-{
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < J; ++i) {
-        if (i < k.NR || ((i - k.NR) & 1) == 0) ph[i] = exp(-k.c[i] * dx);
-        else ph[i] = ph[i > 0 ? i - 1 : 0];
-    }
-}
-
-// S <- phi phi^T o (S + Dp Wp Wp^T),  f <- phi o (f + Wp zp)
-template <int J>
-__device__ __forceinline__ void pat_fwd_step(double *S, double *f, const double *ph, const double *Wp, double Dp, double zp)
-{
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < J; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) S[pat_sy(i, j)] = ph[i] * ph[j] * (S[pat_sy(i, j)] + Dp * Wp[i] * Wp[j]);
-        f[i] = ph[i] * (f[i] + Wp[i] * zp);
-    }
-}
-
+#include "mtg_factor_step.h"
 // g <- phn o (g + Un xn): g_n from g_{n+1} and sample n + 1
 template <int J>
 __device__ __forceinline__ void pat_bwd_g(double *g, const double *phn, const double *Un, double xn)

@@ -36,7 +36,7 @@ EXPORTS = (
     "mtg_chain_autocorr", "mtg_fft_warmup", "mtg_simulate_plan", "mtg_ensemble_restore", "mtg_set_sort", "mtg_set_pipeline", "mtg_set_stream_base", "mtg_set_speculation", "mtg_last_solver", "mtg_pair_contexts", "mtg_unpair_contexts", "mtg_pair_stats", "mtg_set_simulate_pairs", "mtg_set_simulate_transform", "mtg_set_simulate_pdf", "mtg_set_simulate_kraft", "mtg_set_simulate_pdf_draws", "mtg_simulate_pdf_report", "mtg_set_pair_patience", "mtg_chain_autocorr_plans_built",
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
-    "mtg_predict_at",
+    "mtg_predict_at", "mtg_gp_draw",
 )
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
@@ -313,6 +313,8 @@ def load_library():
     lib.mtg_predict.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, _ip]
     lib.mtg_predict_at.restype = c_int
     lib.mtg_predict_at.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, _dp, _dp, _ip]
+    lib.mtg_gp_draw.restype = c_int
+    lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_math_probe.restype = c_int
     lib.mtg_math_probe.argtypes = [c_vp, c_i64, _dp, _dp, _dp, _dp, _dp]
     lib.mtg_structure_supported.restype = c_int
@@ -756,6 +758,24 @@ class Engine:
                                              _iptr(status)))
         return mu, var, status
 
+    def gp_draw(self, theta, lc_index=None, seed=0, normals=None):
+        """Realisations of the GP itself, y[b] ~ N(mean, K(theta[b])) on the sampling and error bars of light curve
+        ``lc_index[b]`` -> (y[B][N], status[B]); y excludes the per-light-curve y_offset.  ``normals`` [B][N]: the
+        caller's standard normals (y = mean + L sqrt(D) normals); None: drawn on the device from ``seed`` and the draw's
+        global index (``set_stream_base``), so that a draw does not depend on the batch it travels in (mtg_gp_draw)."""
+        theta = np.atleast_2d(_f64(theta))
+        B = theta.shape[0]
+        lc = None if lc_index is None else np.ascontiguousarray(lc_index, dtype=np.int32)
+        if normals is not None:
+            normals = _f64(normals).reshape(-1, self.N)
+            if normals.shape[0] != B:
+                raise ValueError("normals must have shape (%d, %d)" % (B, self.N))
+        y = np.full((B, self.N), np.nan)
+        status = np.empty(B, dtype=np.int32)
+        self._check(self._lib.mtg_gp_draw(self._ctx, B, _ptr(theta), _iptr(lc), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(normals),
+                                          _ptr(y), _iptr(status)))
+        return y, status
+
     def apply_inverse(self, theta, rhs, lc_index=0):
         """K^-1 rhs for rhs[N] or rhs[N][M] at parameter vector ``theta`` -> (x, status)."""
         rhs = _f64(rhs)
@@ -898,6 +918,6 @@ class Engine:
 
 for _name in ("set_lightcurves", "set_lightcurves_device", "set_model", "loglike", "loglike_device", "loglike_coeffs",
               "ensemble_init", "ensemble_run", "ensemble_restore", "ensemble_state", "chain_autocorr", "simulate_tk95",
-              "tk95_observe_series", "predict", "predict_at", "apply_inverse", "math_probe"):
+              "tk95_observe_series", "predict", "predict_at", "gp_draw", "apply_inverse", "math_probe"):
     setattr(Engine, _name, _one_thread_at_a_time(getattr(Engine, _name)))
 del _name

@@ -359,6 +359,26 @@ class GP(ModelSet):
         self._raise_for(status)
         return x
 
+    def sample(self, size=None, seed=None):
+        """Realisations of the process at the computed times, ``y ~ N(mean, K)`` with the measurement errors and the
+        jitter on the diagonal (celerite.GP.sample -> solver.dot_L): ``[N]`` for ``size=None``, else ``[size][N]``.
+        The draw is ``mean + L sqrt(D) q`` on the device, O(N J^2) each (``Engine.gp_draw``).  ``seed=None``: the
+        normals ``q`` are ``np.random.randn(size, N)`` of numpy's global generator, celerite's own semantics
+        (``np.random.seed`` reproduces a draw); an integer ``seed``: the device draws them itself (Philox4x32-10 keyed
+        by the seed and the draw's index)."""
+        if self._t is None:
+            raise RuntimeError("you must call 'compute' first")
+        n = 1 if size is None else int(size)
+        if n == 0:
+            return np.empty((0, len(self._t)))          # celerite: an empty [0][N] array
+        eng, model = self._bound_engine(self._y_bound if self._y_bound is not None else np.zeros(len(self._t)))
+        theta = np.tile(model.full[model.free_index][None, :], (n, 1))
+        normals = np.random.randn(n, len(self._t)) if seed is None else None
+        y, status = eng.gp_draw(theta, seed=0 if seed is None else int(seed), normals=normals)
+        self._raise_for(status[0])                      # every row has the same theta, hence the same status
+        y += model.y_offset or 0.0
+        return y[0] if size is None else y
+
     def predict(self, y, t=None, return_cov=True, return_var=False):
         """Conditional mean and (co)variance, celerite.GP.predict.
 

@@ -420,11 +420,19 @@ class GPModelling:
         return self._tau
 
     def generate_from_posteriors(self, nsims: int = 10, cpus: int = 8, pdf: str = "Gaussian",
-                                 extension_factor: int = 2, sigma_noise=None):
+                                 extension_factor: int = 2, sigma_noise=None, method: str = "tk95"):
         """Light curves drawn from the MCMC posteriors (gpmodelling.py:478-539): ``nsims``
         random posterior samples, one Timmer & Koenig realisation each on this light
         curve's sampling, noise and error bars from its exposures (or ``sigma_noise``).
-        All simulations run in one device call (``cpus`` is accepted and ignored)."""
+        All simulations run in one device call (``cpus`` is accepted and ignored).
+
+        ``method="gp"``: each posterior sample (kernel and mean parameters) gives one exact draw of the
+        GP itself at the observed epochs, ``y ~ N(mean, K + diag(dy^2))`` (``Engine.gp_draw``, no grid and
+        no window averages), returned with the observed error bars; Gaussian flux PDF only."""
+        if method not in ("tk95", "gp"):
+            raise ValueError("method must be 'tk95' or 'gp', not %r" % (method,))
+        if method == "gp" and pdf != "Gaussian":
+            raise ValueError("method='gp' draws from the Gaussian process itself: pdf must be 'Gaussian', not %r" % (pdf,))
         if self._mcmc_samples is None:
             raise RuntimeError("Posteriors have not been derived. Please run derive_posteriors prior to "
                                "calling this method.")
@@ -435,6 +443,13 @@ class GPModelling:
         from .simulator import Simulator
         param_samples = self._mcmc_samples[np.random.randint(len(self._mcmc_samples), size=nsims)]
         lc = self._lightcurve
+        if method == "gp":
+            eng, model = self.gp._bound_engine(lc.y)
+            y, status = eng.gp_draw(param_samples, seed=np.random.randint(0, 2 ** 31 - 1))
+            for st in status:
+                self.gp._raise_for(st)
+            y += model.y_offset or 0.0
+            return [GappyLightcurve(lc.times, y[i], lc.dy) for i in range(nsims)]
         simulator = Simulator(self.gp.kernel, lc.times, lc.exposures, lc.mean, pdf, lc.bkg_rate, lc.bkg_rate_err,
                               sigma_noise=sigma_noise, extension_factor=extension_factor,
                               random_state=np.random.randint(0, 2 ** 31 - 1), device=self.gp.device)
