@@ -360,9 +360,11 @@ int check_model_workspace(mtg_ctx *ctx, int64_t B)
     return reserve_workspace(ctx, B, lay.nslots(), nsig);
 }
 
-// arguments of the theta -> coefficients expansion into the context's workspace
+// arguments of the theta -> coefficients expansion into the context's workspace; nsig: structure lists to fill
+// (the model's nsho + 1 for the likelihood's solvers; 1 = none: the per-row entries and the simulator, which read the
+// structure of a row from ctx->sig and, like everybody but mtg_ensemble_run, find the context on bank 0)
 MtgPrepArgs make_prep_args(mtg_ctx *ctx, int64_t B, const double *d_theta, int add_prior, double *d_out,
-                           int32_t *d_status)
+                           int32_t *d_status, int nsig)
 {
     MtgPrepArgs pa;
     pa.model = ctx->model;
@@ -371,7 +373,7 @@ MtgPrepArgs make_prep_args(mtg_ctx *ctx, int64_t B, const double *d_theta, int a
     pa.add_prior = add_prior;
     pa.coef = ctx->coef.as<double>();
     pa.cstride = ctx->cstride;
-    pa.nsig = ctx->model.nsho + 1;
+    pa.nsig = nsig;
     pa.lists = bank_lists(ctx);
     pa.counts = bank_counts(ctx);
     pa.out = d_out;
@@ -380,6 +382,62 @@ MtgPrepArgs make_prep_args(mtg_ctx *ctx, int64_t B, const double *d_theta, int a
     pa.row_lo = 0;
     pa.row_hi = INT64_MAX;
     return pa;
+}
+
+int check_lc_index(mtg_ctx *ctx, int64_t B, const int32_t *lc_index)
+{
+    if (lc_index)
+        for (int64_t b = 0; b < B; ++b)
+            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
+                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b, lc_index[b],
+                            (long long)ctx->L);
+    return MTG_OK;
+}
+
+// The prologue of the per-row entries (`who`: mtg_predict, mtg_predict_at, mtg_gp_draw, mtg_apply_inverse): workspace
+// and staging reserved for B rows, theta and lc_index uploaded, theta expanded on stream s -- the prior's verdict in
+// ctx->status, the structure of every row in ctx->sig -- and the head of the kernels' arguments filled for the whole
+// batch.  (ctx->sig, like ctx->coef, is rewritten by every expansion and read by nothing before the next one.)
+int stage_rows(mtg_ctx *ctx, const char *who, int64_t B, const double *theta, const int32_t *lc_index, int add_prior,
+               hipStream_t s, MtgRowArgs &head)
+{
+    const MtgModel &m = ctx->model;
+    const int P = m.P;
+    const MtgCoefLayout lay{m.nr_max, m.nc_max};
+    int rc = reserve_workspace(ctx, B, lay.nslots(), 1);
+    if (rc) return rc;
+    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
+    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
+    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
+    hipError_t e = hipSuccess;
+    const int32_t *d_lc = nullptr;
+    if (P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && lc_index) {
+        e = ctx->lc.reserve((size_t)B * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s);
+        d_lc = ctx->lc.as<int32_t>();
+    }
+    if (e == hipSuccess) {
+        mtg_launch_prepare(make_prep_args(ctx, B, ctx->theta.as<double>(), add_prior, ctx->out.as<double>(),
+                                          ctx->status.as<int32_t>(), 1), s);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    head.coef = ctx->coef.as<double>(); head.cstride = ctx->cstride; head.lay = lay;
+    head.nr0 = m.nr0; head.nc0 = m.nc0; head.sig = ctx->sig.as<int32_t>();
+    head.row0 = 0; head.B = B; head.lc_index = d_lc; head.status = ctx->status.as<int32_t>();
+    head.dxt = ctx->dxt.as<double2>(); head.yv = ctx->yv.as<double2>();
+    head.N = ctx->N; head.t_stride = ctx->t_per_lc ? ctx->N : 0;
+    return MTG_OK;
+}
+
+// fn(row0, rows) for the slabs [row0, row0 + rows) of a batch of B rows, Bs at a time, until one fails
+template <class F>
+hipError_t for_each_slab(int64_t B, int64_t Bs, F fn)
+{
+    hipError_t e = hipSuccess;
+    for (int64_t row0 = 0; e == hipSuccess && row0 < B; row0 += Bs) e = fn(row0, B - row0 < Bs ? B - row0 : Bs);
+    return e;
 }
 
 // One launch of the serial sweep for structure k of the model.  When the resident set is larger than
@@ -429,7 +487,7 @@ int run_model_batch(mtg_ctx *ctx, int64_t B, const double *d_theta, const int32_
     {
         mtg_trace::Range range("mtg:prepare (theta -> prior, coefficients)");
         if (nsig > 1) HIP_TRY(ctx, hipMemsetAsync(bank_counts(ctx), 0, 64 * sizeof(int), s));
-        mtg_launch_prepare(make_prep_args(ctx, B, d_theta, add_prior, d_out, d_status), s);
+        mtg_launch_prepare(make_prep_args(ctx, B, d_theta, add_prior, d_out, d_status, nsig), s);
     }
     if (prof) HIP_TRY(ctx, hipEventRecord(pe[1], s));
     {
@@ -1061,17 +1119,15 @@ MTG_API int mtg_loglike_batch(mtg_ctx *ctx, int64_t B, const double *theta, cons
         return fail(ctx, MTG_E_ARG, "mtg_loglike_batch: bad arguments");
     if (B == 0) return MTG_OK;
     if (B > INT32_MAX) return fail(ctx, MTG_E_ARG, "batch too large");
-    // (the same pass tells whether the caller's order is already grouped by light curve: then the sweep keeps it)
+    rc = check_lc_index(ctx, B, lc_index);
+    if (rc) return rc;
+    // is the caller's order already grouped by light curve?  Then the sweep keeps it
     int64_t runs = 1;
     bool ascending = true;
-    if (lc_index)
-        for (int64_t b = 0; b < B; ++b) {
-            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
-                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b,
-                            lc_index[b], (long long)ctx->L);
-            if (b > 0 && lc_index[b] != lc_index[b - 1]) ++runs;
-            if (b > 0 && lc_index[b] < lc_index[b - 1]) ascending = false;
-        }
+    for (int64_t b = 1; lc_index && b < B; ++b) {
+        if (lc_index[b] != lc_index[b - 1]) ++runs;
+        if (lc_index[b] < lc_index[b - 1]) ascending = false;
+    }
     rc = use_device(ctx);
     if (rc) return rc;
     // grouped: already in ascending order (sorting changes nothing), or in runs of equal indices long enough that a
@@ -1118,11 +1174,8 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
     mtg_solve_launcher fn = mtg_find_solver(jr, jc);
     if (!fn)
         return fail(ctx, MTG_E_UNSUPPORTED, "no compiled kernel for %d real + %d complex terms", jr, jc);
-    if (lc_index)
-        for (int64_t b = 0; b < B; ++b)
-            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
-                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b,
-                            lc_index[b], (long long)ctx->L);
+    rc = check_lc_index(ctx, B, lc_index);
+    if (rc) return rc;
     rc = use_device(ctx);
     if (rc) return rc;
     MtgCoefLayout lay{jr, jc};
@@ -1551,7 +1604,7 @@ MTG_API int mtg_ensemble_run(mtg_ctx *ctx, int steps, double *chain, double *lnp
     } live_rows(ctx, sharded ? (ctx->shard_hi > ctx->shard_lo ? ctx->shard_hi - ctx->shard_lo : 1) : 0);
     auto prep_args = [&](int bank) {
         ctx->bank = bank;
-        MtgPrepArgs pa = make_prep_args(ctx, EH, ctx->ens_q.as<double>(), 1, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>());
+        MtgPrepArgs pa = make_prep_args(ctx, EH, ctx->ens_q.as<double>(), 1, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>(), ctx->model.nsho + 1);
         if (sharded) {
             pa.row_lo = ctx->shard_lo;
             pa.row_hi = ctx->shard_hi;
@@ -1585,7 +1638,7 @@ MTG_API int mtg_ensemble_run(mtg_ctx *ctx, int steps, double *chain, double *lnp
         if (rc) return rc;
         auto prep3 = [&](int bank_) {
             ctx->bank = bank_;
-            return make_prep_args(ctx, rows3, ctx->ens_q.as<double>(), 1, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>());
+            return make_prep_args(ctx, rows3, ctx->ens_q.as<double>(), 1, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>(), ctx->model.nsho + 1);
         };
         // the splits of the whole run in one launch over the whole GPU, where they are small (an ensemble or a few): the
         // sampler kernel of an iteration is one workgroup's chain of latencies and ranking W keys is 2-5 us of it
@@ -2039,13 +2092,9 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
     const int czt_pairs = czt ? czt_pairs_for(czt_m, S, czt_per) : 0;
     const int64_t chunk = czt ? czt_per * (int64_t)czt_pairs : sim_batch_for(nfft, S);
     DevBuf &spec = ctx->sim_spec, &series = ctx->sim_series;
-    DevBuf d_lo, d_hi, d_expo, d_clean, d_rates, d_dy, d_sig, d_means, d_psd, d_seg;
+    DevBuf d_lo, d_hi, d_expo, d_clean, d_rates, d_dy, d_means, d_psd, d_seg;
     hipError_t e = hipSuccess;
     const char *what = "allocation";
-    auto cleanup = [&]() {
-        DevBuf *bufs[] = {&d_lo, &d_hi, &d_expo, &d_clean, &d_rates, &d_dy, &d_sig, &d_means, &d_psd, &d_seg};
-        for (DevBuf *b : bufs) b->release();
-    };
     HIP_TRY(ctx, ctx->theta.reserve((size_t)S * (P > 0 ? P : 1) * 8));
     HIP_TRY(ctx, ctx->out.reserve((size_t)S * 8));
     HIP_TRY(ctx, ctx->status.reserve((size_t)S * 4));
@@ -2057,7 +2106,6 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
     if (e == hipSuccess && clean) e = d_clean.reserve((size_t)S * N * 8);
     if (e == hipSuccess) e = d_rates.reserve((size_t)S * N * 8);
     if (e == hipSuccess) e = d_dy.reserve((size_t)S * N * 8);
-    if (e == hipSuccess) e = d_sig.reserve((size_t)S * 4);
     if (e == hipSuccess) e = d_means.reserve((size_t)S * 8);
     if (e == hipSuccess && psd_table) e = d_psd.reserve((size_t)psd_rows * nk * 8);
     if (e == hipSuccess && psd_table) e = hipMemcpyAsync(d_psd.p, psd_table, (size_t)psd_rows * nk * 8, hipMemcpyHostToDevice, s);
@@ -2068,12 +2116,7 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
     if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)S * P * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && !psd_table) {
         // theta -> celerite coefficients (no prior: the samples come from the posterior itself)
-        MtgPrepArgs pa;
-        pa.model = m; pa.theta = ctx->theta.as<double>(); pa.B = S; pa.add_prior = 0;
-        pa.coef = ctx->coef.as<double>(); pa.cstride = ctx->cstride; pa.nsig = 1;
-        pa.lists = ctx->lists.as<int>(); pa.counts = ctx->counts.as<int>();
-        pa.out = ctx->out.as<double>(); pa.status = ctx->status.as<int32_t>(); pa.sig = d_sig.as<int32_t>();
-        mtg_launch_prepare(pa, s);
+        mtg_launch_prepare(make_prep_args(ctx, S, ctx->theta.as<double>(), 0, ctx->out.as<double>(), ctx->status.as<int32_t>(), 1), s);
         e = hipGetLastError();
     }
     hipfftHandle plan = 0;
@@ -2083,7 +2126,6 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
                                    ? MTG_E_HIP : czt_plan_get(ctx, czt_m, czt_pairs, &plan))
                             : sim_plan_get(ctx, nfft, S, &plan);
         if (prc != MTG_OK || hipfftSetStream(plan, s) != HIPFFT_SUCCESS) {
-            cleanup();
             return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipFFT plan creation failed (nfft = %lld, batch = %lld)",
                         (long long)nfft, (long long)chunk);
         }
@@ -2094,7 +2136,7 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
         const int64_t sc = s0 + chunk <= S ? chunk : S - s0;
         what = "simulation kernels";
         mtg_launch_tk95_spectrum(sc, s0, ctx->stream_base, nfft, sim_dt, ctx->coef.as<double>(), ctx->cstride, lay, m.nr0, m.nc0,
-                                 d_sig.as<int32_t>(), psd_table ? d_psd.as<double>() : nullptr, psd_rows, seed, given_normals,
+                                 ctx->sig.as<int32_t>(), psd_table ? d_psd.as<double>() : nullptr, psd_rows, seed, given_normals,
                                  spec.as<double2>(), s);
         if (czt) {
             // pairs of series through two power-of-two complex transforms (a short last group packs zeros into the
@@ -2108,7 +2150,6 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
             if (ok) mtg_launch_czt_mul(used, czt_m, ctx->czt.bhat.as<double2>(), work, s);
             ok = ok && hipfftExecZ2Z(plan, (hipfftDoubleComplex *)work, (hipfftDoubleComplex *)work, HIPFFT_BACKWARD) == HIPFFT_SUCCESS;
             if (!ok) {
-                cleanup();
                 return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipfftExecZ2Z failed");  // (the resident set is untouched so far)
             }
             mtg_launch_czt_unpack(sc, czt_per, nfft, czt_m, work, ctx->czt.chirp.as<double2>(), series.as<double>(), s);
@@ -2117,7 +2158,6 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
                 e = hipMemsetAsync((char *)spec.p + (size_t)sc * nk * 16, 0, (size_t)(chunk - sc) * nk * 16, s);
             if (e != hipSuccess) break;
             if (hipfftExecZ2D(plan, (hipfftDoubleComplex *)spec.p, series.as<double>()) != HIPFFT_SUCCESS) {
-                cleanup();
                 return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipfftExecZ2D failed");  // (the resident set is untouched so far)
             }
         }
@@ -2134,7 +2174,6 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
             if (e != hipSuccess) break;
             const int arc = e13_adjust_chunk(ctx, sc, chunk, s0, seg_len, mean_rate, seed, s);
             if (arc) {
-                cleanup();
                 if (make_resident) { ctx->N = 0; ctx->L = 0; }
                 return arc;
             }
@@ -2169,8 +2208,6 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
     if (e == hipSuccess) e = hipMemcpyAsync(rates, d_rates.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dy, d_dy.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    cleanup();
-    yv_tmp.release();
     // the plan's buffers stay with the context for the next call of the workflow -- unless they are large enough to be
     // in somebody's way (a fine simulation grid: hundreds of MB per transform)
     if (spec.cap + series.cap + ctx->czt.work.cap > ((size_t)1 << 30)) { spec.release(); series.release(); ctx->czt.work.release(); }
@@ -2234,55 +2271,28 @@ MTG_API int mtg_predict(mtg_ctx *ctx, int64_t B, const double *theta, const int3
     if (rc) return rc;
     if (B <= 0 || !mu || !var || !status || (!theta && ctx->model.P > 0))
         return fail(ctx, MTG_E_ARG, "mtg_predict: bad arguments");
-    if (lc_index)
-        for (int64_t b = 0; b < B; ++b)
-            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
-                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b, lc_index[b],
-                            (long long)ctx->L);
+    rc = check_lc_index(ctx, B, lc_index);
+    if (rc) return rc;
     rc = use_device(ctx);
     if (rc) return rc;
-    const MtgModel &m = ctx->model;
-    const int P = m.P, J = m.nr_max + 2 * m.nc_max, N = (int)ctx->N;
-    MtgCoefLayout lay{m.nr_max, m.nc_max};
-    rc = reserve_workspace(ctx, B, lay.nslots(), 1);
-    if (rc) return rc;
+    const int J = ctx->model.nr_max + 2 * ctx->model.nc_max, N = (int)ctx->N;
     CTX_STREAM(ctx, s);
-    DevBuf work, d_mu, d_var, d_sig;
-    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
-    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
-    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
+    MtgPredictArgs qa;
+    rc = stage_rows(ctx, "mtg_predict", B, theta, lc_index, 1, s, qa);
+    if (rc) return rc;
+    DevBuf work, d_mu, d_var;
     hipError_t e = work.reserve((size_t)B * N * (3 * J + 2) * 8);
     if (e == hipSuccess) e = d_mu.reserve((size_t)B * N * 8);
     if (e == hipSuccess) e = d_var.reserve((size_t)B * N * 8);
-    if (e == hipSuccess) e = d_sig.reserve((size_t)B * 4);
-    const int32_t *d_lc = nullptr;
-    if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && lc_index) {
-        e = ctx->lc.reserve((size_t)B * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s);
-        d_lc = ctx->lc.as<int32_t>();
-    }
     if (e == hipSuccess) {
-        MtgPrepArgs pa;
-        pa.model = m; pa.theta = ctx->theta.as<double>(); pa.B = B; pa.add_prior = 1;
-        pa.coef = ctx->coef.as<double>(); pa.cstride = ctx->cstride; pa.nsig = 1;
-        pa.lists = ctx->lists.as<int>(); pa.counts = ctx->counts.as<int>();
-        pa.out = ctx->out.as<double>(); pa.status = ctx->status.as<int32_t>(); pa.sig = d_sig.as<int32_t>();
-        mtg_launch_prepare(pa, s);
-        MtgPredictArgs qa;
-        qa.coef = ctx->coef.as<double>(); qa.cstride = ctx->cstride; qa.lay = lay;
-        qa.nr0 = m.nr0; qa.nc0 = m.nc0; qa.sig = d_sig.as<int32_t>(); qa.B = B; qa.lc_index = d_lc;
-        qa.status_in = ctx->status.as<int32_t>(); qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
-        qa.N = ctx->N; qa.t_stride = ctx->t_per_lc ? ctx->N : 0; qa.work = work.as<double>();
-        qa.mu = d_mu.as<double>(); qa.var = d_var.as<double>(); qa.status = ctx->status.as<int32_t>();
-        mtg_launch_predict(&qa, s);
+        qa.work = work.as<double>(); qa.mu = d_mu.as<double>(); qa.var = d_var.as<double>();
+        mtg_launch_predict(qa, s);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(mu, d_mu.p, (size_t)B * N * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(var, d_var.p, (size_t)B * N * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    work.release(); d_mu.release(); d_var.release(); d_sig.release();
     if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_predict: %s", hipGetErrorString(e));
     return MTG_OK;
 }
@@ -2297,11 +2307,8 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
     if (rc) return rc;
     if (B <= 0 || M <= 0 || !ts || !mu || !status || (!theta && ctx->model.P > 0))
         return fail(ctx, MTG_E_ARG, "mtg_predict_at: bad arguments");
-    if (lc_index)
-        for (int64_t b = 0; b < B; ++b)
-            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
-                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b, lc_index[b],
-                            (long long)ctx->L);
+    rc = check_lc_index(ctx, B, lc_index);
+    if (rc) return rc;
     bool ascending = true;
     for (int64_t m = 0; m < M; ++m) {
         if (!std::isfinite(ts[m])) return fail(ctx, MTG_E_ARG, "mtg_predict_at: ts[%lld] is not finite", (long long)m);
@@ -2317,13 +2324,9 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
     }
     rc = use_device(ctx);
     if (rc) return rc;
-    const MtgModel &m = ctx->model;
-    const int P = m.P, J = m.nr0 + 2 * m.nc0;
+    const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
     const int64_t N = ctx->N;
     if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_predict_at: rank %d > %d", J, MTG_MAX_J);
-    MtgCoefLayout lay{m.nr_max, m.nc_max};
-    rc = reserve_workspace(ctx, B, lay.nslots(), 1);
-    if (rc) return rc;
     CTX_STREAM(ctx, s);
     // rows per slab: the stored generators within MTG_PAT_SLAB_BYTES, and the grid of the second stage within 2^30 blocks
     const size_t row_bytes = (size_t)N * (3 * J + 3) * 8;
@@ -2335,57 +2338,36 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
     if (mblocks > ((int64_t)1 << 30)) return fail(ctx, MTG_E_ARG, "mtg_predict_at: M = %lld is too large", (long long)M);
     const int64_t nck = (N + MTG_PAT_C - 1) / MTG_PAT_C;
     const size_t ck_bytes = (size_t)nck * (J * (J + 1) / 2 + J) * 8;
-    DevBuf work, ckf, ckb, ckr, d_mu, d_var, d_sig, d_ts, d_order;
-    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
-    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
-    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
+    MtgPredictAtArgs qa;
+    rc = stage_rows(ctx, "mtg_predict_at", B, theta, lc_index, 1, s, qa);
+    if (rc) return rc;
+    DevBuf work, ckf, ckb, ckr, d_mu, d_var, d_ts, d_order;
     hipError_t e = work.reserve((size_t)Bs * row_bytes + 8);
     if (e == hipSuccess) e = ckf.reserve((size_t)Bs * ck_bytes + 8);
     if (e == hipSuccess) e = ckb.reserve((size_t)Bs * ck_bytes + 8);
     if (e == hipSuccess) e = ckr.reserve((size_t)Bs * (J * (J + 1) / 2) * 8 + 8);
     if (e == hipSuccess) e = d_mu.reserve((size_t)Bs * M * 8);
     if (e == hipSuccess && var) e = d_var.reserve((size_t)Bs * M * 8);
-    if (e == hipSuccess) e = d_sig.reserve((size_t)B * 4);
     if (e == hipSuccess) e = d_ts.reserve((size_t)M * 8);
     if (e == hipSuccess && !ascending) e = d_order.reserve((size_t)M * 8);
-    const int32_t *d_lc = nullptr;
-    if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_ts.p, ts, (size_t)M * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && !ascending) e = hipMemcpyAsync(d_order.p, order.data(), (size_t)M * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && lc_index) {
-        e = ctx->lc.reserve((size_t)B * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s);
-        d_lc = ctx->lc.as<int32_t>();
-    }
-    if (e == hipSuccess) {
-        MtgPrepArgs pa;
-        pa.model = m; pa.theta = ctx->theta.as<double>(); pa.B = B; pa.add_prior = 1;
-        pa.coef = ctx->coef.as<double>(); pa.cstride = ctx->cstride; pa.nsig = 1;
-        pa.lists = ctx->lists.as<int>(); pa.counts = ctx->counts.as<int>();
-        pa.out = ctx->out.as<double>(); pa.status = ctx->status.as<int32_t>(); pa.sig = d_sig.as<int32_t>();
-        mtg_launch_prepare(pa, s);
-        e = hipGetLastError();
-    }
-    for (int64_t row0 = 0; e == hipSuccess && row0 < B; row0 += Bs) {
-        MtgPredictAtArgs qa;
-        qa.coef = ctx->coef.as<double>(); qa.cstride = ctx->cstride; qa.lay = lay;
-        qa.nr0 = m.nr0; qa.nc0 = m.nc0; qa.sig = d_sig.as<int32_t>();
-        qa.row0 = row0; qa.B = B - row0 < Bs ? B - row0 : Bs; qa.lc_index = d_lc;
-        qa.status = ctx->status.as<int32_t>(); qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
-        qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.work = work.as<double>();
-        qa.nck = nck; qa.ckf = ckf.as<double>(); qa.ckb = ckb.as<double>(); qa.ckr = ckr.as<double>(); qa.want_var = var ? 1 : 0;
-        qa.M = M; qa.ts = d_ts.as<double>(); qa.order = ascending ? nullptr : d_order.as<int64_t>();
-        qa.mu = d_mu.as<double>(); qa.var = var ? d_var.as<double>() : nullptr;
-        if (!mtg_launch_predict_at(qa, s)) { e = hipErrorInvalidValue; break; }
-        e = hipGetLastError();
+    qa.work = work.as<double>();
+    qa.nck = nck; qa.ckf = ckf.as<double>(); qa.ckb = ckb.as<double>(); qa.ckr = ckr.as<double>(); qa.want_var = var ? 1 : 0;
+    qa.M = M; qa.ts = d_ts.as<double>(); qa.order = ascending ? nullptr : d_order.as<int64_t>();
+    qa.mu = d_mu.as<double>(); qa.var = var ? d_var.as<double>() : nullptr;
+    if (e == hipSuccess) e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
+        qa.row0 = row0; qa.B = rows;
+        if (!mtg_launch_predict_at(qa, s)) return hipErrorInvalidValue;
+        hipError_t e = hipGetLastError();
         // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
-        if (e == hipSuccess) e = hipMemcpyAsync(mu + row0 * M, d_mu.p, (size_t)qa.B * M * 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && var) e = hipMemcpyAsync(var + row0 * M, d_var.p, (size_t)qa.B * M * 8, hipMemcpyDeviceToHost, s);
-    }
+        if (e == hipSuccess) e = hipMemcpyAsync(mu + row0 * M, d_mu.p, (size_t)rows * M * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && var) e = hipMemcpyAsync(var + row0 * M, d_var.p, (size_t)rows * M * 8, hipMemcpyDeviceToHost, s);
+        return e;
+    });
     if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     else (void)hipStreamSynchronize(s);
-    work.release(); ckf.release(); ckb.release(); ckr.release(); d_mu.release(); d_var.release(); d_sig.release(); d_ts.release(); d_order.release();
     if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_predict_at: %s", hipGetErrorString(e));
     return MTG_OK;
 }
@@ -2401,69 +2383,40 @@ MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int3
     if (rc) return rc;
     if (B <= 0 || !y || !status || (!theta && ctx->model.P > 0))
         return fail(ctx, MTG_E_ARG, "mtg_gp_draw: bad arguments");
-    if (lc_index)
-        for (int64_t b = 0; b < B; ++b)
-            if (lc_index[b] < 0 || lc_index[b] >= ctx->L)
-                return fail(ctx, MTG_E_ARG, "lc_index[%lld] = %d outside [0, %lld)", (long long)b, lc_index[b],
-                            (long long)ctx->L);
+    rc = check_lc_index(ctx, B, lc_index);
+    if (rc) return rc;
     rc = use_device(ctx);
     if (rc) return rc;
-    const MtgModel &m = ctx->model;
-    const int P = m.P, J = m.nr0 + 2 * m.nc0;
+    const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
     const int64_t N = ctx->N;
     if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_gp_draw: rank %d > %d", J, MTG_MAX_J);
-    MtgCoefLayout lay{m.nr_max, m.nc_max};
-    rc = reserve_workspace(ctx, B, lay.nslots(), 1);
-    if (rc) return rc;
     CTX_STREAM(ctx, s);
     const size_t row_bytes = (size_t)N * 8;
     int64_t Bs = (int64_t)(MTG_DRAW_SLAB_BYTES / row_bytes) / 64 * 64;
     if (Bs < 64) Bs = 64;
     if (Bs > B) Bs = B;
-    DevBuf d_y, d_q, d_sig;
-    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
-    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
-    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
+    MtgGpDrawArgs qa;
+    rc = stage_rows(ctx, "mtg_gp_draw", B, theta, lc_index, 1, s, qa);
+    if (rc) return rc;
+    DevBuf d_y, d_q;
     hipError_t e = d_y.reserve((size_t)Bs * row_bytes);
     if (e == hipSuccess && normals) e = d_q.reserve((size_t)Bs * row_bytes);
-    if (e == hipSuccess) e = d_sig.reserve((size_t)B * 4);
-    const int32_t *d_lc = nullptr;
-    if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && lc_index) {
-        e = ctx->lc.reserve((size_t)B * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s);
-        d_lc = ctx->lc.as<int32_t>();
-    }
-    if (e == hipSuccess) {
-        MtgPrepArgs pa;
-        pa.model = m; pa.theta = ctx->theta.as<double>(); pa.B = B; pa.add_prior = 1;
-        pa.coef = ctx->coef.as<double>(); pa.cstride = ctx->cstride; pa.nsig = 1;
-        pa.lists = ctx->lists.as<int>(); pa.counts = ctx->counts.as<int>();
-        pa.out = ctx->out.as<double>(); pa.status = ctx->status.as<int32_t>(); pa.sig = d_sig.as<int32_t>();
-        mtg_launch_prepare(pa, s);
-        e = hipGetLastError();
-    }
-    for (int64_t row0 = 0; e == hipSuccess && row0 < B; row0 += Bs) {
-        MtgGpDrawArgs qa;
-        qa.coef = ctx->coef.as<double>(); qa.cstride = ctx->cstride; qa.lay = lay;
-        qa.nr0 = m.nr0; qa.nc0 = m.nc0; qa.sig = d_sig.as<int32_t>();
-        qa.row0 = row0; qa.B = B - row0 < Bs ? B - row0 : Bs; qa.lc_index = d_lc;
-        qa.status = ctx->status.as<int32_t>(); qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
-        qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0;
-        qa.normals = normals ? d_q.as<double>() : nullptr;
-        qa.seed_lo = (uint32_t)seed; qa.seed_hi = (uint32_t)(seed >> 32); qa.draw0 = ctx->stream_base;
-        qa.y = d_y.as<double>();
+    qa.normals = normals ? d_q.as<double>() : nullptr;
+    qa.seed_lo = (uint32_t)seed; qa.seed_hi = (uint32_t)(seed >> 32); qa.draw0 = ctx->stream_base;
+    qa.y = d_y.as<double>();
+    if (e == hipSuccess) e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
+        qa.row0 = row0; qa.B = rows;
         // (the copies are ordered on the stream: the next slab's upload and kernel touch the buffers only after them)
-        if (normals) e = hipMemcpyAsync(d_q.p, normals + row0 * N, (size_t)qa.B * row_bytes, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) break;
-        if (!mtg_launch_gp_draw(qa, s)) { e = hipErrorInvalidValue; break; }
+        hipError_t e = normals ? hipMemcpyAsync(d_q.p, normals + row0 * N, (size_t)rows * row_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+        if (e != hipSuccess) return e;
+        if (!mtg_launch_gp_draw(qa, s)) return hipErrorInvalidValue;
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(y + row0 * N, d_y.p, (size_t)qa.B * row_bytes, hipMemcpyDeviceToHost, s);
-    }
+        if (e == hipSuccess) e = hipMemcpyAsync(y + row0 * N, d_y.p, (size_t)rows * row_bytes, hipMemcpyDeviceToHost, s);
+        return e;
+    });
     if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     else (void)hipStreamSynchronize(s);
-    d_y.release(); d_q.release(); d_sig.release();
     if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_gp_draw: %s", hipGetErrorString(e));
     return MTG_OK;
 }
@@ -2480,41 +2433,23 @@ MTG_API int mtg_apply_inverse(mtg_ctx *ctx, const double *theta, int32_t lc_inde
     rc = use_device(ctx);
     if (rc) return rc;
     const MtgModel &m = ctx->model;
-    const int P = m.P, Jws = m.nr_max + 2 * m.nc_max, J = m.nr0 + 2 * m.nc0;
+    const int Jws = m.nr_max + 2 * m.nc_max, J = m.nr0 + 2 * m.nc0;
     const int64_t N = ctx->N;
-    MtgCoefLayout lay{m.nr_max, m.nc_max};
-    rc = reserve_workspace(ctx, 1, lay.nslots(), 1);
-    if (rc) return rc;
     CTX_STREAM(ctx, s);
-    DevBuf work, d_mu, d_var, d_sig, d_x;
-    HIP_TRY(ctx, ctx->theta.reserve((size_t)(P > 0 ? P : 1) * 8));
-    HIP_TRY(ctx, ctx->out.reserve(8));
-    HIP_TRY(ctx, ctx->status.reserve(4));
-    HIP_TRY(ctx, ctx->lc.reserve(4));
+    // the factorisation of this parameter vector: the forward sweep of mtg_predict_kernel leaves
+    // U_n, W_n, phi_n, D_n of every sample in `work`
+    MtgPredictArgs qa;
+    rc = stage_rows(ctx, "mtg_apply_inverse", 1, theta, &lc_index, 1, s, qa);
+    if (rc) return rc;
+    DevBuf work, d_mu, d_var, d_x;
     hipError_t e = work.reserve((size_t)N * (3 * Jws + 2) * 8);
     if (e == hipSuccess) e = d_mu.reserve((size_t)N * 8);
     if (e == hipSuccess) e = d_var.reserve((size_t)N * 8);
-    if (e == hipSuccess) e = d_sig.reserve(4);
     if (e == hipSuccess) e = d_x.reserve((size_t)N * M * 8);
-    if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)P * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, &lc_index, 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_x.p, x, (size_t)N * M * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        // the factorisation of this parameter vector: the forward sweep of mtg_predict_kernel leaves
-        // U_n, W_n, phi_n, D_n of every sample in `work`
-        MtgPrepArgs pa;
-        pa.model = m; pa.theta = ctx->theta.as<double>(); pa.B = 1; pa.add_prior = 1;
-        pa.coef = ctx->coef.as<double>(); pa.cstride = ctx->cstride; pa.nsig = 1;
-        pa.lists = ctx->lists.as<int>(); pa.counts = ctx->counts.as<int>();
-        pa.out = ctx->out.as<double>(); pa.status = ctx->status.as<int32_t>(); pa.sig = d_sig.as<int32_t>();
-        mtg_launch_prepare(pa, s);
-        MtgPredictArgs qa;
-        qa.coef = ctx->coef.as<double>(); qa.cstride = ctx->cstride; qa.lay = lay;
-        qa.nr0 = m.nr0; qa.nc0 = m.nc0; qa.sig = d_sig.as<int32_t>(); qa.B = 1; qa.lc_index = ctx->lc.as<int32_t>();
-        qa.status_in = ctx->status.as<int32_t>(); qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
-        qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.work = work.as<double>();
-        qa.mu = d_mu.as<double>(); qa.var = d_var.as<double>(); qa.status = ctx->status.as<int32_t>();
-        mtg_launch_predict(&qa, s);
+        qa.work = work.as<double>(); qa.mu = d_mu.as<double>(); qa.var = d_var.as<double>();
+        mtg_launch_predict(qa, s);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, 4, hipMemcpyDeviceToHost, s);
@@ -2525,7 +2460,6 @@ MTG_API int mtg_apply_inverse(mtg_ctx *ctx, const double *theta, int32_t lc_inde
         if (e == hipSuccess) e = hipMemcpyAsync(x, d_x.p, (size_t)N * M * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
-    work.release(); d_mu.release(); d_var.release(); d_sig.release(); d_x.release();
     if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_apply_inverse: %s", hipGetErrorString(e));
     return MTG_OK;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/mtg.h"
 
@@ -129,29 +130,9 @@ size_t mtg_tables_bytes();
 // serialised 64-fold -- measured as 5.6 us per scan round instead of ~1)
 #define MTG_TP_ELEM(J) (((J) * (J) + 2 * (J) + (J) * ((J) + 1) + 5) | 1)
 
-struct MtgPredictArgs {
-    const double *coef;     // SoA coefficient workspace (mtg_prepare_kernel)
-    int64_t cstride;
-    MtgCoefLayout lay;
-    int nr0, nc0;           // structure with no over-damped SHO term
-    const int32_t *sig;     // [B] over-damped SHO terms of each evaluation
-    int64_t B;
-    const int32_t *lc_index;
-    const int32_t *status_in;   // prior verdict from prepare
-    const double2 *dxt, *yv;
-    int64_t N, t_stride;
-    double *work;           // [B][N][3 J + 2]: U, W, phi (per slot), D, z
-    double *mu, *var;       // [B][N]
-    int32_t *status;        // [B]
-};
-
-// samples between two checkpoints of the new-time prediction (mtg_predict_at.hip): a new time replays at most this
-// many stored steps in each direction; the checkpoints take N J^2 / C doubles per row
-#ifndef MTG_PAT_C
-#define MTG_PAT_C 64
-#endif
-
-struct MtgPredictAtArgs {
+// What every per-row entry (mtg_predict, mtg_predict_at, mtg_gp_draw, mtg_apply_inverse) hands its kernels: the expanded
+// coefficients of the whole batch and the resident light curves (stage_rows of mtg_capi.hip fills it)
+struct MtgRowArgs {
     const double *coef;     // SoA coefficient workspace (mtg_prepare_kernel), indexed by the row of the batch
     int64_t cstride;
     MtgCoefLayout lay;
@@ -162,6 +143,21 @@ struct MtgPredictAtArgs {
     int32_t *status;        // [batch] prior verdict from prepare on entry; MTG_ST_NOTPD added by the factorisation
     const double2 *dxt, *yv;
     int64_t N, t_stride;
+};
+
+struct MtgPredictArgs : MtgRowArgs {   // the whole batch in one launch: row0 = 0
+    double *work;           // [B][N][3 J + 2]: U, W, phi (per slot), D, z
+    double *mu, *var;       // [B][N]
+};
+void mtg_launch_predict(const MtgPredictArgs &, hipStream_t);
+
+// samples between two checkpoints of the new-time prediction (mtg_predict_at.hip): a new time replays at most this
+// many stored steps in each direction; the checkpoints take N J^2 / C doubles per row
+#ifndef MTG_PAT_C
+#define MTG_PAT_C 64
+#endif
+
+struct MtgPredictAtArgs : MtgRowArgs {
     double *work;           // [B][N][3 J + 3]: U, W, phi (per slot), D, z, x = (K^-1 r)_n
     int64_t nck;            // checkpoints per row: ceil(N / MTG_PAT_C)
     double *ckf, *ckb;      // [B][nck][J (J + 1) / 2 + J]: (S_n, f_n) and (G_n, g_n) at n = k MTG_PAT_C
@@ -180,17 +176,7 @@ int mtg_launch_predict_at(const MtgPredictAtArgs &, hipStream_t);
 #define MTG_DRAW_T 32
 #endif
 
-struct MtgGpDrawArgs {
-    const double *coef;     // SoA coefficient workspace (mtg_prepare_kernel), indexed by the row of the batch
-    int64_t cstride;
-    MtgCoefLayout lay;
-    int nr0, nc0;           // structure with no over-damped SHO term
-    const int32_t *sig;     // [batch] over-damped SHO terms of each evaluation
-    int64_t row0, B;        // this launch takes rows [row0, row0 + B) of the batch (a slab)
-    const int32_t *lc_index;
-    int32_t *status;        // [batch] prior verdict from prepare on entry; MTG_ST_NOTPD added by the sweep
-    const double2 *dxt, *yv;   // of yv only the sigma^2 half is read
-    int64_t N, t_stride;
+struct MtgGpDrawArgs : MtgRowArgs {     // of yv only the sigma^2 half is read
     const double *normals;  // [B][N] standard normals of this slab, or NULL: Philox on the device
     uint32_t seed_lo, seed_hi;
     int64_t draw0;          // global index of row 0 of the batch (mtg_set_stream_base): random counters only
@@ -198,6 +184,8 @@ struct MtgGpDrawArgs {
 };
 // one slab of draws; 0 = rank outside 0 .. MTG_MAX_J
 int mtg_launch_gp_draw(const MtgGpDrawArgs &, hipStream_t);
+static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivially_copyable<MtgPredictAtArgs>::value &&
+              std::is_trivially_copyable<MtgGpDrawArgs>::value, "passed by value as kernel arguments");
 
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
@@ -305,7 +293,6 @@ void mtg_launch_czt_tables(int64_t n, int64_t m, double2 *chirp, double2 *b, hip
 void mtg_launch_czt_pack(int64_t S, int per, int64_t n, int64_t m, const double2 *X, const double2 *chirp, double2 *a, hipStream_t);
 void mtg_launch_czt_mul(int64_t pairs, int64_t m, const double2 *bhat, double2 *a, hipStream_t);
 void mtg_launch_czt_unpack(int64_t S, int per, int64_t n, int64_t m, const double2 *c, const double2 *chirp, double *series, hipStream_t);
-void mtg_launch_predict(const void *predict_args, hipStream_t);
 void mtg_launch_apply_inverse(const double *work, int64_t N, int J, int64_t M, double *x, hipStream_t);
 void mtg_launch_math_probe(int64_t n, const double *x, double *e, double *s, double *c, double *rcp,
                            hipStream_t);

@@ -1,6 +1,6 @@
 // mtg_factor_step.h -- the forward step of the semiseparable factorisation with the state in registers (template on
-// the rank J, runtime split NR real slots | complex pairs): coefficient load, generators, decay and the (S, f)
-// recurrence.  Shared by mtg_predict_at.hip (factorisation + replay) and mtg_gp_draw.hip (the draw y = L sqrt(D) q).
+// the rank J, runtime split NR real slots | complex pairs): coefficient load, generators, decay, the (S, f)
+// recurrence and the pivot; and the switch from a runtime rank to the template.  Shared by mtg_predict_at.hip (factorisation + replay) and mtg_gp_draw.hip (the draw y = L sqrt(D) q).
 #pragma once
 #include "mtg_math.h"
 #include "mtg_device.h"
@@ -14,9 +14,8 @@ struct PatCoef {
 
 __host__ __device__ constexpr int pat_sy(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
-// Args: any launch argument block with coef, cstride, lay, nr0 and sig (MtgPredictAtArgs, MtgGpDrawArgs)
-template <int J, class Args>
-__device__ __forceinline__ void pat_load_coef(const Args &a, int64_t e, PatCoef<J> &k)
+template <int J>
+__device__ __forceinline__ void pat_load_coef(const MtgRowArgs &a, int64_t e, PatCoef<J> &k)
 {
 #pragma clang fp contract(off)
     const int NR = a.nr0 + 2 * a.sig[e];
@@ -81,4 +80,39 @@ __device__ __forceinline__ void pat_fwd_step(double *S, double *f, const double 
         for (int j = 0; j <= i; ++j) S[pat_sy(i, j)] = ph[i] * ph[j] * (S[pat_sy(i, j)] + Dp * Wp[i] * Wp[j]);
         f[i] = ph[i] * (f[i] + Wp[i] * zp);
     }
+}
+
+// the pivot of sample n: q = S U,  Wn = V - q (not yet divided by D),  D -= U^T q
+template <int J>
+__device__ __forceinline__ void pat_pivot(const double *S, const double *U, const double *V, double *Wn, double &D)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+        double q = 0.0;
+#pragma unroll
+        for (int j = 0; j < J; ++j) q += S[pat_sy(i, j)] * U[j];
+        Wn[i] = V[i] - q;
+        D -= U[i] * q;
+    }
+}
+
+// F<J>::launch(args...) for the rank J in 1 .. MTG_MAX_J; 0 = no such rank (rank 0, the white model, is the caller's)
+template <template <int> class F, class... A>
+int pat_dispatch_rank(int J, const A &...args)
+{
+    switch (J) {
+    case 1: F<1>::launch(args...); break;
+    case 2: F<2>::launch(args...); break;
+    case 3: F<3>::launch(args...); break;
+    case 4: F<4>::launch(args...); break;
+    case 5: F<5>::launch(args...); break;
+    case 6: F<6>::launch(args...); break;
+    case 7: F<7>::launch(args...); break;
+    case 8: F<8>::launch(args...); break;
+    case 9: F<9>::launch(args...); break;
+    case 10: F<10>::launch(args...); break;
+    default: return 0;
+    }
+    return 1;
 }

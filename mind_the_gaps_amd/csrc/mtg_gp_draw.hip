@@ -124,14 +124,8 @@ __global__ void __launch_bounds__(64) mtg_gp_draw_kernel(MtgGpDrawArgs a)
                     pat_fwd_step<J>(S, f, ph, Wp, Dp, vp);
                     double Wn[J];
 #pragma unroll
-                    for (int i = 0; i < J; ++i) {
-                        double q = 0.0;
-#pragma unroll
-                        for (int jj = 0; jj < J; ++jj) q += S[pat_sy(i, jj)] * U[jj];
-                        Wn[i] = V[i] - q;
-                        D -= U[i] * q;
-                        uf += U[i] * f[i];
-                    }
+                    for (int i = 0; i < J; ++i) uf += U[i] * f[i];
+                    pat_pivot<J>(S, U, V, Wn, D);
 #pragma unroll
                     for (int i = 0; i < J; ++i) Wp[i] = Wn[i] / D;
                 }
@@ -165,29 +159,20 @@ __global__ void __launch_bounds__(64) mtg_gp_draw_kernel(MtgGpDrawArgs a)
 }
 
 template <int J>
-static void draw_launch(const MtgGpDrawArgs &a, hipStream_t s)
-{
-    const dim3 grid((unsigned)((a.B + 63) / 64)), block(64);
-    if (a.normals) hipLaunchKernelGGL((mtg_gp_draw_kernel<J, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((mtg_gp_draw_kernel<J, false>), grid, block, 0, s, a);
-}
+struct DrawLaunch {
+    static void launch(const MtgGpDrawArgs &a, hipStream_t s)
+    {
+        const dim3 grid((unsigned)((a.B + 63) / 64)), block(64);
+        if (a.normals) hipLaunchKernelGGL((mtg_gp_draw_kernel<J, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((mtg_gp_draw_kernel<J, false>), grid, block, 0, s, a);
+    }
+};
 
 // rows [row0, row0 + B) of the batch; J = nr0 + 2 nc0 in 0 .. MTG_MAX_J (returns 0 otherwise)
 int mtg_launch_gp_draw(const MtgGpDrawArgs &a, hipStream_t s)
 {
-    switch (a.nr0 + 2 * a.nc0) {
-    case 0: draw_launch<0>(a, s); break;
-    case 1: draw_launch<1>(a, s); break;
-    case 2: draw_launch<2>(a, s); break;
-    case 3: draw_launch<3>(a, s); break;
-    case 4: draw_launch<4>(a, s); break;
-    case 5: draw_launch<5>(a, s); break;
-    case 6: draw_launch<6>(a, s); break;
-    case 7: draw_launch<7>(a, s); break;
-    case 8: draw_launch<8>(a, s); break;
-    case 9: draw_launch<9>(a, s); break;
-    case 10: draw_launch<10>(a, s); break;
-    default: return 0;
-    }
+    const int J = a.nr0 + 2 * a.nc0;
+    if (J != 0) return pat_dispatch_rank<DrawLaunch>(J, a, s);
+    DrawLaunch<0>::launch(a, s);
     return 1;
 }

@@ -114,14 +114,8 @@ __global__ void __launch_bounds__(64) mtg_predict_at_factor_kernel(MtgPredictAtA
         double D = yv[n].y + k.asum, z = yv[n].x - (k.slope * t + k.icpt);
         double Wn[J];
 #pragma unroll
-        for (int i = 0; i < J; ++i) {
-            double q = 0.0;
-#pragma unroll
-            for (int j = 0; j < J; ++j) q += S[pat_sy(i, j)] * U[j];
-            Wn[i] = V[i] - q;
-            D -= U[i] * q;
-            z -= U[i] * f[i];
-        }
+        for (int i = 0; i < J; ++i) z -= U[i] * f[i];
+        pat_pivot<J>(S, U, V, Wn, D);
         bad = bad || !(D > 0.0);
         double *w = wk + n * stride;
 #pragma unroll
@@ -183,14 +177,7 @@ __global__ void __launch_bounds__(64) mtg_predict_at_factor_kernel(MtgPredictAtA
         pat_generators<J>(k, t_last, dxt[n].y, U, V);
         pat_fwd_step<J>(S, f, ph, Wp, Dp, 0.0);
         double D = yv[n].y + k.asum;
-#pragma unroll
-        for (int i = 0; i < J; ++i) {
-            double q = 0.0;
-#pragma unroll
-            for (int j = 0; j < J; ++j) q += S[pat_sy(i, j)] * U[j];
-            Wp[i] = V[i] - q;
-            D -= U[i] * q;
-        }
+        pat_pivot<J>(S, U, V, Wp, D);
 #pragma unroll
         for (int i = 0; i < J; ++i) Wp[i] /= D;
         Dp = D;
@@ -267,6 +254,7 @@ __global__ void __launch_bounds__(64) mtg_predict_at_eval_kernel(MtgPredictAtArg
             }
             pat_fwd_step<J>(T, v, ph, Wn, w[3 * J], w[3 * J + 1]);
         }
+        // (pat_pivot's arithmetic, written out: U*^T q is summed from 0 here, not taken off a pivot)
         double uq = 0.0, uf = 0.0;
 #pragma unroll
         for (int i = 0; i < J; ++i) {
@@ -391,31 +379,20 @@ __global__ void __launch_bounds__(64) mtg_predict_at_white_eval_kernel(MtgPredic
 }
 
 template <int J>
-static void pat_launch(const MtgPredictAtArgs &a, hipStream_t s)
-{
-    hipLaunchKernelGGL(mtg_predict_at_factor_kernel<J>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(mtg_predict_at_eval_kernel<J>, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
-}
+struct PatLaunch {
+    static void launch(const MtgPredictAtArgs &a, hipStream_t s)
+    {
+        hipLaunchKernelGGL(mtg_predict_at_factor_kernel<J>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
+        hipLaunchKernelGGL(mtg_predict_at_eval_kernel<J>, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
+    }
+};
 
 // both stages for rows [row0, row0 + B) of the batch; J = nr0 + 2 nc0 in 0 .. MTG_MAX_J (returns 0 otherwise)
 int mtg_launch_predict_at(const MtgPredictAtArgs &a, hipStream_t s)
 {
-    switch (a.nr0 + 2 * a.nc0) {
-    case 0:
-        hipLaunchKernelGGL(mtg_predict_at_white_factor_kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(mtg_predict_at_white_eval_kernel, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
-        break;
-    case 1: pat_launch<1>(a, s); break;
-    case 2: pat_launch<2>(a, s); break;
-    case 3: pat_launch<3>(a, s); break;
-    case 4: pat_launch<4>(a, s); break;
-    case 5: pat_launch<5>(a, s); break;
-    case 6: pat_launch<6>(a, s); break;
-    case 7: pat_launch<7>(a, s); break;
-    case 8: pat_launch<8>(a, s); break;
-    case 9: pat_launch<9>(a, s); break;
-    case 10: pat_launch<10>(a, s); break;
-    default: return 0;
-    }
+    const int J = a.nr0 + 2 * a.nc0;
+    if (J != 0) return pat_dispatch_rank<PatLaunch>(J, a, s);
+    hipLaunchKernelGGL(mtg_predict_at_white_factor_kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(mtg_predict_at_white_eval_kernel, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
     return 1;
 }

@@ -175,7 +175,9 @@ void mtg_launch_initial_best(int E, int W, int P, const double *coords, const do
 //   G_m = U_m U_m^T / D_m + (I - U_m W_m^T) Phi_{m+1} G_{m+1} Phi_{m+1} (I - W_m U_m^T)
 // This is a diagnostic evaluated for one or a few parameter vectors, so it is a plain
 // generic-J kernel (one thread per evaluation, per-step generators kept in a global
-// workspace), not a tuned template family.
+// workspace), not a tuned template family.  Its forward sweep is a copy of its own, not the step functions of
+// mtg_factor_step.h: those keep S symmetric and forbid contraction, this one keeps a full, not-quite-symmetric S and
+// lets the compiler contract, so moving it over would change its bits -- a change of behaviour, to be made on its own.
 #define MTG_PJ MTG_MAX_J
 
 
@@ -190,7 +192,7 @@ __global__ void __launch_bounds__(64) mtg_predict_kernel(MtgPredictArgs a)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= a.B) return;
-    if (a.status_in[e] != MTG_ST_OK) { a.status[e] = a.status_in[e]; mtg_predict_nan_row(a, e); return; }
+    if (a.status[e] != MTG_ST_OK) { mtg_predict_nan_row(a, e); return; }     // the prior's verdict (prepare) stands
     const int NR = a.nr0 + 2 * a.sig[e], NC = a.nc0 - a.sig[e], J = NR + 2 * NC;
     const double *cf = a.coef + e;
     const int64_t cs = a.cstride;
@@ -336,8 +338,7 @@ void mtg_launch_apply_inverse(const double *work, int64_t N, int J, int64_t M, d
     hipLaunchKernelGGL(mtg_apply_inverse_kernel, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, s, work, N, J, M, x);
 }
 
-void mtg_launch_predict(const void *args_void, hipStream_t s)
+void mtg_launch_predict(const MtgPredictArgs &a, hipStream_t s)
 {
-    const MtgPredictArgs &a = *static_cast<const MtgPredictArgs *>(args_void);
     hipLaunchKernelGGL(mtg_predict_kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
 }
