@@ -194,11 +194,9 @@ __global__ void __launch_bounds__(MTG_BLOCK) mtg_white_kernel(MtgSolveArgs a)
         dexp += __builtin_amdgcn_frexp_exp(dprod);
         dprod = __builtin_amdgcn_frexp_mant(dprod);
     }
-    const double logdet = fma((double)dexp, 0.69314718055994530942, log(dprod));
-    double ll = -0.5 * fma((double)a.N, MTG_LN_2PI, dot + logdet);
-    int st = MTG_ST_OK;
-    if (dmin_hi <= 0) { st = MTG_ST_NOTPD; ll = -INFINITY; }
-    else if (!isfinite(ll)) { st = MTG_ST_NONFINITE; ll = -INFINITY; }
+    double ll;
+    int st;
+    mtg_finish_lnl(a.N, dot, dprod, dexp, dmin_hi, &ll, &st);
     a.out[e] = ll;
     a.status[e] = st;
 }

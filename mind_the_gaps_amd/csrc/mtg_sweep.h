@@ -4,12 +4,8 @@
 #ifndef MTG_SWEEP_H
 #define MTG_SWEEP_H
 
-#include "mtg_device.h"
-#include "mtg_math.h"
+#include "mtg_sweep_step.h"
 
-#include <math.h>
-
-#define MTG_LN_2PI 1.8378770664093454835606594728112
 #define MTG_BLOCK 256
 
 // ---------------------------------------------------------------------------
@@ -73,11 +69,8 @@ __device__ __forceinline__ void mtg_sweep(MtgLane<NR, NC> &L, const MtgSolveArgs
         __builtin_amdgcn_make_buffer_rsrc((void *)yv_base, 0, (int)yv_records, 0x00020000);
     const __amdgpu_buffer_rsrc_t rdt =
         __builtin_amdgcn_make_buffer_rsrc((void *)dxt_base, 0, (int)dxt_records, 0x00020000);
-    auto ld = [](__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-        return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
 
-    const double t0 = ld(rdt, toff, 0).y;  // phases are measured from the first sample
+    const double t0 = mtg_ld128(rdt, toff, 0).y;  // phases are measured from the first sample
     // One step of the recurrence for the sample (dxc, tc, yc, vc): a single basic block.
     auto step = [&](const double2 dtc, const double2 yvc) __attribute__((always_inline)) {
         const double dxc = dtc.x, tc = dtc.y, yc = yvc.x, vc = yvc.y;
@@ -164,13 +157,13 @@ __device__ __forceinline__ void mtg_sweep(MtgLane<NR, NC> &L, const MtgSolveArgs
     // Two steps per trip with ping-pong sample registers: the sample of step n + 1 is
     // loaded under the arithmetic of step n and nothing is copied between registers.
     const uint32_t N = (uint32_t)a.N;
-    double2 dtA = ld(rdt, toff, 0), yvA = ld(ryv, yoff, 0);
+    double2 dtA = mtg_ld128(rdt, toff, 0), yvA = mtg_ld128(ryv, yoff, 0);
     uint32_t soff = 0;
     for (uint32_t n = 0; n + 1 < N; n += 2) {
-        const double2 dtB = ld(rdt, toff, soff + 16), yvB = ld(ryv, yoff, soff + 16);
+        const double2 dtB = mtg_ld128(rdt, toff, soff + 16), yvB = mtg_ld128(ryv, yoff, soff + 16);
         step(dtA, yvA);
         soff += 32;
-        dtA = ld(rdt, toff, soff); yvA = ld(ryv, yoff, soff);
+        dtA = mtg_ld128(rdt, toff, soff); yvA = mtg_ld128(ryv, yoff, soff);
         step(dtB, yvB);
         renorm();
     }
@@ -264,11 +257,9 @@ __device__ __forceinline__ void mtg_solve_row(const MtgSolveArgs &a, int64_t e, 
         mtg_sweep<NR, NC, false, true, NB0>(L, a, yv_base, yv_rec, yoff, dxt_base, dxt_rec, toff, &tab);
     }
 
-    const double logdet = fma((double)L.dexp, 0.69314718055994530942, log(L.dprod));
-    double ll = -0.5 * fma((double)a.N, MTG_LN_2PI, L.dot + logdet);
-    int st = MTG_ST_OK;
-    if (L.dmin_hi <= 0) { st = MTG_ST_NOTPD; ll = -INFINITY; }
-    else if (!isfinite(ll)) { st = MTG_ST_NONFINITE; ll = -INFINITY; }
+    double ll;
+    int st;
+    mtg_finish_lnl(a.N, L.dot, L.dprod, L.dexp, L.dmin_hi, &ll, &st);
     a.out[e] = ll;
     a.status[e] = st;
 }

@@ -23,8 +23,9 @@
 //    stores, so the chunk's own stores land under arithmetic, not under an s_waitcnt;
 //  * the consumer runs two chunks behind and fetches the generators of sample n + 1 while it works on sample n.
 //
-// The arithmetic is that of mtg_sweep.h, expression by expression, under `fp contract(off)`: a row comes out the same
-// to the last bit as from mtg_solve_kernel / mtg_solve_kernel_multi (tests/test_pipe_gpu.py).
+// The arithmetic of a step is that of mtg_sweep.h, expression by expression, under `fp contract(off)`; the loads and the
+// epilogue are its functions (mtg_sweep_step.h): a row comes out the same to the last bit as from mtg_solve_kernel /
+// mtg_solve_kernel_multi (tests/test_pipe_gpu.py, tests/test_sweep_golden_gpu.py).
 #ifndef MTG_SWEEP_PIPE_H
 #define MTG_SWEEP_PIPE_H
 
@@ -108,10 +109,7 @@ __device__ __forceinline__ void mtg_pipe_produce(const MtgSolveArgs &a, int64_t 
     const uint64_t dxt_left = a.t_stride ? a.dxt_bytes : (uint64_t)a.N * 16u;
     const __amdgpu_buffer_rsrc_t rdt = __builtin_amdgcn_make_buffer_rsrc(
         (void *)a.dxt, 0, (int)(dxt_left > 0xffffffffull ? 0xffffffffu : (uint32_t)dxt_left), 0x00020000);
-    auto ld = [](__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-        return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    const double t0 = ld(rdt, toff, 0).y;
+    const double t0 = mtg_ld128(rdt, toff, 0).y;
 
     struct Gen { double v[NV + 1]; };
     auto compute = [&](const double2 dtc, Gen &g) __attribute__((always_inline)) {
@@ -153,7 +151,7 @@ __device__ __forceinline__ void mtg_pipe_produce(const MtgSolveArgs &a, int64_t 
     const uint32_t N = (uint32_t)a.N, nch = (N + CH - 1) / CH;
     double2 d[TRIP];
 #pragma unroll
-    for (int s = 0; s < TRIP; ++s) d[s] = ld(rdt, toff, 16u * s);
+    for (int s = 0; s < TRIP; ++s) d[s] = mtg_ld128(rdt, toff, 16u * s);
     uint32_t soff = 16u * TRIP;   // byte offset of the next trip's first sample
     uint32_t c = 0;
     Gen g[2];
@@ -165,7 +163,7 @@ __device__ __forceinline__ void mtg_pipe_produce(const MtgSolveArgs &a, int64_t 
             for (int s = 0; s < CH; ++s) {
                 const int i = u * CH + s;                 // this sample of the trip
                 store(g[s & 1], ring + i * N2 * 64);
-                d[i] = ld(rdt, toff, soff + 16u * i);
+                d[i] = mtg_ld128(rdt, toff, soff + 16u * i);
                 compute(d[(i + 1) % TRIP], g[(s + 1) & 1]);
             }
             hand_over(g[0], d[(u * CH + CH + 1) % TRIP], d[(u * CH + CH + 2) % TRIP]);
@@ -178,7 +176,7 @@ __device__ __forceinline__ void mtg_pipe_produce(const MtgSolveArgs &a, int64_t 
     for (; c < nch; ++c) {
         double2 nx[CH];
 #pragma unroll
-        for (int s = 0; s < CH; ++s) nx[s] = ld(rdt, toff, 16u * (CH * c + s + 1));
+        for (int s = 0; s < CH; ++s) nx[s] = mtg_ld128(rdt, toff, 16u * (CH * c + s + 1));
 #pragma unroll
         for (int s = 0; s < CH; ++s) {
             store(g[s & 1], slot + s * N2 * 64);
@@ -226,9 +224,6 @@ __device__ __forceinline__ void mtg_pipe_consume(const MtgSolveArgs &a, int64_t 
     const uint64_t dxt_left = a.t_stride ? a.dxt_bytes : (uint64_t)a.N * 16u;
     const __amdgpu_buffer_rsrc_t rdt = __builtin_amdgcn_make_buffer_rsrc(
         (void *)a.dxt, 0, (int)(dxt_left > 0xffffffffull ? 0xffffffffu : (uint32_t)dxt_left), 0x00020000);
-    auto ld = [](__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
-        return __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
     auto ldt = [](__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {   // t_n alone: the second half of (dx, t)
         return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff + 8u, 0));
     };
@@ -311,7 +306,7 @@ __device__ __forceinline__ void mtg_pipe_consume(const MtgSolveArgs &a, int64_t 
     double tt[MEAN ? TRIP : 1];
 #pragma unroll
     for (int s = 0; s < TRIP; ++s) {
-        y[s] = ld(ryv, yoff, 16u * s);
+        y[s] = mtg_ld128(ryv, yoff, 16u * s);
         if constexpr (MEAN) tt[s] = ldt(rdt, toff, 16u * s);
     }
     uint32_t soff = 16u * TRIP;
@@ -332,7 +327,7 @@ __device__ __forceinline__ void mtg_pipe_consume(const MtgSolveArgs &a, int64_t 
                 double tc = 0.0;
                 if constexpr (MEAN) tc = tt[i];
                 step(y[i], tc, g[s & 1]);
-                y[i] = ld(ryv, yoff, soff + 16u * i);
+                y[i] = mtg_ld128(ryv, yoff, soff + 16u * i);
                 if constexpr (MEAN) tt[i] = ldt(rdt, toff, soff + 16u * i);
                 if (s & 1) renorm();
             }
@@ -349,7 +344,7 @@ __device__ __forceinline__ void mtg_pipe_consume(const MtgSolveArgs &a, int64_t 
 #pragma unroll 1
         for (uint32_t s = 0; s < left; ++s) {
             fetch(g[0], slot + s * N2 * 64);
-            const double2 ys = ld(ryv, yoff, 16u * (n0 + s));
+            const double2 ys = mtg_ld128(ryv, yoff, 16u * (n0 + s));
             double tc = 0.0;
             if constexpr (MEAN) tc = ldt(rdt, toff, 16u * (n0 + s));
             step(ys, tc, g[0]);
@@ -361,11 +356,9 @@ __device__ __forceinline__ void mtg_pipe_consume(const MtgSolveArgs &a, int64_t 
     }
     dot = fma(z * z, invD, dot);
 
-    const double logdet = fma((double)dexp, 0.69314718055994530942, log(dprod));
-    double ll = -0.5 * fma((double)a.N, MTG_LN_2PI, dot + logdet);
-    int st = MTG_ST_OK;
-    if (dmin_hi <= 0) { st = MTG_ST_NOTPD; ll = -INFINITY; }
-    else if (!isfinite(ll)) { st = MTG_ST_NONFINITE; ll = -INFINITY; }
+    double ll;
+    int st;
+    mtg_finish_lnl(a.N, dot, dprod, dexp, dmin_hi, &ll, &st);
     if (active) {
         a.out[e] = ll;
         a.status[e] = st;

@@ -11,7 +11,7 @@
 //            waves per 64 chunks (two keep A's columns, two the symmetric matrices Dv and Jm; see below);
 //            also the chunk's likelihood given x_in = 0 (kappa);
 //   up-sweep mtg_tp_scan.h: combinations level by level down to four elements per evaluation, each J x J
-//            operation spread over 16 lanes with the operands in LDS -- no lane holds a matrix; the
+//            operation spread over the lanes of one wave with the operands in LDS -- no lane holds a matrix; the
 //            likelihood records (kappa and the combinations' contributions) travel along;
 //   top      mtg_tpb_top_direct_kernel: those four elements applied to the state after sample 0 give lnL --
 //            no further pass over the data.  Evaluations whose terms cancel badly, or that met a pivot that

@@ -1,16 +1,15 @@
 // mtg_tp_scan.h -- the scan over the chunk elements of the big-J time-parallel path
-// (mtg_tp_big.h), with every J x J operation of a combination spread over a group of 16 lanes.
+// (mtg_tp_big.h), with every J x J operation of a combination spread over the lanes of one wave.
 //
 // A filtering element of rank J = 10 is 230 doubles; combining two of them in one lane needs
 // eight 10 x 10 products and an inverse -- ~800 doubles of temporaries, i.e. scratch memory (round 1:
-// 9.8 KB per lane, 10 ms per launch).  Here no lane ever holds a matrix: lane r of a group owns ROW r
-// of whatever is being computed (10 doubles), the operands sit in the group's LDS region and are
-// read as broadcasts (every lane of the group reads the same row of the right-hand operand), so a
-// product costs each lane J (J + J/2) issue slots and ~60 VGPRs; four groups share a wave.
+// 9.8 KB per lane, 10 ms per launch).  Here no lane ever holds a matrix: a lane owns a column pair of one
+// row of whatever is being computed, the operands sit in the wave's LDS region and are read as broadcasts
+// (namespace tpw below).
 //
 // Structure of the scan (per evaluation, C chunk elements e_0 .. e_{C-1} in global memory):
 //   up-sweep    mtg_tpb_reduce_kernel: groups of g (mtg_tp_big_gsize) consecutive elements are composed into
-//               one (g - 1 sequential combinations per lane group), level after level until four
+//               one (g - 1 sequential combinations per wave), level after level until four
 //               elements remain.  With the likelihood record (below) carried along, those four applied to
 //               the state after sample 0 give lnL (mtg_tpb_top_direct_kernel): no down-sweep, no filter pass;
 //   down-sweep  mtg_tpb_down_kernel (only for evaluations that need the filter pass): from the state after
@@ -33,8 +32,6 @@
 #include "mtg_device.h"
 #include "mtg_solve_plan.h"   // MtgTpBigPlan and the chunk / group sizes of the rank-10 path
 
-#define MTG_TPB_LANES 16    /* lanes per lane group */
-
 // up-sweep; kappa != 0: every group (the last one's total too) and the likelihood records; zero_me: an int the first
 // level's first workgroup clears (the redo counter), or NULL
 void mtg_launch_tpb_up(int J, const MtgSolveArgs &a, const MtgTpBigPlan &plan, int64_t nevals, int kappa, int *zero_me,
@@ -48,332 +45,26 @@ void mtg_launch_tpb_down(int J, const MtgSolveArgs &a, const MtgTpBigPlan &plan,
 void mtg_launch_tp_big(const MtgSolveArgs &a, int64_t nevals, hipStream_t stream);
 
 #ifdef __HIPCC__
-namespace tpg {
+// ---------------------------------------------------------------------------------------------------------------
+// One WAVE per combination.  With a lane per ROW (groups of 16 lanes, four to a wave) a combination
+// was 13 us long -- a chain of ~1100 dependent FP64 instructions per lane and 7.9 KB of LDS per group, five waves to a
+// CU -- and the up-sweep is a chain of such combinations: 0.37 ms of a 0.85 ms half-step at 32 evaluations.  Here lane
+// (r, q) of a wave owns the column PAIR (2q, 2q + 1) of row r of whatever J x J matrix is being computed (J = 10: 50
+// lanes at work, the other 14 repeat lane 49), so that a product costs a lane 2 J multiply-adds instead of J^2, the
+// elimination J steps of 4 instead of 2 J, and a wave's 8.8 KB of LDS let eighteen of them share a CU.  Operands are
+// read from LDS -- row r of the left factor (the same address for the five lanes of a row), pairs of the right factor's
+// rows (the same address for the ten lanes of a column pair).  There is one wave, so every "barrier" is the wave's own
+// LDS ordering (wsync).
+namespace tpw {
 
-// wave-level ordering of LDS traffic between the lanes of a group (they run in lock-step: one
-// wave; LDS operations of a wave complete in order)
+// wave-level ordering of LDS traffic between the lanes of a wave (they run in lock-step; LDS operations of a wave
+// complete in order)
 __device__ __forceinline__ void wsync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-
-template <int J> struct Lds {  // one lane group's region
-    static constexpr int M = J * J;
-    double A1[M], eta1[J], b1[J], C1[M], J1[M];   // running element (reduce) / state (b1 | C1, contiguous) (down)
-    double A2[M], b2[J], eta2[J], C2[M], J2[M];   // the next element, in the order of the global layout
-    double T1[M], T2[M], T3[M];
-    double v1[J], v2[J], v3[J];
-    double piv[2 * J];
-};
-
-template <int J> __device__ __forceinline__ void row(const double *X, int r, double (&x)[J])
-{
-#pragma unroll
-    for (int k = 0; k < J; ++k) x[k] = X[r * J + k];
-}
-template <int J> __device__ __forceinline__ void col(const double *X, int r, double (&x)[J])
-{
-#pragma unroll
-    for (int k = 0; k < J; ++k) x[k] = X[k * J + r];
-}
-template <int J> __device__ __forceinline__ void put(double *X, int r, const double (&x)[J])
-{
-#pragma unroll
-    for (int k = 0; k < J; ++k) X[r * J + k] = x[k];
-}
-// o += x Y (x a row vector, Y in LDS, its rows read by every lane of the group)
-template <int J> __device__ __forceinline__ void mm(const double (&x)[J], const double *Y, double (&o)[J])
-{
-#pragma unroll
-    for (int k = 0; k < J; ++k) {
-#pragma unroll
-        for (int j = 0; j < J; ++j) o[j] = fma(x[k], Y[k * J + j], o[j]);
-    }
-}
-// o += x Y^T
-template <int J> __device__ __forceinline__ void mmT(const double (&x)[J], const double *Y, double (&o)[J])
-{
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        double s = o[j];
-#pragma unroll
-        for (int k = 0; k < J; ++k) s = fma(x[k], Y[j * J + k], s);
-        o[j] = s;
-    }
-}
-template <int J> __device__ __forceinline__ double dot(const double (&x)[J], const double *v)
-{
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < J; ++k) s = fma(x[k], v[k], s);
-    return s;
-}
-
-// Lanes J .. 15 of a group have no row of their own: they are given r = J - 1 and duplicate that row's
-// work, identical stores included (predicating the stores instead makes the compiler sink the arithmetic
-// into the predicated block while the LDS reads stay where they are -- every operand then lives in
-// scratch memory in between).
-//
-// Row r of (I + X Y)^-1 by Gauss-Jordan without pivoting (I + C J is similar to a symmetric positive
-// definite matrix); the pivot row travels through L.piv.  Returns the row of the inverse in gi and the
-// reciprocal of the product of the pivots (1 / det) as dm * 2^de.
-template <int J>
-__device__ __forceinline__ void inv_ipxy(Lds<J> &L, const double *X, const double *Y, int r, double (&gi)[J],
-                                         double &dm, int &de)
-{
-    double g[J], x[J];
-    row<J>(X, r, x);
-#pragma unroll
-    for (int j = 0; j < J; ++j) { g[j] = j == r ? 1.0 : 0.0; gi[j] = g[j]; }
-    mm<J>(x, Y, g);
-    dm = 1.0; de = 0;
-#pragma unroll
-    for (int p = 0; p < J; ++p) {
-        if (r == p) {
-            const double ip = 1.0 / g[p];
-#pragma unroll
-            for (int j = 0; j < J; ++j) { g[j] *= ip; gi[j] *= ip; }
-#pragma unroll
-            for (int j = 0; j < J; ++j) { L.piv[j] = g[j]; L.piv[J + j] = gi[j]; }
-            L.v3[0] = ip;
-        }
-        wsync();
-        const double f = r == p ? 0.0 : g[p];
-        {
-            // (single pivots of I + X Y may be negative -- it is not symmetric -- only their product is a sign test)
-            const double pr = dm * L.v3[0];
-            dm = __builtin_amdgcn_frexp_mant(pr);
-            de += __builtin_amdgcn_frexp_exp(pr);
-        }
-#pragma unroll
-        for (int j = 0; j < J; ++j) { g[j] = fma(-f, L.piv[j], g[j]); gi[j] = fma(-f, L.piv[J + j], gi[j]); }
-        wsync();
-    }
-}
-
-// running element (A1, b1, eta1, C1, J1) <- (running) o (A2, b2, eta2, C2, J2), the running one earlier in
-// time:  G = I + C1 J2;  A = A2 G^-1 A1;  b = A2 G^-1 (b1 + C1 eta2) + b2;  C = A2 G^-1 C1 A2^T + C2;
-//        eta = A1^T G^-T (eta2 - J2 b1) + eta1;  J = A1^T G^-T J2 A1 + J1,
-// with G^-T J2 = J2 G^-1 (push-through identity).
-// KAPPA: kap = (lin, quad) of the likelihood record's update and 1 / det G = dm 2^de (same on every lane of
-// the group; the caller takes the logarithm of the product of a whole group's determinants once).
-template <int J, bool KAPPA = false>
-__device__ __forceinline__ void combine(Lds<J> &L, int r, double (&kap)[2], double &dm, int &de)
-{
-    double gi[J];
-    inv_ipxy<J>(L, L.C1, L.J2, r, gi, dm, de);
-    // w = b1 + C1 eta2 -> v1 ; t = eta2 - J2 b1 -> v2 ; Gi -> T1
-    {
-        double x[J];
-        row<J>(L.C1, r, x);
-        const double w = L.b1[r] + dot<J>(x, L.eta2);
-        row<J>(L.J2, r, x);
-        const double t = L.eta2[r] - dot<J>(x, L.b1);
-        L.v1[r] = w; L.v2[r] = t;
-        put<J>(L.T1, r, gi);
-    }
-    wsync();
-    // XA = Gi A1 -> T2 ; XC = Gi C1 -> T3 ; xb = Gi w -> v3
-    {
-        double xa[J], xc[J];
-#pragma unroll
-        for (int j = 0; j < J; ++j) { xa[j] = 0.0; xc[j] = 0.0; }
-        mm<J>(gi, L.A1, xa);
-        mm<J>(gi, L.C1, xc);
-        const double xb = dot<J>(gi, L.v1);
-        put<J>(L.T2, r, xa);
-        put<J>(L.T3, r, xc);
-        L.v3[r] = xb;
-        if (KAPPA) {  // this row's share of lin and of quad (t in v2; piv is free after the inverse)
-            const double tr = L.v2[r];
-            L.piv[r] = 0.5 * L.b1[r] * (L.eta2[r] + tr);
-            L.piv[J + r] = 0.5 * tr * dot<J>(xc, L.v2);
-        }
-    }
-    // yeta = G^-T t (column r of Gi; stays in this lane until A1's columns are read);
-    // YJ = G^-T J2 = J2 Gi ; Z = YJ A1
-    double yeta, z[J];
-    {
-        double x[J], yj[J];
-        col<J>(L.T1, r, x);
-        yeta = dot<J>(x, L.v2);
-        row<J>(L.J2, r, x);
-#pragma unroll
-        for (int j = 0; j < J; ++j) { yj[j] = 0.0; z[j] = 0.0; }
-        mm<J>(x, L.T1, yj);
-        mm<J>(yj, L.A1, z);
-    }
-    wsync();                       // everybody has read Gi (T1) and v2
-    if (KAPPA) {
-        double lin = 0.0, quad = 0.0;
-#pragma unroll
-        for (int k = 0; k < J; ++k) { lin += L.piv[k]; quad += L.piv[J + k]; }
-        kap[0] = lin; kap[1] = quad;
-    }
-    put<J>(L.T1, r, z);       // Z -> T1
-    L.v2[r] = yeta;
-    wsync();
-    // new information part: eta = eta1 + A1^T yeta ; J = J1 + A1^T Z   (column r of A1)
-    double eta_new, j_new[J];
-    {
-        double a1c[J];
-        col<J>(L.A1, r, a1c);
-        eta_new = L.eta1[r] + dot<J>(a1c, L.v2);
-        row<J>(L.J1, r, j_new);
-        mm<J>(a1c, L.T1, j_new);
-    }
-    // new state part: A = A2 XA ; Y = A2 XC ; C = C2 + Y A2^T ; b = b2 + A2 xb
-    double a_new[J], c_new[J], b_new;
-    {
-        double a2[J], y[J];
-        row<J>(L.A2, r, a2);
-#pragma unroll
-        for (int j = 0; j < J; ++j) { a_new[j] = 0.0; y[j] = 0.0; }
-        mm<J>(a2, L.T2, a_new);
-        mm<J>(a2, L.T3, y);
-        row<J>(L.C2, r, c_new);
-        mmT<J>(y, L.A2, c_new);
-        b_new = L.b2[r] + dot<J>(a2, L.v3);
-    }
-    wsync();                       // all reads of the old running element are done
-    put<J>(L.A1, r, a_new);
-    put<J>(L.C1, r, c_new);
-    put<J>(L.J1, r, j_new);
-    L.b1[r] = b_new; L.eta1[r] = eta_new;
-    wsync();
-}
-
-// state (m in b1, P in C1) <- element (A2, b2, eta2, C2, J2) applied to it:
-//   G = I + P J2;  m' = A2 G^-1 (m + P eta2) + b2;  P' = A2 G^-1 P A2^T + C2
-// CORR: also returns the element's chunk likelihood given the state it is applied to, relative to
-// the chunk likelihood given x_in = 0 (kappa, which the composition pass accumulates):
-//   ln p(y_chunk | m, P) - kappa = -1/2 ln det G + eta^T m - 1/2 m^T J m + 1/2 t^T (G^-1 P) t,  t = eta - J m
-// (p(y_chunk | x_in) = exp(kappa + eta^T x_in - 1/2 x_in^T J x_in), integrated against N(m, P)).
-// NaN when det G is not positive.  UPDATE = false: only that number, the state is left alone.
-template <int J, bool CORR = false, bool UPDATE = true> __device__ __forceinline__ double apply(Lds<J> &L, int r)
-{
-    double gi[J], dm;
-    int de;
-    inv_ipxy<J>(L, L.C1, L.J2, r, gi, dm, de);
-    double t = 0.0, mr = 0.0, er = 0.0;
-    {
-        double x[J];
-        row<J>(L.C1, r, x);
-        const double w = L.b1[r] + dot<J>(x, L.eta2);
-        L.v1[r] = w;
-        if (CORR) {
-            row<J>(L.J2, r, x);
-            mr = L.b1[r]; er = L.eta2[r];
-            t = er - dot<J>(x, L.b1);
-            L.v2[r] = t;
-        }
-    }
-    wsync();
-    double corr = 0.0;
-    {
-        double xc[J];
-#pragma unroll
-        for (int j = 0; j < J; ++j) xc[j] = 0.0;
-        mm<J>(gi, L.C1, xc);
-        const double xb = dot<J>(gi, L.v1);
-        put<J>(L.T3, r, xc);
-        L.v3[r] = xb;
-        if (CORR) {
-            const double xt = dot<J>(xc, L.v2);
-            // this row's share of eta^T m - 1/2 m^T J m + 1/2 t^T X t   (J m = eta - t)
-            L.piv[r] = fma(er, mr, 0.5 * fma(t, xt, -mr * (er - t)));
-            wsync();
-            double sum = 0.0;
-#pragma unroll
-            for (int k = 0; k < J; ++k) sum += L.piv[k];
-            // 1 / det G = dm 2^de > 0, or some pivot was not positive
-            corr = dm > 0.0 ? sum + 0.5 * (log(dm) + (double)de * 0.69314718055994530942) : __builtin_nan("");
-        }
-    }
-    if (!UPDATE) { wsync(); return corr; }
-    wsync();
-    double c_new[J], b_new;
-    {
-        double a2[J], y[J];
-        row<J>(L.A2, r, a2);
-#pragma unroll
-        for (int j = 0; j < J; ++j) y[j] = 0.0;
-        mm<J>(a2, L.T3, y);
-        row<J>(L.C2, r, c_new);
-        mmT<J>(y, L.A2, c_new);
-        b_new = L.b2[r] + dot<J>(a2, L.v3);
-    }
-    wsync();
-    put<J>(L.C1, r, c_new);
-    L.b1[r] = b_new;
-    wsync();
-    return corr;
-}
-
-// copy n doubles global <-> LDS by the 16 lanes of a group
-__device__ __forceinline__ void gcopy(double *dst, const double *src, int n, int l16)
-{
-    for (int i = l16; i < n; i += MTG_TPB_LANES) dst[i] = src[i];
-}
-
-// The next element travels global memory -> registers (issued before the current combination, whose
-// arithmetic hides the latency) -> LDS (after it): MTG_TPB_ELEM(J) / 16 doubles per lane.
-template <int J> struct Pre { double v[(MTG_TPB_ELEM(J) + MTG_TPB_LANES - 1) / MTG_TPB_LANES]; };
-template <int J> __device__ __forceinline__ void fetch(Pre<J> &p, const double *e, int l16)
-{
-    constexpr int N = MTG_TPB_ELEM(J), Q = (N + MTG_TPB_LANES - 1) / MTG_TPB_LANES;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int i = l16 + MTG_TPB_LANES * q;
-        p.v[q] = e[i < N ? i : N - 1];
-    }
-}
-template <int J> __device__ __forceinline__ void put_second(Lds<J> &L, const Pre<J> &p, int l16)
-{
-    constexpr int N = MTG_TPB_ELEM(J), Q = (N + MTG_TPB_LANES - 1) / MTG_TPB_LANES;
-    double *dst = L.A2;  // A2 | b2 | eta2 | C2 | J2 are contiguous and in the global order
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int i = l16 + MTG_TPB_LANES * q;
-        if (i < N) dst[i] = p.v[q];
-    }
-}
-template <int J> __device__ __forceinline__ void load_first(Lds<J> &L, const double *e, int l16)
-{
-    constexpr int M = J * J;
-    gcopy(L.A1, e, M, l16);
-    gcopy(L.b1, e + M, J, l16);
-    gcopy(L.eta1, e + M + J, J, l16);
-    gcopy(L.C1, e + M + 2 * J, M, l16);
-    gcopy(L.J1, e + 2 * M + 2 * J, M, l16);
-}
-template <int J> __device__ __forceinline__ void store_first(const Lds<J> &L, double *e, int l16)
-{
-    constexpr int M = J * J;
-    gcopy(e, L.A1, M, l16);
-    gcopy(e + M, L.b1, J, l16);
-    gcopy(e + M + J, L.eta1, J, l16);
-    gcopy(e + M + 2 * J, L.C1, M, l16);
-    gcopy(e + 2 * M + 2 * J, L.J1, M, l16);
-}
-
-}  // namespace tpg
-
-// ---------------------------------------------------------------------------------------------------------------
-// One WAVE per combination (round 3).  The 16-lane groups above leave a combination 13 us long -- a chain of ~1100
-// dependent FP64 instructions per lane and 7.9 KB of LDS per group, four groups to a wave, five waves to a CU -- and
-// the up-sweep is a chain of such combinations: 0.37 ms of a 0.85 ms half-step at 32 evaluations.  Here lane (r, q) of
-// a wave owns the column PAIR (2q, 2q + 1) of row r of whatever J x J matrix is being computed (J = 10: 50 lanes at
-// work, the other 14 repeat lane 49), so that a product costs a lane 2 J multiply-adds instead of J^2, the elimination
-// J steps of 4 instead of 2 J, and a wave's 8.8 KB of LDS let eighteen of them share a CU.  Operands are read from
-// LDS as before -- row r of the left factor (the same address for the five lanes of a row), pairs of the right factor's
-// rows (the same address for the ten lanes of a column pair).  There is one wave, so every "barrier" is the wave's own
-// LDS ordering (tpg::wsync).
-namespace tpw {
-
-using tpg::wsync;
 
 template <int J> struct alignas(16) Lds {
     static_assert(J % 2 == 0, "column pairs");
@@ -510,8 +201,12 @@ __device__ __forceinline__ void inv_ipxy(Lds<J> &L, const double (&xr)[J], const
     }
 }
 
-// running element (A1, b1, eta1, C1, J1) <- (running) o (A2, b2, eta2, C2, J2), the running one earlier in time
-// (the formulas of tpg::combine; J2 G^-1 A1 is taken as J2 (G^-1 A1), so that G^-T J2 is never formed).
+// running element (A1, b1, eta1, C1, J1) <- (running) o (A2, b2, eta2, C2, J2), the running one earlier in
+// time:  G = I + C1 J2;  A = A2 G^-1 A1;  b = A2 G^-1 (b1 + C1 eta2) + b2;  C = A2 G^-1 C1 A2^T + C2;
+//        eta = A1^T G^-T (eta2 - J2 b1) + eta1;  J = A1^T G^-T J2 A1 + J1,
+// with G^-T J2 = J2 G^-1 (push-through identity); J2 G^-1 A1 is taken as J2 (G^-1 A1), so that G^-T J2 is never formed.
+// KAPPA: kap = (lin, quad) of the likelihood record's update and 1 / det G = dm 2^de (same on every lane of the
+// wave; the caller takes the logarithm of the product of a whole group's determinants once).
 template <int J, bool KAPPA = false>
 __device__ __forceinline__ void combine(Lds<J> &L, const Lane w, double (&kap)[2], double &dm, int &de)
 {
@@ -590,8 +285,13 @@ __device__ __forceinline__ void combine(Lds<J> &L, const Lane w, double (&kap)[2
     wsync();
 }
 
-// state (m in b1, P in C1) <- element (A2, b2, eta2, C2, J2) applied to it (tpg::apply): CORR also returns the element's
-// chunk likelihood given that state relative to kappa; UPDATE = false: only that number.
+// state (m in b1, P in C1) <- element (A2, b2, eta2, C2, J2) applied to it:
+//   G = I + P J2;  m' = A2 G^-1 (m + P eta2) + b2;  P' = A2 G^-1 P A2^T + C2
+// CORR: also returns the element's chunk likelihood given the state it is applied to, relative to
+// the chunk likelihood given x_in = 0 (kappa, which the composition pass accumulates):
+//   ln p(y_chunk | m, P) - kappa = -1/2 ln det G + eta^T m - 1/2 m^T J m + 1/2 t^T (G^-1 P) t,  t = eta - J m
+// (p(y_chunk | x_in) = exp(kappa + eta^T x_in - 1/2 x_in^T J x_in), integrated against N(m, P)).
+// NaN when det G is not positive.  UPDATE = false: only that number, the state is left alone.
 template <int J, bool CORR = false, bool UPDATE = true> __device__ __forceinline__ double apply(Lds<J> &L, const Lane w)
 {
     const int r = w.r, c0 = w.c0;

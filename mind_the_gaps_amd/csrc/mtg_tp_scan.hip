@@ -133,7 +133,7 @@ __device__ __forceinline__ bool tpb_head_state(const MtgSolveArgs &a, int64_t ev
 }
 
 // lnL of an evaluation from its n top-level elements and their likelihood records: the elements applied one after
-// the other to the state after sample 0, each leaving its correction (tpg::apply) -- the samples were read once,
+// the other to the state after sample 0, each leaving its correction (tpw::apply) -- the samples were read once,
 // by the composition pass.  The records are computed under a wrong hypothesis (x_in = 0), so the terms can be far
 // larger than the result and cancel; an evaluation whose terms exceed 1e3 x the result, with anything not positive or
 // not finite on the way, or with a complex term whose power spectrum can go negative (b d > a c: the matrix need not

@@ -89,7 +89,7 @@ def rows():
     share_s = share.get("whole_test_s_with_observed_split", share["whole_test_s"])
     table = [
         ("a1–a8 log-probability (GP set-up, prior, coefficients, factorisation + solve)",
-         "`csrc/mtg_sweep.h`, `mtg_kernels.hip`, `mtg_kernels_multi.hip`, `mtg_sweep_pipe.h`, `mtg_kernels_pipe.hip`, `mtg_prepare.h`, "
+         "`csrc/mtg_sweep_step.h`, `mtg_sweep.h`, `mtg_kernels.hip`, `mtg_kernels_multi.hip`, `mtg_sweep_pipe.h`, `mtg_kernels_pipe.hip`, `mtg_prepare.h`, "
          "`mtg_sort.hip`, `mtg_timeparallel*`, `mtg_tp_scan.*`, `mtg_tp_big*`, `mtg_capi.hip`; `gp.py`, `gpmodelling.py`",
          "`test_hip_parity`, `test_golden_gpu` (180 dense/mpmath vectors × 3 dispatch modes), `test_box_golden`, `test_fuzz_gpu`, "
          "`test_edge_cases_gpu`, `test_timeparallel_gpu`, `test_tp_big_gpu`, `test_window_gpu`, `test_sort_gpu`, `test_device_math_gpu`, "

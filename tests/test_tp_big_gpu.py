@@ -1,5 +1,5 @@
 """GPU parity of the rank-10 time-parallel path (csrc/mtg_tp_big.h, mtg_tp_scan.h): composition by
-two waves per 64 chunks, scan spread over 16-lane groups, likelihood with and without the filter
+two waves per 64 chunks, scan with one wave per combination, likelihood with and without the filter
 pass, every chunk count the dispatch can pick, the large-phase reduction, the fall-back of badly
 cancelling evaluations -- against the oracle (celerite's algorithm on the CPU) and against the serial
 sweep of the same library.  BASELINE configs[4] (N = 200 000, five SHO terms, 512 walkers) at its full
