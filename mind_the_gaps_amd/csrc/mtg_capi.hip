@@ -1,6 +1,7 @@
 // mtg_capi.hip -- host side of the C-ABI declared in include/mtg.h.
 // One context = one MI355X + resident light curves + model + workspaces.
 #include "mtg_device.h"
+#include "mtg_sim_plan.h"
 #include "mtg_solve_plan.h"
 #include "mtg_tp_scan.h"
 #include "mtg_trace.h"
@@ -31,8 +32,70 @@ thread_local std::string g_create_error;
 
 // hipFFT plans are made from helper threads too (mtg_fft_warmup, mtg_simulate_plan) while another thread may be making
 // or destroying one for a convergence check: plan creation and destruction go through one process-wide lock
-// (executions do not).
+// (executions do not).  FftPlan below is the only code that takes it.
 std::mutex g_fft_plan_mu;
+
+// what a 1-D hipFFT plan is made for; idist = odist = 0: hipfftPlan1d, otherwise hipfftPlanMany over contiguous transforms
+// that lie idist / odist elements apart
+struct FftKey {
+    hipfftType type = HIPFFT_Z2Z;
+    int64_t len = 0;
+    int batch = 0;
+    int64_t idist = 0, odist = 0;
+    bool operator==(const FftKey &o) const { return type == o.type && len == o.len && batch == o.batch && idist == o.idist && odist == o.odist; }
+};
+
+struct FftPlan {  // owning hipFFT plan and the key it was made for; every cached and throw-away plan of the library is one
+    FftPlan() = default;
+    FftPlan(FftPlan &&o) noexcept : h(o.h), made(o.made), key(o.key) { o.made = false; }
+    FftPlan &operator=(FftPlan &&o) noexcept
+    {
+        if (this != &o) { reset(); h = o.h; made = o.made; key = o.key; o.made = false; }
+        return *this;
+    }
+    ~FftPlan() { reset(); }
+    bool holds(const FftKey &k) const { return made && key == k; }
+    const FftKey *held() const { return made ? &key : nullptr; }
+    // the plan for `k`: the one held if it was made for k, else made now in its place; 0 when hipFFT refuses (nothing is
+    // held then).  The caller sets the stream and executes.
+    hipfftHandle get(const FftKey &k)
+    {
+        if (holds(k)) return h;
+        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
+        drop();
+        int len = (int)k.len;
+        const hipfftResult r = k.idist ? hipfftPlanMany(&h, 1, &len, nullptr, 1, (int)k.idist, nullptr, 1, (int)k.odist, k.type, k.batch)
+                                       : hipfftPlan1d(&h, len, k.type, k.batch);
+        if (r != HIPFFT_SUCCESS) return 0;
+        made = true;
+        key = k;
+        return h;
+    }
+    void reset()
+    {
+        if (!made) return;
+        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
+        drop();
+    }
+
+private:
+    void drop() { if (made) (void)hipfftDestroy(h); made = false; }   // under g_fft_plan_mu
+    hipfftHandle h = 0;
+    bool made = false;
+    FftKey key;
+};
+
+// A forward / inverse pair (convergence check, E13 adjustment) is two plans, both made or neither: 0, or which creation
+// failed (1 forward, 2 inverse) with both plans empty.
+int fft_pair_get(FftPlan &fwd, const FftKey &kf, FftPlan &inv, const FftKey &ki, hipfftHandle *hf, hipfftHandle *hi)
+{
+    *hf = fwd.get(kf);
+    *hi = *hf ? inv.get(ki) : 0;
+    if (*hf && *hi) return 0;
+    fwd.reset();
+    inv.reset();
+    return *hf ? 2 : 1;
+}
 
 struct DevBuf {  // owning device allocation; locals free themselves on every return path
     void *p = nullptr;
@@ -56,6 +119,7 @@ struct DevBuf {  // owning device allocation; locals free themselves on every re
         if (p) (void)hipFree(p);
         p = nullptr; cap = 0;
     }
+    template <class T> hipError_t reserve_n(int64_t n) { return reserve((size_t)n * sizeof(T)); }   // room for n elements
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
@@ -127,7 +191,7 @@ struct mtg_ctx {
     // pairs, the least recently used one making room: the tutorial's loop checks the null and the alternative model's
     // chains in turn (two shapes), and a single slot was rebuilt at every check -- 9 ms each, a third of that loop
     // (scripts/tutorial_loop_probe.py)
-    struct AcfPlans { hipfftHandle fwd = 0, inv = 0; bool have = false; int64_t n2 = 0, S = 0, P = 0; uint64_t used = 0; } acf_slots[4];
+    struct AcfPlans { FftPlan fwd, inv; uint64_t used = 0; } acf_slots[MTG_ACF_SLOTS];   // (slot choice: mtg_sim_plan.h)
     uint64_t acf_clock = 0;
     DevBuf acf_chain, acf_x, acf_f, acf_g, acf_r, acf_ss, acf_tmp;
     int64_t acf_plans_built = 0;   // plan pairs made so far (mtg_chain_autocorr_plans_built: a cached shape must not add to it)
@@ -136,9 +200,10 @@ struct mtg_ctx {
     // of BASELINE configs[3] takes 0.9 s to build, as long as the 2000 simulations it then runs) and its buffers.
     // mtg_simulate_plan may build it from a helper thread while the context is busy elsewhere: sim_mu.
     std::mutex sim_mu;
-    // C2R plans of the simulator: [0] the bulk plan (sim_batch_for's batch for the length), [1] a short call's (fewer
-    // series than that batch: a single light curve runs ONE transform); each remade when its (length, batch) changes
-    struct SimPlan { hipfftHandle h = 0; bool have = false; int64_t nfft = 0; int batch = 0; } sim_plans[2];
+    // C2R plans of the simulator: [0] the bulk plan (the batch of a full call at the length), [1] a short call's (fewer
+    // series than that batch: a single light curve runs ONE transform); each remade when its (length, batch) changes.
+    // Which slot a call takes: MtgSimLayout::slot (mtg_sim_plan.h)
+    FftPlan sim_plans[2];
     DevBuf sim_spec, sim_series;
     // ... and the hand-made chirp-z transform for lengths hipFFT would take through a Bluestein plan (0.9 s to build
     // against 15 ms for the power-of-two plans this needs; mtg_simulate.hip): chirp w [nfft], transform of the wrapped
@@ -148,7 +213,7 @@ struct mtg_ctx {
         bool pairs_on = true;   // two series per complex transform (mtg_set_simulate_pairs)
         int64_t nfft = 0, m = 0;
         DevBuf chirp, bhat, work;
-        struct { hipfftHandle h = 0; bool have = false; int64_t m = 0; int pairs = 0; } plans[2];
+        FftPlan plans[2];
     } czt;
     // draws handed in by the caller for the NEXT mtg_simulate_tk95 (mtg_set_simulate_draws): standard normals
     // [S][2][nfft / 2 + 1] and segment starts [S]
@@ -160,9 +225,14 @@ struct mtg_ctx {
     struct E13 {
         int kind = 0, max_iter = 400;
         DevBuf seg, x, fresh, values, adj, keys, amp, spec, idx, order, order_tmp, segment, segment_out, flags, stdv, temp;
-        hipfftHandle fwd = 0, inv = 0;
-        bool have = false;
-        int64_t n = 0, batch = 0;
+        FftPlan fwd, inv;   // D2Z / Z2D over [batch][n], remade together when n or the batch changes
+        // the scratch of one chunk, all of it (what the simulator's epilogue weighs and releases; not `given`)
+        template <class F> void each_scratch(F f)
+        {
+            for (DevBuf *b : {&seg, &x, &fresh, &values, &adj, &keys, &amp, &spec, &idx, &order, &order_tmp, &segment, &segment_out,
+                              &flags, &stdv, &temp})
+                f(*b);
+        }
         int64_t not_converged = 0;
         int iterations = 0;
         DevBuf given;            // caller's draws for the next simulation (mtg_set_simulate_pdf_draws): [S][n]
@@ -206,6 +276,13 @@ struct mtg_ctx {
 
     // mtg_set_simulate_transform: 0 = by grid length (default), 1 = hipFFT's own plan, 2 = chirp-z
     int sim_transform = 0;
+
+    // every hipFFT plan of the context (mtg_destroy: before the stream they run on goes)
+    void reset_plans()
+    {
+        for (AcfPlans &sl : acf_slots) { sl.fwd.reset(); sl.inv.reset(); }
+        for (FftPlan *pl : {&sim_plans[0], &sim_plans[1], &czt.plans[0], &czt.plans[1], &e13.fwd, &e13.inv}) pl->reset();
+    }
 };
 
 // Two contexts whose pipelined sweeps go out in ONE launch (mtg_kernels_pipe_pair.hip): the two models of the Protassov
@@ -875,32 +952,11 @@ MTG_API void mtg_destroy(mtg_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->foreign_pending) (void)hipEventSynchronize(ctx->foreign_done);
-    DevBuf *bufs[] = {&ctx->sort_keys, &ctx->sort_keys_out, &ctx->sort_order, &ctx->sort_tmp, &ctx->dxt, &ctx->yv, &ctx->t_tmp, &ctx->y_tmp, &ctx->dy_tmp, &ctx->off_tmp, &ctx->dxmax, &ctx->coef, &ctx->lists,
-                      &ctx->counts, &ctx->tp_ws, &ctx->sig, &ctx->tables, &ctx->theta, &ctx->lc, &ctx->out, &ctx->status,
-                      &ctx->ens_coords, &ctx->ens_lnp, &ctx->ens_perm, &ctx->ens_q, &ctx->ens_factor,
-                      &ctx->ens_new, &ctx->ens_st, &ctx->ens_lc_full, &ctx->ens_lc_half, &ctx->ens_lc_spec, &ctx->ens_perm_all, &ctx->ens_naccept,
-                      &ctx->ens_best_lnp, &ctx->ens_best_coords, &ctx->ens_notpd, &ctx->ens_chain,
-                      &ctx->ens_lnp_chain};
-    for (DevBuf *b : bufs) b->release();
+    // In this order: the RCCL / host exchange, then the hipFFT plans -- reset here, by hand, because they must go before
+    // the stream they were set on, and the stream is destroyed below, before the members are.  The device buffers need
+    // no list: ~DevBuf frees each with `delete ctx`.
     shard_release(ctx);
-    {
-        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-        for (auto &sl : ctx->acf_slots)
-            if (sl.have) { (void)hipfftDestroy(sl.fwd); (void)hipfftDestroy(sl.inv); }
-        for (auto &sp : ctx->sim_plans)
-            if (sp.have) (void)hipfftDestroy(sp.h);
-        for (auto &sp : ctx->czt.plans)
-            if (sp.have) (void)hipfftDestroy(sp.h);
-        if (ctx->e13.have) { (void)hipfftDestroy(ctx->e13.fwd); (void)hipfftDestroy(ctx->e13.inv); ctx->e13.have = false; }
-    }
-    for (DevBuf *b : {&ctx->kraft.bkg, &ctx->kraft.err, &ctx->kraft.med, &ctx->kraft.half}) b->release();
-    for (DevBuf *b : {&ctx->e13.seg, &ctx->e13.x, &ctx->e13.fresh, &ctx->e13.values, &ctx->e13.adj, &ctx->e13.keys, &ctx->e13.amp,
-                      &ctx->e13.spec, &ctx->e13.idx, &ctx->e13.order, &ctx->e13.order_tmp, &ctx->e13.segment, &ctx->e13.segment_out, &ctx->e13.flags, &ctx->e13.stdv, &ctx->e13.temp,
-                      &ctx->e13.given})
-        b->release();
-    ctx->sim_spec.release();
-    ctx->sim_series.release();
-    for (DevBuf *b : {&ctx->acf_chain, &ctx->acf_x, &ctx->acf_f, &ctx->acf_g, &ctx->acf_r, &ctx->acf_ss, &ctx->acf_tmp}) b->release();
+    ctx->reset_plans();
     for (hipEvent_t e : ctx->prof_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->shard_ev) (void)hipEventDestroy(e);
     if (ctx->foreign_done) (void)hipEventDestroy(ctx->foreign_done);
@@ -1755,11 +1811,8 @@ MTG_API int mtg_fft_warmup(mtg_ctx *ctx)
     if (ctx && hipSetDevice(ctx->device) != hipSuccess) return MTG_E_HIP;
     // hipFFT needs ~1.4 s the first time a plan is made in a process (rocFFT loads its kernels): callers that will
     // need mtg_chain_autocorr or mtg_simulate_tk95 later can pay that early, from another thread
-    std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-    hipfftHandle plan = 0;
-    if (hipfftPlan1d(&plan, 64, HIPFFT_D2Z, 1) != HIPFFT_SUCCESS) return MTG_E_HIP;
-    (void)hipfftDestroy(plan);
-    return MTG_OK;
+    FftPlan plan;
+    return plan.get({HIPFFT_D2Z, 64, 1}) ? MTG_OK : MTG_E_HIP;
 }
 
 MTG_API int mtg_chain_autocorr(mtg_ctx *ctx, int64_t n_t, int64_t E, int W, int P, const double *chain, double *rho)
@@ -1787,32 +1840,26 @@ MTG_API int mtg_chain_autocorr(mtg_ctx *ctx, int64_t n_t, int64_t E, int W, int 
     mtg_launch_acf_center(n_t, n2, S, d_chain.as<double>(), d_x.as<double>(), d_ss.as<double>(), ctx->acf_tmp.as<double>(), s);
     mtg_launch_acf_transpose(n2, S, d_x.as<double>(), d_chain.as<double>(), s);
     // contiguous batched transforms (stock kernels: no run-time compilation inside rocFFT)
-    mtg_ctx::AcfPlans *slot = nullptr;
-    for (auto &sl : ctx->acf_slots)
-        if (sl.have && sl.n2 == n2 && sl.S == S && sl.P == EP) slot = &sl;
-    if (!slot) {
-        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-        slot = &ctx->acf_slots[0];
-        for (auto &sl : ctx->acf_slots)  // an empty slot, else the least recently used
-            if (!sl.have || (slot->have && sl.used < slot->used)) slot = &sl;
-        if (slot->have) { (void)hipfftDestroy(slot->fwd); (void)hipfftDestroy(slot->inv); slot->have = false; }
-        int len = (int)n2;
-        if (hipfftPlanMany(&slot->fwd, 1, &len, nullptr, 1, (int)n2, nullptr, 1, (int)nk, HIPFFT_D2Z, (int)S) != HIPFFT_SUCCESS)
-            return fail(ctx, MTG_E_HIP, "mtg_chain_autocorr: hipfftPlanMany (forward) failed");
-        if (hipfftPlanMany(&slot->inv, 1, &len, nullptr, 1, (int)nk, nullptr, 1, (int)n2, HIPFFT_Z2D, (int)EP) != HIPFFT_SUCCESS) {
-            (void)hipfftDestroy(slot->fwd);
-            return fail(ctx, MTG_E_HIP, "mtg_chain_autocorr: hipfftPlanMany (inverse) failed");
-        }
-        slot->have = true; slot->n2 = n2; slot->S = S; slot->P = EP;
+    MtgAcfSlot held[MTG_ACF_SLOTS];
+    for (int i = 0; i < MTG_ACF_SLOTS; ++i) {
+        const FftKey *kf = ctx->acf_slots[i].fwd.held(), *ki = ctx->acf_slots[i].inv.held();
+        held[i] = kf && ki ? MtgAcfSlot{true, kf->len, kf->batch, ki->batch, ctx->acf_slots[i].used} : MtgAcfSlot{};
+    }
+    bool hit = false;
+    mtg_ctx::AcfPlans &slot = ctx->acf_slots[mtg_acf_slot_choose(held, n2, S, EP, &hit)];
+    hipfftHandle fwd = 0, inv = 0;
+    const int bad = fft_pair_get(slot.fwd, {HIPFFT_D2Z, n2, (int)S, n2, nk}, slot.inv, {HIPFFT_Z2D, n2, (int)EP, nk, n2}, &fwd, &inv);
+    if (bad) return fail(ctx, MTG_E_HIP, "mtg_chain_autocorr: hipfftPlanMany (%s) failed", bad == 1 ? "forward" : "inverse");
+    if (!hit) {   // a pair made now: counted, and bound to the context's stream once
         ctx->acf_plans_built += 1;
-        if (hipfftSetStream(slot->fwd, s) != HIPFFT_SUCCESS || hipfftSetStream(slot->inv, s) != HIPFFT_SUCCESS)
+        if (hipfftSetStream(fwd, s) != HIPFFT_SUCCESS || hipfftSetStream(inv, s) != HIPFFT_SUCCESS)
             return fail(ctx, MTG_E_HIP, "mtg_chain_autocorr: hipfftSetStream failed");
     }
-    slot->used = ++ctx->acf_clock;
-    if (hipfftExecD2Z(slot->fwd, d_chain.as<double>(), (hipfftDoubleComplex *)d_f.p) != HIPFFT_SUCCESS)
+    slot.used = ++ctx->acf_clock;
+    if (hipfftExecD2Z(fwd, d_chain.as<double>(), (hipfftDoubleComplex *)d_f.p) != HIPFFT_SUCCESS)
         return fail(ctx, MTG_E_HIP, "mtg_chain_autocorr: hipfftExecD2Z failed");
     mtg_launch_acf_power(nk, E, W, P, d_f.as<double2>(), d_ss.as<double>(), d_g.as<double2>(), s);
-    if (hipfftExecZ2D(slot->inv, (hipfftDoubleComplex *)d_g.p, d_r.as<double>()) != HIPFFT_SUCCESS)
+    if (hipfftExecZ2D(inv, (hipfftDoubleComplex *)d_g.p, d_r.as<double>()) != HIPFFT_SUCCESS)
         return fail(ctx, MTG_E_HIP, "mtg_chain_autocorr: hipfftExecZ2D failed");
     double *d_rho = d_r.as<double>() + n2 * EP;
     mtg_launch_acf_out(n_t, n2, EP, 1.0 / (double)n2, d_r.as<double>(), d_rho, s);   // hipFFT does not normalise
@@ -1822,107 +1869,37 @@ MTG_API int mtg_chain_autocorr(mtg_ctx *ctx, int64_t n_t, int64_t E, int W, int 
     return MTG_OK;
 }
 
-// transforms per execution of the simulator's hipFFT plan (lengths hipFFT transforms natively; the others take the
-// chirp-z path below): a function of the length alone for a full call, so that one plan serves every such call (16
-// transforms of 10^6 points fill the GPU; short transforms are batched by the hundred; MTG_SIM_BATCH overrides, for
-// measurements) -- as long as the spectrum and series buffers of one execution, 16 nk + 8 nfft bytes per transform, stay
-// within 2 GiB.  A call of fewer series than that (Simulator.generate_lightcurve() asks for ONE) gets a plan of its own
-// size in the context's second slot: no transforms of empty slots, and a native plan costs milliseconds to build.
-static int sim_batch_for(int64_t nfft, int64_t S = INT64_MAX)
+// ---- the TK95 simulator: how a call is cut and which cached plan serves it is mtg_sim_plan.h's to say ----
+static MtgSimLayout sim_layout(const mtg_ctx *ctx, int64_t nfft, int64_t S)
 {
-    int64_t b = ((int64_t)1 << 24) / nfft;
-    b = b < 16 ? 16 : b > 256 ? 256 : b;
-    if (const char *env = mtg_measure_env("MTG_SIM_BATCH")) b = atoi(env) > 0 ? atoi(env) : b;   // MTG_MEASURE builds only
-    const int64_t fit = ((int64_t)1 << 31) / (16 * (nfft / 2 + 1) + 8 * nfft);
-    if (b > fit) b = fit;
-    if (b > S) b = S;   // fewer series than a full batch: no transforms of empty slots
-    return (int)(b < 1 ? 1 : b);
+    const char *env = mtg_measure_env("MTG_SIM_BATCH");   // MTG_MEASURE builds only
+    return mtg_sim_layout(nfft, S, ctx->sim_transform, ctx->czt.pairs_on, env ? atoi(env) : 0);
 }
 
-// the context's C2R plan of length nfft for a call of S series (made, or remade for another length or batch, under
-// sim_mu); no fail(): may run on a helper thread
-static int sim_plan_get(mtg_ctx *ctx, int64_t nfft, int64_t S, hipfftHandle *plan)
+// the context's cached plan for a layout -- the Z2D plan of length nfft, or the chirp-z path's Z2Z plan of length m --
+// made, or remade for another length or batch, under sim_mu; 0 when hipFFT refuses.  No fail(): may run on a helper thread
+static hipfftHandle sim_plan_get(mtg_ctx *ctx, int64_t nfft, const MtgSimLayout &cut)
 {
     std::lock_guard<std::mutex> lock(ctx->sim_mu);
-    const int batch = sim_batch_for(nfft, S);
-    mtg_ctx::SimPlan &sp = ctx->sim_plans[batch == sim_batch_for(nfft) ? 0 : 1];
-    if (!(sp.have && sp.nfft == nfft && sp.batch == batch)) {
-        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-        if (sp.have) { (void)hipfftDestroy(sp.h); sp.have = false; }
-        if (hipfftPlan1d(&sp.h, (int)nfft, HIPFFT_Z2D, batch) != HIPFFT_SUCCESS) return MTG_E_HIP;
-        sp.have = true;
-        sp.nfft = nfft;
-        sp.batch = batch;
-    }
-    if (plan) *plan = sp.h;
-    return MTG_OK;
+    return cut.czt ? ctx->czt.plans[cut.slot].get({HIPFFT_Z2Z, cut.m, cut.batch})
+                   : ctx->sim_plans[cut.slot].get({HIPFFT_Z2D, nfft, cut.batch});
 }
 
-// ---- the chirp-z path (mtg_simulate.hip) ----
-static int64_t czt_length(int64_t nfft)
-{
-    int64_t m = 1;
-    while (m < 2 * nfft - 1) m <<= 1;
-    return m;
-}
-// lengths hipFFT transforms natively (radices 2 .. 13) keep its Z2D plan; anything with a larger prime factor goes through
-// power-of-two transforms -- while one pair's work area (16 m bytes) stays within 2 GiB.  mtg_set_simulate_transform
-// forces one or the other (mode 1: the library's plan, 2: chirp-z).
-static bool sim_wants_czt(const mtg_ctx *ctx, int64_t nfft)
-{
-    if (ctx->sim_transform == 1) return false;
-    if (ctx->sim_transform == 2) return czt_length(nfft) * 16 <= ((int64_t)1 << 31);
-    int64_t r = nfft;
-    for (int64_t f : {2, 3, 5, 7, 11, 13})
-        while (r % f == 0) r /= f;
-    return r > 1 && czt_length(nfft) * 16 <= ((int64_t)1 << 31);
-}
-// complex transforms per execution (each carries `per` = 2 series, or 1 with pairing off): up to 1 GiB of work area, no more
-// than the call needs
-static int czt_pairs_for(int64_t m, int64_t S = INT64_MAX, int per = 2)
-{
-    int64_t pairs = ((int64_t)1 << 30) / (m * 16);
-    pairs = pairs < 1 ? 1 : pairs > 128 ? 128 : pairs;
-    const int64_t need = S == INT64_MAX ? pairs : (S + per - 1) / per;
-    return (int)(pairs < need ? pairs : need);
-}
-static int czt_plan_get(mtg_ctx *ctx, int64_t m, int pairs, hipfftHandle *plan)
-{
-    std::lock_guard<std::mutex> lock(ctx->sim_mu);
-    auto &sp = ctx->czt.plans[pairs == czt_pairs_for(m) ? 0 : 1];
-    if (!(sp.have && sp.m == m && sp.pairs == pairs)) {
-        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-        if (sp.have) { (void)hipfftDestroy(sp.h); sp.have = false; }
-        if (hipfftPlan1d(&sp.h, (int)m, HIPFFT_Z2Z, pairs) != HIPFFT_SUCCESS) return MTG_E_HIP;
-        sp.have = true;
-        sp.m = m;
-        sp.pairs = pairs;
-    }
-    if (plan) *plan = sp.h;
-    return MTG_OK;
-}
-// chirp and transformed wrapped chirp of length nfft, made on `s` the first time a length is used
+// chirp and transformed wrapped chirp of length nfft (mtg_simulate.hip), made on `s` the first time a length is used
 static int czt_tables_get(mtg_ctx *ctx, int64_t nfft, hipStream_t s)
 {
     mtg_ctx::SimCzt &z = ctx->czt;
-    const int64_t m = czt_length(nfft);
+    const int64_t m = mtg_czt_length(nfft);
     if (z.tables && z.nfft == nfft) return MTG_OK;
     z.tables = false;
-    if (z.chirp.reserve((size_t)nfft * 16) != hipSuccess || z.bhat.reserve((size_t)m * 16) != hipSuccess) return MTG_E_HIP;
+    if (z.chirp.reserve_n<double2>(nfft) != hipSuccess || z.bhat.reserve_n<double2>(m) != hipSuccess) return MTG_E_HIP;
     mtg_launch_czt_tables(nfft, m, z.chirp.as<double2>(), z.bhat.as<double2>(), s);
-    hipfftHandle one = 0;
-    {
-        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-        if (hipfftPlan1d(&one, (int)m, HIPFFT_Z2Z, 1) != HIPFFT_SUCCESS) return MTG_E_HIP;
-    }
-    bool ok = hipfftSetStream(one, s) == HIPFFT_SUCCESS &&
-              hipfftExecZ2Z(one, (hipfftDoubleComplex *)z.bhat.p, (hipfftDoubleComplex *)z.bhat.p, HIPFFT_FORWARD) == HIPFFT_SUCCESS;
-    ok = ok && hipStreamSynchronize(s) == hipSuccess;    // (the plan's own work area goes with the plan)
-    {
-        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-        (void)hipfftDestroy(one);
-    }
-    if (!ok) return MTG_E_HIP;
+    FftPlan one;   // (the plan and its own work area go at the return: after the synchronisation, where it ran)
+    const hipfftHandle h = one.get({HIPFFT_Z2Z, m, 1});
+    if (!h || hipfftSetStream(h, s) != HIPFFT_SUCCESS ||
+        hipfftExecZ2Z(h, (hipfftDoubleComplex *)z.bhat.p, (hipfftDoubleComplex *)z.bhat.p, HIPFFT_FORWARD) != HIPFFT_SUCCESS ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return MTG_E_HIP;
     z.tables = true;
     z.nfft = nfft;
     z.m = m;
@@ -1933,11 +1910,8 @@ MTG_API int mtg_simulate_plan(mtg_ctx *ctx, int64_t nfft)
 {
     if (!ctx || nfft < 4 || nfft > ((int64_t)1 << 30)) return MTG_E_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return MTG_E_HIP;   // (HIP's current device is per thread)
-    if (sim_wants_czt(ctx, nfft)) {   // the bulk plan of the power-of-two transforms (milliseconds); the tables at first use
-        const int64_t m = czt_length(nfft);
-        return czt_plan_get(ctx, m, czt_pairs_for(m), nullptr);
-    }
-    return sim_plan_get(ctx, nfft, INT64_MAX, nullptr);   // the bulk plan
+    // the bulk plan: of the power-of-two transforms for a chirp-z length (milliseconds; the tables at first use)
+    return sim_plan_get(ctx, nfft, sim_layout(ctx, nfft, INT64_MAX)) ? MTG_OK : MTG_E_HIP;
 }
 
 // The E13 flux-PDF adjustment (mtg_e13.hip) of the `sc` segments e13.seg[sc][n] of one simulation chunk (global indices
@@ -1963,19 +1937,12 @@ static int e13_adjust_chunk(mtg_ctx *ctx, int64_t sc, int64_t chunk, int64_t s0,
     HIP_TRY(ctx, E.flags.reserve((size_t)(2 * chunk + 1) * 4));
     HIP_TRY(ctx, E.stdv.reserve((size_t)chunk * 8));
     HIP_TRY(ctx, E.temp.reserve(temp_bytes > 0 ? temp_bytes : 16));
-    if (!E.have || E.n != n || E.batch != chunk) {
-        std::lock_guard<std::mutex> plans(g_fft_plan_mu);
-        if (E.have) { (void)hipfftDestroy(E.fwd); (void)hipfftDestroy(E.inv); E.have = false; }
-        int len = (int)n;
-        if (hipfftPlanMany(&E.fwd, 1, &len, nullptr, 1, (int)n, nullptr, 1, (int)nk, HIPFFT_D2Z, (int)chunk) != HIPFFT_SUCCESS)
-            return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftPlanMany (forward, n = %lld, batch = %lld) failed", (long long)n, (long long)chunk);
-        if (hipfftPlanMany(&E.inv, 1, &len, nullptr, 1, (int)nk, nullptr, 1, (int)n, HIPFFT_Z2D, (int)chunk) != HIPFFT_SUCCESS) {
-            (void)hipfftDestroy(E.fwd);
-            return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftPlanMany (inverse, n = %lld, batch = %lld) failed", (long long)n, (long long)chunk);
-        }
-        E.have = true; E.n = n; E.batch = chunk;
-    }
-    if (hipfftSetStream(E.fwd, s) != HIPFFT_SUCCESS || hipfftSetStream(E.inv, s) != HIPFFT_SUCCESS)
+    hipfftHandle fwd = 0, inv = 0;
+    const int bad = fft_pair_get(E.fwd, {HIPFFT_D2Z, n, (int)chunk, n, nk}, E.inv, {HIPFFT_Z2D, n, (int)chunk, nk, n}, &fwd, &inv);
+    if (bad)
+        return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftPlanMany (%s, n = %lld, batch = %lld) failed", bad == 1 ? "forward" : "inverse",
+                    (long long)n, (long long)chunk);
+    if (hipfftSetStream(fwd, s) != HIPFFT_SUCCESS || hipfftSetStream(inv, s) != HIPFFT_SUCCESS)
         return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftSetStream failed");
     double *seg = E.seg.as<double>(), *x = E.x.as<double>(), *fresh = E.fresh.as<double>(), *values = E.values.as<double>();
     double *adj = E.adj.as<double>(), *keys = E.keys.as<double>(), *amp = E.amp.as<double>();
@@ -1990,7 +1957,7 @@ static int e13_adjust_chunk(mtg_ctx *ctx, int64_t sc, int64_t chunk, int64_t s0,
     }
     mtg_launch_e13_iota(sc, n, idx, done, s);
     // the target: amplitudes of the TK95 segment; the white series and its sorted values
-    if (hipfftExecD2Z(E.fwd, seg, (hipfftDoubleComplex *)spec) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftExecD2Z failed");
+    if (hipfftExecD2Z(fwd, seg, (hipfftDoubleComplex *)spec) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftExecD2Z failed");
     mtg_launch_e13_abs(sc * nk, spec, amp, s);
     if (E.given_S) {
         const int64_t gS = E.given_S, gn = E.given_n;
@@ -2006,9 +1973,9 @@ static int e13_adjust_chunk(mtg_ctx *ctx, int64_t sc, int64_t chunk, int64_t s0,
     int it = 0;
     int32_t still = (int32_t)sc;
     for (; it <= E.max_iter && still > 0; ++it) {
-        if (hipfftExecD2Z(E.fwd, x, (hipfftDoubleComplex *)spec) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftExecD2Z failed");
+        if (hipfftExecD2Z(fwd, x, (hipfftDoubleComplex *)spec) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftExecD2Z failed");
         mtg_launch_e13_phase(sc * nk, amp, spec, s);
-        if (hipfftExecZ2D(E.inv, (hipfftDoubleComplex *)spec, adj) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftExecZ2D failed");
+        if (hipfftExecZ2D(inv, (hipfftDoubleComplex *)spec, adj) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "E13 adjustment: hipfftExecZ2D failed");
         HIP_TRY(ctx, mtg_launch_e13_rank(sc, n, adj, keys, idx, order_tmp, segment, segment_out, order, E.temp.p, temp_bytes, s));
         HIP_TRY(ctx, hipMemsetAsync(running, 0, 4, s));
         mtg_launch_e13_step(sc, n, order, values, x, fresh, done, notconv, running, s);
@@ -2021,17 +1988,58 @@ static int e13_adjust_chunk(mtg_ctx *ctx, int64_t sc, int64_t chunk, int64_t s0,
     return MTG_OK;
 }
 
-MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, const double *psd_table, int64_t psd_rows,
-                              uint64_t seed, int64_t nfft, double sim_dt, double mean_rate, int64_t seg_len,
-                              const int32_t *win_lo, const int32_t *win_hi, int noise_kind, double sigma_noise,
-                              const double *exposures, double *clean, double *rates, double *dy, double *lc_means,
-                              double *segments, int make_resident)
+namespace {
+
+struct SimArgs {   // what mtg_simulate_tk95 is called with, in its order
+    int64_t S; const double *theta, *psd_table; int64_t psd_rows; uint64_t seed; int64_t nfft; double sim_dt, mean_rate;
+    int64_t seg_len; const int32_t *win_lo, *win_hi; int noise_kind; double sigma_noise; const double *exposures;
+    double *clean, *rates, *dy, *lc_means, *segments; int make_resident;
+};
+
+// One mtg_simulate_tk95 in flight.  The entry runs the stages in order -- check, stage, make_plan, then transform and
+// observe chunk by chunk, finish -- and returns at the first that fails; ~SimCall is the epilogue of every return.
+struct SimCall : SimArgs {
+    SimCall(const SimArgs &a, mtg_ctx *c) : SimArgs(a), ctx(c) {}
+    mtg_ctx *ctx;
+    hipStream_t s = nullptr;
+    int64_t N = 0, nk = 0;
+    int P = 0;
+    MtgSimLayout cut{};
+    hipfftHandle plan = 0;
+    DevBuf d_lo, d_hi, d_expo, d_clean, d_rates, d_dy, d_means, d_psd, d_seg, yv_tmp;
+    MtgTk95Spectrum spectrum;   // the launchers' arguments: the call's part filled by check() and stage(), the chunk's as it comes
+    MtgTk95Segment segment;
+    MtgTk95Observe observed;
+    const char *what = "allocation";   // the stage a HIP error is reported under
+    bool entered = false;              // the checks passed: the draws handed in for this call are consumed
+    bool armed = false;                // staging has begun: a failure now may leave the resident set freed or half written
+    bool done = false;
+
+    int check();
+    int stage();
+    int make_plan();
+    int transform(int64_t s0, int64_t sc);
+    int observe(int64_t s0, int64_t sc);
+    int finish();
+    ~SimCall();
+};
+
+#define SIM_TRY(call)                                                                                         \
+    do {                                                                                                      \
+        hipError_t e__ = (call);                                                                              \
+        if (e__ != hipSuccess)                                                                                \
+            return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95 (%s): %s", what, hipGetErrorString(e__));          \
+    } while (0)
+
+// arguments and state; the draws handed in for this call
+int SimCall::check()
 {
     int rc = check_ready(ctx, psd_table == nullptr);   // a tabulated spectrum needs no model
     if (rc) return rc;
     if (psd_table && psd_rows != 1 && psd_rows != S)
         return fail(ctx, MTG_E_ARG, "mtg_simulate_tk95: psd_rows must be 1 or S");
-    const int64_t N = ctx->N;
+    N = ctx->N;
+    nk = nfft / 2 + 1;
     if (nfft > ((int64_t)1 << 30)) return fail(ctx, MTG_E_ARG, "mtg_simulate_tk95: nfft above 2^30");
     if (S <= 0 || nfft < 4 || !(sim_dt > 0.0) || seg_len <= 0 || seg_len > nfft || !win_lo || !win_hi || !rates || !dy ||
         (!psd_table && !theta && ctx->model.P > 0))
@@ -2040,8 +2048,8 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
         return fail(ctx, MTG_E_ARG, "mtg_simulate_tk95: bad noise specification");
     if (noise_kind == 3 && ctx->kraft.N != N)
         return fail(ctx, MTG_E_STATE, "mtg_simulate_tk95: noise_kind 3 (Kraft) needs mtg_set_simulate_kraft for the %lld epochs of the resident sampling", (long long)N);
-    MtgKraftTables kraft;
     if (noise_kind == 3) {
+        MtgKraftTables &kraft = observed.kraft;
         kraft.bkg_counts = ctx->kraft.bkg.as<double>(); kraft.bkg_rate_err = ctx->kraft.err.as<double>();
         kraft.median = ctx->kraft.med.as<double>(); kraft.half = ctx->kraft.half.as<double>();
         kraft.K = ctx->kraft.K; kraft.threshold = ctx->kraft.threshold;
@@ -2055,177 +2063,216 @@ MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, cons
     // draws handed in for this call (consumed whatever happens next)
     const int64_t given_S = ctx->given.S, given_nk = ctx->given.nk;
     ctx->given.S = 0;
-    if (given_S && (given_S != S || given_nk != nfft / 2 + 1))
+    if (given_S && (given_S != S || given_nk != nk))
         return fail(ctx, MTG_E_ARG, "mtg_simulate_tk95: the draws of mtg_set_simulate_draws are for %lld series of %lld frequencies, "
-                    "this call simulates %lld of %lld", (long long)given_S, (long long)given_nk, (long long)S, (long long)(nfft / 2 + 1));
+                    "this call simulates %lld of %lld", (long long)given_S, (long long)given_nk, (long long)S, (long long)nk);
     for (int64_t i = 0; i < given_S; ++i)  // a start is an index into the series: the kernels do not check it
         if (ctx->given.starts_host[i] + seg_len > nfft)
             return fail(ctx, MTG_E_ARG, "mtg_simulate_tk95: given start %lld + segment %lld beyond the series of %lld samples",
                         (long long)ctx->given.starts_host[i], (long long)seg_len, (long long)nfft);
-    const double *given_normals = given_S ? ctx->given.normals.as<double>() : nullptr;
-    const int64_t *given_starts = given_S ? ctx->given.starts.as<int64_t>() : nullptr;
+    spectrum.given = given_S ? ctx->given.normals.as<double>() : nullptr;
+    segment.given_start = observed.given_start = given_S ? ctx->given.starts.as<int64_t>() : nullptr;
     rc = use_device(ctx);
     if (rc) return rc;
-    struct E13Given {   // the E13 draws handed in for this call are consumed whatever happens next; the report starts afresh
-        mtg_ctx *c;
-        ~E13Given() { c->e13.given_S = 0; }
-    } e13_given{ctx};
+    entered = true;   // (the E13 draws too are consumed from here on; the report starts afresh)
     ctx->e13.iterations = 0;
     ctx->e13.not_converged = 0;
     if (ctx->e13.kind != 0 && !(mean_rate > 0.0) && ctx->e13.kind == 1)
         return fail(ctx, MTG_E_ARG, "mtg_simulate_tk95: a lognormal flux PDF needs a positive mean rate");
-    mtg_trace::Range range("mtg:simulate_tk95");
+    return MTG_OK;
+}
+
+// the layout of the call; allocations, uploads and the model's expansion; the launchers' arguments that every chunk shares
+int SimCall::stage()
+{
     MtgModel m0;
     memset(&m0, 0, sizeof m0);
     const MtgModel &m = psd_table ? m0 : ctx->model;
-    const int P = m.P;
-    MtgCoefLayout lay{m.nr_max, m.nc_max};
-    rc = reserve_workspace(ctx, S, lay.nslots() > 4 ? lay.nslots() : 4, 1);
+    P = m.P;
+    const MtgCoefLayout lay{m.nr_max, m.nc_max};
+    int rc = reserve_workspace(ctx, S, lay.nslots() > 4 ? lay.nslots() : 4, 1);
     if (rc) return rc;
-    CTX_STREAM(ctx, s);
-    const int64_t nk = nfft / 2 + 1;
+    CTX_STREAM(ctx, st);
+    s = st;
     // the simulations go through the context's plan `chunk` at a time (the last group may be short: the transforms of
-    // the unused slots run on whatever the buffer holds and are not looked at)
-    const bool czt = sim_wants_czt(ctx, nfft);
-    const int64_t czt_m = czt ? czt_length(nfft) : 0;
-    const int czt_per = ctx->czt.pairs_on ? 2 : 1;   // series per complex transform
-    const int czt_pairs = czt ? czt_pairs_for(czt_m, S, czt_per) : 0;
-    const int64_t chunk = czt ? czt_per * (int64_t)czt_pairs : sim_batch_for(nfft, S);
-    DevBuf &spec = ctx->sim_spec, &series = ctx->sim_series;
-    DevBuf d_lo, d_hi, d_expo, d_clean, d_rates, d_dy, d_means, d_psd, d_seg;
-    hipError_t e = hipSuccess;
-    const char *what = "allocation";
+    // the unused slots run on zeros and are not looked at)
+    cut = sim_layout(ctx, nfft, S);
     HIP_TRY(ctx, ctx->theta.reserve((size_t)S * (P > 0 ? P : 1) * 8));
     HIP_TRY(ctx, ctx->out.reserve((size_t)S * 8));
     HIP_TRY(ctx, ctx->status.reserve((size_t)S * 4));
-    e = spec.reserve((size_t)chunk * nk * 16);
-    if (e == hipSuccess) e = series.reserve((size_t)chunk * nfft * 8);
-    if (e == hipSuccess) e = d_lo.reserve((size_t)N * 4);
-    if (e == hipSuccess) e = d_hi.reserve((size_t)N * 4);
-    if (e == hipSuccess) e = d_expo.reserve((size_t)N * 8);
-    if (e == hipSuccess && clean) e = d_clean.reserve((size_t)S * N * 8);
-    if (e == hipSuccess) e = d_rates.reserve((size_t)S * N * 8);
-    if (e == hipSuccess) e = d_dy.reserve((size_t)S * N * 8);
-    if (e == hipSuccess) e = d_means.reserve((size_t)S * 8);
-    if (e == hipSuccess && psd_table) e = d_psd.reserve((size_t)psd_rows * nk * 8);
-    if (e == hipSuccess && psd_table) e = hipMemcpyAsync(d_psd.p, psd_table, (size_t)psd_rows * nk * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && segments) e = d_seg.reserve((size_t)S * seg_len * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo.p, win_lo, (size_t)N * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_hi.p, win_hi, (size_t)N * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && exposures) e = hipMemcpyAsync(d_expo.p, exposures, (size_t)N * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)S * P * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && !psd_table) {
+    armed = true;
+    const auto upload = [this](DevBuf &b, const void *src, size_t bytes) {
+        const hipError_t e = b.reserve(bytes);
+        return e != hipSuccess || !src ? e : hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, s);
+    };
+    SIM_TRY(ctx->sim_spec.reserve((size_t)cut.spec_bytes));
+    SIM_TRY(ctx->sim_series.reserve((size_t)cut.series_bytes));
+    SIM_TRY(upload(d_lo, win_lo, (size_t)N * 4));
+    SIM_TRY(upload(d_hi, win_hi, (size_t)N * 4));
+    SIM_TRY(upload(d_expo, exposures, (size_t)N * 8));
+    if (clean) SIM_TRY(d_clean.reserve_n<double>(S * N));
+    SIM_TRY(d_rates.reserve_n<double>(S * N));
+    SIM_TRY(d_dy.reserve_n<double>(S * N));
+    SIM_TRY(d_means.reserve_n<double>(S));
+    if (psd_table) SIM_TRY(upload(d_psd, psd_table, (size_t)psd_rows * nk * 8));
+    if (segments) SIM_TRY(d_seg.reserve_n<double>(S * seg_len));
+    if (P > 0) SIM_TRY(hipMemcpyAsync(ctx->theta.p, theta, (size_t)S * P * 8, hipMemcpyHostToDevice, s));
+    if (!psd_table) {
         // theta -> celerite coefficients (no prior: the samples come from the posterior itself)
         mtg_launch_prepare(make_prep_args(ctx, S, ctx->theta.as<double>(), 0, ctx->out.as<double>(), ctx->status.as<int32_t>(), 1), s);
-        e = hipGetLastError();
-    }
-    hipfftHandle plan = 0;
-    if (e == hipSuccess) {
-        what = "hipfftPlan1d";
-        const int prc = czt ? (czt_tables_get(ctx, nfft, s) != MTG_OK || ctx->czt.work.reserve((size_t)czt_pairs * czt_m * 16) != hipSuccess
-                                   ? MTG_E_HIP : czt_plan_get(ctx, czt_m, czt_pairs, &plan))
-                            : sim_plan_get(ctx, nfft, S, &plan);
-        if (prc != MTG_OK || hipfftSetStream(plan, s) != HIPFFT_SUCCESS) {
-            return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipFFT plan creation failed (nfft = %lld, batch = %lld)",
-                        (long long)nfft, (long long)chunk);
-        }
+        SIM_TRY(hipGetLastError());
     }
     // irfft normalisation (hipFFT C2R is unnormalised) and the reference's power scaling
     const double scale = sqrt((double)nfft * sim_dt * sqrt(2.0 * M_PI)) / (double)nfft;
-    for (int64_t s0 = 0; e == hipSuccess && s0 < S; s0 += chunk) {
-        const int64_t sc = s0 + chunk <= S ? chunk : S - s0;
-        what = "simulation kernels";
-        mtg_launch_tk95_spectrum(sc, s0, ctx->stream_base, nfft, sim_dt, ctx->coef.as<double>(), ctx->cstride, lay, m.nr0, m.nc0,
-                                 ctx->sig.as<int32_t>(), psd_table ? d_psd.as<double>() : nullptr, psd_rows, seed, given_normals,
-                                 spec.as<double2>(), s);
-        if (czt) {
-            // pairs of series through two power-of-two complex transforms (a short last group packs zeros into the
-            // pairs it does not fill: the plan's batch is fixed)
-            double2 *work = ctx->czt.work.as<double2>();
-            mtg_launch_czt_pack(sc, czt_per, nfft, czt_m, spec.as<double2>(), ctx->czt.chirp.as<double2>(), work, s);
-            const int64_t used = (sc + czt_per - 1) / czt_per;
-            if (used < czt_pairs) e = hipMemsetAsync(work + used * czt_m, 0, (size_t)(czt_pairs - used) * czt_m * 16, s);
-            if (e != hipSuccess) break;
-            bool ok = hipfftExecZ2Z(plan, (hipfftDoubleComplex *)work, (hipfftDoubleComplex *)work, HIPFFT_FORWARD) == HIPFFT_SUCCESS;
-            if (ok) mtg_launch_czt_mul(used, czt_m, ctx->czt.bhat.as<double2>(), work, s);
-            ok = ok && hipfftExecZ2Z(plan, (hipfftDoubleComplex *)work, (hipfftDoubleComplex *)work, HIPFFT_BACKWARD) == HIPFFT_SUCCESS;
-            if (!ok) {
-                return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipfftExecZ2Z failed");  // (the resident set is untouched so far)
-            }
-            mtg_launch_czt_unpack(sc, czt_per, nfft, czt_m, work, ctx->czt.chirp.as<double2>(), series.as<double>(), s);
-        } else {
-            if (sc < chunk)  // a short last group: the unused slots transform zeros
-                e = hipMemsetAsync((char *)spec.p + (size_t)sc * nk * 16, 0, (size_t)(chunk - sc) * nk * 16, s);
-            if (e != hipSuccess) break;
-            if (hipfftExecZ2D(plan, (hipfftDoubleComplex *)spec.p, series.as<double>()) != HIPFFT_SUCCESS) {
-                return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipfftExecZ2D failed");  // (the resident set is untouched so far)
-            }
-        }
-        if (ctx->e13.kind != 0) {
-            // A non-Gaussian flux PDF (simulator.py:65-140): the cut segments as rates on the fine grid, adjusted on the
-            // device (mtg_e13.hip), then averaged into the epochs from the ADJUSTED series (start 0, no rescaling).
-            what = "E13 adjustment";
-            e = ctx->e13.seg.reserve((size_t)chunk * seg_len * 8);
-            if (e != hipSuccess) break;
-            mtg_launch_tk95_segment(sc, s0, ctx->stream_base, nfft, seg_len, sim_dt, scale, mean_rate, series.as<double>(), seed,
-                                    given_starts, ctx->e13.seg.as<double>(), s, /* out_first = */ s0);
-            if (segments)   // (what the caller asked for: the segments as the reference hands them to its adjustment)
-                e = hipMemcpyAsync(d_seg.as<double>() + s0 * seg_len, ctx->e13.seg.p, (size_t)sc * seg_len * 8, hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) break;
-            const int arc = e13_adjust_chunk(ctx, sc, chunk, s0, seg_len, mean_rate, seed, s);
-            if (arc) {
-                if (make_resident) { ctx->N = 0; ctx->L = 0; }
-                return arc;
-            }
-            mtg_launch_tk95_observe(sc, s0, ctx->stream_base, N, seg_len, seg_len, sim_dt, sim_dt, 0.0, ctx->e13.x.as<double>(),
-                                    d_lo.as<int32_t>(), d_hi.as<int32_t>(), noise_kind, sigma_noise, d_expo.as<double>(),
-                                    0, seed, nullptr, clean ? d_clean.as<double>() : nullptr, d_rates.as<double>(), d_dy.as<double>(), s, kraft);
-            e = hipGetLastError();
-            continue;
-        }
-        mtg_launch_tk95_observe(sc, s0, ctx->stream_base, N, nfft, seg_len, sim_dt, scale, mean_rate, series.as<double>(),
-                                d_lo.as<int32_t>(), d_hi.as<int32_t>(), noise_kind, sigma_noise, d_expo.as<double>(),
-                                -1, seed, given_starts, clean ? d_clean.as<double>() : nullptr, d_rates.as<double>(), d_dy.as<double>(), s, kraft);
-        if (segments)
-            mtg_launch_tk95_segment(sc, s0, ctx->stream_base, nfft, seg_len, sim_dt, scale, mean_rate, series.as<double>(), seed,
-                                    given_starts, d_seg.as<double>(), s);
-        e = hipGetLastError();
+    spectrum.sbase = segment.sbase = observed.sbase = ctx->stream_base;
+    spectrum.seed = segment.seed = observed.seed = seed;
+    spectrum.nfft = nfft; spectrum.dt = sim_dt;
+    spectrum.coef = ctx->coef.as<double>(); spectrum.cstride = ctx->cstride; spectrum.lay = lay; spectrum.nr0 = m.nr0; spectrum.nc0 = m.nc0;
+    spectrum.sig = ctx->sig.as<int32_t>(); spectrum.psd_table = psd_table ? d_psd.as<double>() : nullptr; spectrum.psd_rows = psd_rows;
+    spectrum.X = ctx->sim_spec.as<double2>();
+    segment.nfft = nfft; segment.seg_len = seg_len; segment.dt = sim_dt; segment.scale = scale; segment.mean_rate = mean_rate;
+    segment.series = ctx->sim_series.as<double>();
+    observed.N = N; observed.seg_len = seg_len; observed.dt = sim_dt;
+    observed.win_lo = d_lo.as<int32_t>(); observed.win_hi = d_hi.as<int32_t>();
+    observed.noise_kind = noise_kind; observed.sigma_noise = sigma_noise; observed.exposures = d_expo.as<double>();
+    observed.clean = clean ? d_clean.as<double>() : nullptr; observed.rates = d_rates.as<double>(); observed.dy = d_dy.as<double>();
+    if (ctx->e13.kind != 0) {
+        // the epochs are averaged from the ADJUSTED segments: start 0, no rescaling
+        observed.nfft = seg_len; observed.scale = sim_dt; observed.mean_rate = 0.0; observed.fixed_start = 0; observed.given_start = nullptr;
+    } else {
+        observed.nfft = nfft; observed.scale = scale; observed.mean_rate = mean_rate; observed.series = ctx->sim_series.as<double>();
     }
-    DevBuf yv_tmp;
-    if (e == hipSuccess && (make_resident || lc_means)) {
+    return MTG_OK;
+}
+
+// the cached plan of the layout, on the call's stream; for a chirp-z length its tables and work area
+int SimCall::make_plan()
+{
+    const bool ready = !cut.czt || (czt_tables_get(ctx, nfft, s) == MTG_OK && ctx->czt.work.reserve((size_t)cut.work_bytes) == hipSuccess);
+    plan = ready ? sim_plan_get(ctx, nfft, cut) : 0;
+    if (!plan || hipfftSetStream(plan, s) != HIPFFT_SUCCESS)
+        return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipFFT plan creation failed (nfft = %lld, batch = %lld)",
+                    (long long)nfft, (long long)cut.chunk);
+    return MTG_OK;
+}
+
+// series s0 .. s0 + sc: random spectra, then their inverse transforms into sim_series[sc][nfft]
+int SimCall::transform(int64_t s0, int64_t sc)
+{
+    what = "simulation kernels";
+    spectrum.S = sc; spectrum.s0 = s0;
+    mtg_launch_tk95_spectrum(spectrum, s);
+    double2 *spec = ctx->sim_spec.as<double2>();
+    if (!cut.czt) {
+        if (sc < cut.chunk)  // a short last group: the unused slots transform zeros
+            SIM_TRY(hipMemsetAsync(spec + sc * nk, 0, (size_t)(cut.chunk - sc) * nk * 16, s));
+        if (hipfftExecZ2D(plan, (hipfftDoubleComplex *)spec, ctx->sim_series.as<double>()) != HIPFFT_SUCCESS)
+            return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipfftExecZ2D failed");
+        return MTG_OK;
+    }
+    // pairs of series through two power-of-two complex transforms (a short last group packs zeros into the pairs it
+    // does not fill: the plan's batch is fixed)
+    const mtg_ctx::SimCzt &z = ctx->czt;
+    double2 *work = z.work.as<double2>();
+    hipfftDoubleComplex *w = (hipfftDoubleComplex *)work;
+    mtg_launch_czt_pack(sc, cut.per, nfft, cut.m, spec, z.chirp.as<double2>(), work, s);
+    const int64_t used = (sc + cut.per - 1) / cut.per;
+    if (used < cut.batch) SIM_TRY(hipMemsetAsync(work + used * cut.m, 0, (size_t)(cut.batch - used) * cut.m * 16, s));
+    if (hipfftExecZ2Z(plan, w, w, HIPFFT_FORWARD) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipfftExecZ2Z failed");
+    mtg_launch_czt_mul(used, cut.m, z.bhat.as<double2>(), work, s);
+    if (hipfftExecZ2Z(plan, w, w, HIPFFT_BACKWARD) != HIPFFT_SUCCESS) return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95: hipfftExecZ2Z failed");
+    mtg_launch_czt_unpack(sc, cut.per, nfft, cut.m, work, z.chirp.as<double2>(), ctx->sim_series.as<double>(), s);
+    return MTG_OK;
+}
+
+// series s0 .. s0 + sc at the epochs: cut, averaged over the windows, with noise -- for a non-Gaussian flux PDF
+// (simulator.py:65-140) the cut segments as rates on the fine grid, adjusted on the device (mtg_e13.hip), then averaged
+int SimCall::observe(int64_t s0, int64_t sc)
+{
+    segment.S = observed.S = sc;
+    segment.s0 = observed.s0 = s0;
+    if (ctx->e13.kind == 0) {
+        mtg_launch_tk95_observe(observed, s);
+        if (segments) {
+            segment.out = d_seg.as<double>();
+            mtg_launch_tk95_segment(segment, s);
+        }
+        SIM_TRY(hipGetLastError());
+        return MTG_OK;
+    }
+    what = "E13 adjustment";
+    SIM_TRY(ctx->e13.seg.reserve_n<double>(cut.chunk * seg_len));
+    segment.out = ctx->e13.seg.as<double>();
+    segment.out_first = s0;
+    mtg_launch_tk95_segment(segment, s);
+    if (segments)   // (what the caller asked for: the segments as the reference hands them to its adjustment)
+        SIM_TRY(hipMemcpyAsync(d_seg.as<double>() + s0 * seg_len, ctx->e13.seg.p, (size_t)sc * seg_len * 8, hipMemcpyDeviceToDevice, s));
+    const int rc = e13_adjust_chunk(ctx, sc, cut.chunk, s0, seg_len, mean_rate, seed, s);
+    if (rc) return rc;
+    observed.series = ctx->e13.x.as<double>();
+    mtg_launch_tk95_observe(observed, s);
+    SIM_TRY(hipGetLastError());
+    return MTG_OK;
+}
+
+// the resident set and the means, the downloads
+int SimCall::finish()
+{
+    if (make_resident || lc_means) {
         what = "resident set";
         DevBuf &target = make_resident ? ctx->yv : yv_tmp;  // without make_resident only the means are wanted
-        e = target.reserve((size_t)S * N * 16);
-        if (e == hipSuccess) {
-            mtg_launch_tk95_resident(S, N, d_rates.as<double>(), d_dy.as<double>(), target.as<double2>(),
-                                     d_means.as<double>(), s);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && lc_means) e = hipMemcpyAsync(lc_means, d_means.p, (size_t)S * 8, hipMemcpyDeviceToHost, s);
+        SIM_TRY(target.reserve_n<double2>(S * N));
+        mtg_launch_tk95_resident(S, N, d_rates.as<double>(), d_dy.as<double>(), target.as<double2>(), d_means.as<double>(), s);
+        SIM_TRY(hipGetLastError());
+        if (lc_means) SIM_TRY(hipMemcpyAsync(lc_means, d_means.p, (size_t)S * 8, hipMemcpyDeviceToHost, s));
     }
-    if (e == hipSuccess && clean) e = hipMemcpyAsync(clean, d_clean.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && segments) e = hipMemcpyAsync(segments, d_seg.p, (size_t)S * seg_len * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(rates, d_rates.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, d_dy.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (clean) SIM_TRY(hipMemcpyAsync(clean, d_clean.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s));
+    if (segments) SIM_TRY(hipMemcpyAsync(segments, d_seg.p, (size_t)S * seg_len * 8, hipMemcpyDeviceToHost, s));
+    SIM_TRY(hipMemcpyAsync(rates, d_rates.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s));
+    SIM_TRY(hipMemcpyAsync(dy, d_dy.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s));
+    SIM_TRY(hipStreamSynchronize(s));
+    if (make_resident) ctx->L = S;  // the simulated light curves replace the resident set (same sampling)
+    done = true;
+    return MTG_OK;
+}
+
+// The epilogue, on every return once the checks have passed.
+SimCall::~SimCall()
+{
+    if (!entered) return;
+    ctx->e13.given_S = 0;
     // the plan's buffers stay with the context for the next call of the workflow -- unless they are large enough to be
     // in somebody's way (a fine simulation grid: hundreds of MB per transform)
-    if (spec.cap + series.cap + ctx->czt.work.cap > ((size_t)1 << 30)) { spec.release(); series.release(); ctx->czt.work.release(); }
-    {   // ... and so do the E13 adjustment's (92 bytes per fine sample and segment of a chunk)
-        mtg_ctx::E13 &E = ctx->e13;
-        DevBuf *eb[] = {&E.seg, &E.x, &E.fresh, &E.values, &E.adj, &E.keys, &E.amp, &E.spec, &E.idx, &E.order, &E.order_tmp, &E.segment, &E.segment_out, &E.temp};
-        size_t held = 0;
-        for (DevBuf *b : eb) held += b->cap;
-        if (held > ((size_t)1 << 30))
-            for (DevBuf *b : eb) b->release();
+    DevBuf &spec = ctx->sim_spec, &series = ctx->sim_series, &work = ctx->czt.work;
+    if (spec.cap + series.cap + work.cap > ((size_t)1 << 30)) { spec.release(); series.release(); work.release(); }
+    // ... and so do the E13 adjustment's (92 bytes per fine sample and segment of a chunk; the flags and standard
+    // deviations counted with them are (2 chunk + 1) 4 + chunk 8 bytes: nothing).  e13.given is the caller's, not scratch
+    size_t held = 0;
+    ctx->e13.each_scratch([&held](DevBuf &b) { held += b.cap; });
+    if (held > ((size_t)1 << 30)) ctx->e13.each_scratch([](DevBuf &b) { b.release(); });
+    // after a failure the resident set may have been freed or partly overwritten on the way: nothing is resident any more
+    if (!done && armed && make_resident) { ctx->N = 0; ctx->L = 0; }
+}
+
+}  // namespace
+
+MTG_API int mtg_simulate_tk95(mtg_ctx *ctx, int64_t S, const double *theta, const double *psd_table, int64_t psd_rows,
+                              uint64_t seed, int64_t nfft, double sim_dt, double mean_rate, int64_t seg_len,
+                              const int32_t *win_lo, const int32_t *win_hi, int noise_kind, double sigma_noise,
+                              const double *exposures, double *clean, double *rates, double *dy, double *lc_means,
+                              double *segments, int make_resident)
+{
+    SimCall c({S, theta, psd_table, psd_rows, seed, nfft, sim_dt, mean_rate, seg_len, win_lo, win_hi, noise_kind, sigma_noise,
+               exposures, clean, rates, dy, lc_means, segments, make_resident}, ctx);
+    int rc = c.check();
+    if (rc) return rc;
+    mtg_trace::Range range("mtg:simulate_tk95");
+    if ((rc = c.stage()) || (rc = c.make_plan())) return rc;
+    for (int64_t s0 = 0; s0 < S; s0 += c.cut.chunk) {
+        const int64_t sc = s0 + c.cut.chunk <= S ? c.cut.chunk : S - s0;
+        if ((rc = c.transform(s0, sc)) || (rc = c.observe(s0, sc))) return rc;
     }
-    if (e != hipSuccess) {
-        // the resident set may have been freed or partly overwritten on the way: nothing is resident any more
-        if (make_resident) { ctx->N = 0; ctx->L = 0; }
-        return fail(ctx, MTG_E_HIP, "mtg_simulate_tk95 (%s): %s", what, hipGetErrorString(e));
-    }
-    if (make_resident) ctx->L = S;  // the simulated light curves replace the resident set (same sampling)
-    return MTG_OK;
+    return c.finish();
 }
 
 MTG_API int mtg_tk95_observe_series(mtg_ctx *ctx, int64_t S, int64_t nfft, int64_t seg_len, int64_t start,
@@ -2242,25 +2289,29 @@ MTG_API int mtg_tk95_observe_series(mtg_ctx *ctx, int64_t S, int64_t nfft, int64
     rc = use_device(ctx);
     if (rc) return rc;
     CTX_STREAM(ctx, s);
+#define OBS_TRY(call)                                                                                             \
+    do {                                                                                                          \
+        hipError_t e__ = (call);                                                                                  \
+        if (e__ != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_tk95_observe_series: %s", hipGetErrorString(e__)); \
+    } while (0)
     DevBuf d_series, d_lo, d_hi, d_rates, d_dy;
-    hipError_t e = d_series.reserve((size_t)S * nfft * 8);
-    if (e == hipSuccess) e = d_lo.reserve((size_t)N * 4);
-    if (e == hipSuccess) e = d_hi.reserve((size_t)N * 4);
-    if (e == hipSuccess) e = d_rates.reserve((size_t)S * N * 8);
-    if (e == hipSuccess) e = d_dy.reserve((size_t)S * N * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_series.p, series, (size_t)S * nfft * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo.p, win_lo, (size_t)N * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_hi.p, win_hi, (size_t)N * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        // scale = dt = 1, mean 0, no noise: the plain window average of the series
-        mtg_launch_tk95_observe(S, 0, 0, N, nfft, seg_len, 1.0, 1.0, 0.0, d_series.as<double>(), d_lo.as<int32_t>(),
-                                d_hi.as<int32_t>(), 0, 0.0, nullptr, start, 0, nullptr, nullptr, d_rates.as<double>(),
-                                d_dy.as<double>(), s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(rates, d_rates.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_tk95_observe_series: %s", hipGetErrorString(e));
+    OBS_TRY(d_series.reserve_n<double>(S * nfft));
+    OBS_TRY(d_lo.reserve_n<int32_t>(N));
+    OBS_TRY(d_hi.reserve_n<int32_t>(N));
+    OBS_TRY(d_rates.reserve_n<double>(S * N));
+    OBS_TRY(d_dy.reserve_n<double>(S * N));
+    OBS_TRY(hipMemcpyAsync(d_series.p, series, (size_t)S * nfft * 8, hipMemcpyHostToDevice, s));
+    OBS_TRY(hipMemcpyAsync(d_lo.p, win_lo, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    OBS_TRY(hipMemcpyAsync(d_hi.p, win_hi, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    MtgTk95Observe oa;   // scale = dt = 1, mean 0, no noise: the plain window average of the series
+    oa.N = N; oa.nfft = nfft; oa.seg_len = seg_len; oa.fixed_start = start;
+    oa.win_lo = d_lo.as<int32_t>(); oa.win_hi = d_hi.as<int32_t>(); oa.rates = d_rates.as<double>(); oa.dy = d_dy.as<double>();
+    oa.S = S; oa.series = d_series.as<double>();
+    mtg_launch_tk95_observe(oa, s);
+    OBS_TRY(hipGetLastError());
+    OBS_TRY(hipMemcpyAsync(rates, d_rates.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s));
+    OBS_TRY(hipStreamSynchronize(s));
+#undef OBS_TRY
     return MTG_OK;
 }
 

@@ -253,12 +253,35 @@ void mtg_launch_split_all(const MtgEnsembleArgs &g, uint32_t iteration0, int ste
 void mtg_launch_initial_best(int E, int W, int P, const double *coords, const double *lnp, double *best_lnp,
                              double *best_coords, hipStream_t);
 // TK95 light-curve simulation (mtg_simulate.hip)
-void mtg_launch_tk95_spectrum(int64_t S, int64_t s0, int64_t sbase, int64_t nfft, double dt, const double *coef, int64_t cstride,
-                              MtgCoefLayout lay, int nr0, int nc0, const int32_t *sig, const double *psd_table,
-                              int64_t psd_rows, uint64_t seed, const double *given, double2 *X, hipStream_t);
-void mtg_launch_tk95_segment(int64_t S, int64_t s0, int64_t sbase, int64_t nfft, int64_t seg_len, double dt, double scale,
-                             double mean_rate, const double *series, uint64_t seed, const int64_t *given_start, double *out,
-                             hipStream_t, int64_t out_first = 0);
+// The launchers take their arguments by name: first what a whole call shares (filled once), then what changes from one
+// chunk of S series, global indices s0 .. s0 + S, to the next.
+struct MtgTk95Spectrum {   // random spectra X[S][nfft / 2 + 1] of the model's (or a tabulated) power spectrum
+    int64_t sbase = 0, nfft = 0;
+    double dt = 1.0;
+    const double *coef = nullptr;   // the expanded model (no table): [slot][cstride], structure of series i in sig[i]
+    int64_t cstride = 0;
+    MtgCoefLayout lay = {0, 0};
+    int nr0 = 0, nc0 = 0;
+    const int32_t *sig = nullptr;
+    const double *psd_table = nullptr;   // [psd_rows][nfft / 2 + 1], psd_rows = 1 or one per series
+    int64_t psd_rows = 0;
+    uint64_t seed = 0;
+    const double *given = nullptr;       // standard normals handed in instead of drawn
+    int64_t S = 0, s0 = 0;
+    double2 *X = nullptr;
+};
+void mtg_launch_tk95_spectrum(const MtgTk95Spectrum &, hipStream_t);
+struct MtgTk95Segment {    // the cut segment of every series as rates: out[s0 - out_first + i][seg_len]
+    int64_t sbase = 0, nfft = 0, seg_len = 0;
+    double dt = 1.0, scale = 1.0, mean_rate = 0.0;
+    uint64_t seed = 0;
+    const int64_t *given_start = nullptr;   // starts handed in instead of drawn
+    int64_t S = 0, s0 = 0;
+    const double *series = nullptr;         // [S][nfft]
+    double *out = nullptr;
+    int64_t out_first = 0;
+};
+void mtg_launch_tk95_segment(const MtgTk95Segment &, hipStream_t);
 // KraftNoise (noise_models.py:81-150) for noise_kind 3: background counts and rate errors per epoch, and the posterior
 // median / half-width of the 68 % interval of the source counts for total counts 0 .. K - 1 (< threshold), [N][K]
 struct MtgKraftTables {
@@ -281,11 +304,22 @@ hipError_t mtg_launch_e13_rank(int64_t S, int64_t n, const double *keys, double 
                                uint32_t *segment, uint32_t *segment_out, int32_t *order, void *temp, size_t temp_bytes, hipStream_t);
 void mtg_launch_e13_step(int64_t S, int64_t n, const int32_t *order, const double *values, double *x, double *fresh, int32_t *done,
                          int32_t *notconv, int32_t *running, hipStream_t);
-void mtg_launch_tk95_observe(int64_t S, int64_t s0, int64_t sbase, int64_t N, int64_t nfft, int64_t seg_len, double dt, double scale,
-                             double mean_rate, const double *series, const int32_t *win_lo, const int32_t *win_hi,
-                             int noise_kind, double sigma_noise, const double *exposures, int64_t fixed_start,
-                             uint64_t seed, const int64_t *given_start, double *clean, double *rates, double *dy, hipStream_t,
-                             const MtgKraftTables &kraft = MtgKraftTables());
+struct MtgTk95Observe {    // window averages of the cut segments at the N epochs, with noise: rates / dy [.][N] by global index
+    int64_t sbase = 0, N = 0, nfft = 0, seg_len = 0;
+    double dt = 1.0, scale = 1.0, mean_rate = 0.0;   // (all neutral: the plain window average of the series)
+    const int32_t *win_lo = nullptr, *win_hi = nullptr;
+    int noise_kind = 0;
+    double sigma_noise = 0.0;
+    const double *exposures = nullptr;
+    MtgKraftTables kraft;
+    int64_t fixed_start = -1;               // >= 0: every segment starts here; -1: drawn from the seed
+    uint64_t seed = 0;
+    const int64_t *given_start = nullptr;   // starts handed in: they go before either
+    double *clean = nullptr, *rates = nullptr, *dy = nullptr;
+    int64_t S = 0, s0 = 0;
+    const double *series = nullptr;         // [S][nfft]
+};
+void mtg_launch_tk95_observe(const MtgTk95Observe &, hipStream_t);
 void mtg_launch_tk95_resident(int64_t L, int64_t N, const double *rates, const double *dy, double2 *yv, double *means,
                               hipStream_t);
 // inverse real transform of a length with large prime factors on power-of-two transforms (chirp-z; mtg_simulate.hip)

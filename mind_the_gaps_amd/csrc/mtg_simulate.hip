@@ -355,34 +355,28 @@ void mtg_launch_tk95_resident(int64_t L, int64_t N, const double *rates, const d
     hipLaunchKernelGGL(mtg_tk95_resident_kernel, dim3((unsigned)L), dim3(256), 0, st, N, rates, dy, yv, means);
 }
 
-void mtg_launch_tk95_spectrum(int64_t S, int64_t s0, int64_t sbase, int64_t nfft, double dt, const double *coef, int64_t cstride,
-                              MtgCoefLayout lay, int nr0, int nc0, const int32_t *sig, const double *psd_table,
-                              int64_t psd_rows, uint64_t seed, const double *given, double2 *X, hipStream_t st)
+void mtg_launch_tk95_spectrum(const MtgTk95Spectrum &a, hipStream_t st)
 {
-    const int64_t n = S * (nfft / 2 + 1);
-    hipLaunchKernelGGL(mtg_tk95_spectrum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, s0, sbase, nfft, dt,
-                       coef, cstride, lay, nr0, nc0, sig, psd_table, psd_rows, (uint32_t)seed, (uint32_t)(seed >> 32), given, X);
+    const int64_t n = a.S * (a.nfft / 2 + 1);
+    hipLaunchKernelGGL(mtg_tk95_spectrum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.S, a.s0, a.sbase, a.nfft, a.dt,
+                       a.coef, a.cstride, a.lay, a.nr0, a.nc0, a.sig, a.psd_table, a.psd_rows, (uint32_t)a.seed,
+                       (uint32_t)(a.seed >> 32), a.given, a.X);
 }
 
-void mtg_launch_tk95_segment(int64_t S, int64_t s0, int64_t sbase, int64_t nfft, int64_t seg_len, double dt, double scale,
-                             double mean_rate, const double *series, uint64_t seed, const int64_t *given_start, double *out,
-                             hipStream_t st, int64_t out_first)
+void mtg_launch_tk95_segment(const MtgTk95Segment &a, hipStream_t st)
 {
-    const int64_t n = S * seg_len;
-    hipLaunchKernelGGL(mtg_tk95_segment_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, s0, sbase, nfft, seg_len,
-                       dt, scale, mean_rate, series, (uint32_t)seed, (uint32_t)(seed >> 32), given_start, out, out_first);
+    const int64_t n = a.S * a.seg_len;
+    hipLaunchKernelGGL(mtg_tk95_segment_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.S, a.s0, a.sbase, a.nfft,
+                       a.seg_len, a.dt, a.scale, a.mean_rate, a.series, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.given_start,
+                       a.out, a.out_first);
 }
 
-void mtg_launch_tk95_observe(int64_t S, int64_t s0, int64_t sbase, int64_t N, int64_t nfft, int64_t seg_len, double dt, double scale,
-                             double mean_rate, const double *series, const int32_t *win_lo, const int32_t *win_hi,
-                             int noise_kind, double sigma_noise, const double *exposures, int64_t fixed_start,
-                             uint64_t seed, const int64_t *given_start, double *clean, double *rates, double *dy, hipStream_t st,
-                             const MtgKraftTables &kraft)
+void mtg_launch_tk95_observe(const MtgTk95Observe &a, hipStream_t st)
 {
-    const int64_t n = S * N;
-    hipLaunchKernelGGL(mtg_tk95_observe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, s0, sbase, N, nfft,
-                       seg_len, dt, scale, mean_rate, series, win_lo, win_hi, noise_kind, sigma_noise, exposures,
-                       fixed_start, (uint32_t)seed, (uint32_t)(seed >> 32), given_start, clean, rates, dy, kraft);
+    const int64_t n = a.S * a.N;
+    hipLaunchKernelGGL(mtg_tk95_observe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.S, a.s0, a.sbase, a.N, a.nfft,
+                       a.seg_len, a.dt, a.scale, a.mean_rate, a.series, a.win_lo, a.win_hi, a.noise_kind, a.sigma_noise, a.exposures,
+                       a.fixed_start, (uint32_t)a.seed, (uint32_t)(a.seed >> 32), a.given_start, a.clean, a.rates, a.dy, a.kraft);
 }
 
 
