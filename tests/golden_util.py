@@ -1,5 +1,6 @@
 """Loaders for tests/golden/loglike_golden.{json,npz} (made by tests/golden/make_golden.py), the light curves of
-tests/golden/quad_golden.json (made by tests/golden/make_quad_golden.py), the right-hand sides and new times of
+tests/golden/quad_golden.json and tests/golden/tp_fallback_golden.json (made by tests/golden/make_quad_golden.py and
+tests/golden/make_tp_fallback_golden.py), the right-hand sides and new times of
 tests/golden/predict_golden.npz (made by tests/golden/make_predict_golden.py) and the calls of
 tests/golden/solve_dispatch.json (made by tests/golden/make_solve_dispatch_golden.py)."""
 import hashlib
@@ -34,7 +35,9 @@ def best_truth(c):
 
 def quad_lightcurve(rec):
     """A quad_golden.json recipe -> (t, y, dy): synthetic.make_lightcurves(N, L, seed, offset), then the edit of the
-    sampling if any ("dup_gap": repeated epochs, dx = 0, every N / 7 samples and a gap of 1e6 days after the middle)."""
+    sampling if any ("dup_gap": repeated epochs, dx = 0, every N / 7 samples and a gap of 1e6 days after the middle;
+    "quiet_spike", tp_fallback_golden.json: the scatter of y about 100 and the errors both scaled by rec["scale"] / 10
+    and rec["scale"], then a second light curve equal to the first but for y[1][rec["spike"]] = rec["spike_value"])."""
     from mind_the_gaps_amd import synthetic as synth
     t, y, dy = synth.make_lightcurves(rec["N"], rec["L"], rec["seed"], rec["offset"])
     edit = rec.get("edit")
@@ -43,6 +46,10 @@ def quad_lightcurve(rec):
         for i in range(10, rec["N"] - 1, rec["N"] // 7):
             t[i + 1] = t[i]
         t[rec["N"] // 2:] += 1.0e6
+    elif edit == "quiet_spike":
+        quiet = 100.0 + rec["scale"] * (y[0] - 100.0) / 10.0
+        y, dy = np.stack([quiet, quiet]), np.stack([rec["scale"] * dy[0]] * 2)
+        y[1, rec["spike"]] = rec["spike_value"]
     elif edit is not None:
         raise ValueError(edit)
     return t, y, dy
