@@ -16,18 +16,35 @@ the burn-in / thinning arithmetic are those of `sampler.EnsembleSampler` and
 `GPModelling.derive_posteriors` (gpmodelling.py:197-286), applied per light curve;
 random numbers come from one vectorised generator instead of L private streams.
 """
+import time
 import warnings
 
 import numpy as np
 
 from . import engine as _engine
 from . import walkers as _walkers
+from ._ppp_plan import BLOCK_SEED_STRIDE, REPRODUCIBLE_TP_ROWS, _plan_protassov, _reproducible_is_free, _split_by_model  # noqa: F401
 from .gp import DeviceModel, LinAlgError, LogProbEvaluator
 from .modeling import ConstantModel
 from .sampler import integrated_time
 
 __all__ = ["EnsembleBatchSampler", "BatchPosteriors", "derive_posteriors_batch", "batched_minimize",
            "protassov_test", "derive_posteriors_sharded"]
+
+
+class PhaseTimer:
+    """Wall time by named phase: ``mark(name)`` closes the phase that began at the previous mark (or at construction)."""
+
+    def __init__(self):
+        self.seconds = {}
+        self._last = time.perf_counter()
+
+    def mark(self, name, seconds=None):
+        """``seconds``: book that much instead of the time since the last mark (which it does not move)."""
+        if seconds is None:
+            now = time.perf_counter()
+            seconds, self._last = now - self._last, now
+        self.seconds[name] = seconds
 
 
 class EnsembleBatchSampler:
@@ -258,11 +275,6 @@ class BatchPosteriors:
             self.median_parameters = None
 
 
-# rows per half-step of a WHOLE set of light curves up to which derive_posteriors_batch(index_base=...) keeps the chains on
-# the batch-independent time-parallel kernel (mtg_set_time_parallel 3); see its docstring
-REPRODUCIBLE_TP_ROWS = 16384
-
-
 def _spread(rng, centers, lower, upper, walkers, percent=0.1, max_attempts=20):
     """spread_walkers (gpmodelling.py:289-350) for every light curve at once."""
     return _walkers.spread(rng.normal, centers, lower, upper, walkers, percent=percent, max_attempts=max_attempts)
@@ -334,12 +346,11 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
     if not model.device_terms:
         raise ValueError("the lock-step driver needs device-expandable terms")
     model.y_offset = None                         # offsets are per light curve, owned by the evaluator
-    import time
-    clock = [("start", time.perf_counter())]
+    timer = PhaseTimer()
     ev = None
     if evaluate is None:
         ev = LogProbEvaluator(times, Y, DY + 1e-12, device=device, y_offset=Y.mean(axis=1), own_engine=own_engine)
-        clock.append(("upload", time.perf_counter()))
+        timer.mark("upload")
 
         def evaluate(theta, lc, add_prior):
             return ev.evaluate(model, theta, lc, add_prior=add_prior)
@@ -371,7 +382,7 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
             kernels(3)
             fit_x, fit_f, _ = batched_minimize(lambda x, lc: -checked(x, lc, False), centers, lower, upper)
             centers, fit_f = fit_x, -fit_f
-            clock.append(("fit", time.perf_counter()))
+            timer.mark("fit")
         kernels(chain_mode)
         if block_free:
             p0 = np.concatenate([_spread(np.random.default_rng([int(seed), 1, int(index_base) + l]), centers[l:l + 1],
@@ -380,10 +391,10 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
         else:
             rng = np.random.default_rng(seed)
             p0 = _spread(rng, centers, lower, upper, walkers)
-        clock.append(("spread", time.perf_counter()))
+        timer.mark("spread")
         if before_sampling is not None:
             before_sampling()
-            clock.append(("wait", time.perf_counter()))
+            timer.mark("wait")
         if device_sampler and ev is not None:
             from .device_sampler import DeviceEnsembleSampler
             dev = DeviceEnsembleSampler(lambda: ev._bind(model), walkers, P, n_ensembles=L,
@@ -399,7 +410,7 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
             sampler.run(p0, max_steps)
     finally:
         kernels(2)
-    clock.append(("sample", time.perf_counter()))
+    timer.mark("sample")
     if store_chain:
         tau = sampler.get_autocorr_time(tol=0)
         mean_tau = np.mean(tau, axis=1)
@@ -414,8 +425,8 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
     res = BatchPosteriors(sampler, tau, discard, thin, fit_x, fit_f, names)
     if own_engine and ev is not None:
         ev.close()      # (everything BatchPosteriors needs has been copied to the host by now)
-    clock.append(("collect", time.perf_counter()))
-    res.seconds = {b[0]: b[1] - a[1] for a, b in zip(clock[:-1], clock[1:])}   # wall time of each phase
+    timer.mark("collect")
+    res.seconds = timer.seconds     # wall time of each phase
     return res
 
 
@@ -431,6 +442,9 @@ def protassov_test(lightcurve, null_kernel, alt_kernel, nsims=100, walkers=12, m
     2. ``nsims`` light curves simulated from the null posteriors (device TK95);
     3. both kernels refitted to every simulated light curve in lock-step;
     4. p-value of ``T_obs`` in the simulated distribution.
+
+    Who does what is decided first, in one value (``_ppp_plan._plan_protassov``); the steps then run as the stages of
+    ``_ProtassovRun`` over that plan, on random numbers drawn in the order ``_seed_schedule`` states.
 
     Returns dict(T_obs, T_sim[nsims], p_value ((1 + #{T_sim >= T_obs}) / (1 + nsims)), p_value_percentile (the tutorial's own
     ``1 - percentileofscore(T_sim, T_obs) / 100``), null, alt, sim_null, sim_alt, lightcurves, seconds, split, reproducible) --
@@ -483,33 +497,16 @@ def protassov_test(lightcurve, null_kernel, alt_kernel, nsims=100, walkers=12, m
     rank's share is beyond the time-parallel range anyway (BASELINE configs[3]: 250 x 128 rows per rank) -- and the
     returned dict says which it was (``reproducible``).  (The observed light curve's chains are rank 0's either way.)
     """
-    from .gpmodelling import GPModelling
     from .simulator import Simulator
     from .stats import lrt_pvalue, lrt_pvalue_percentile, lrt_statistic
-    rng = np.random.default_rng(seed)
-
-    seeds = [int(rng.integers(0, 2 ** 31 - 1)) for _ in range(2)]
-
-    def observed(kernel, seed, own_engine=False):
-        """The observed light curve's chain for one model, from a generator of its own (the stream np.random.seed(seed)
-        would give: nothing here touches numpy's global generator unless the walkers are odd -- the host-side sampler
-        copies the global state, as emcee does)."""
-        g = GPModelling(lightcurve, kernel, device=device, own_engine=own_engine,
-                        random_state=np.random.RandomState(seed) if walkers % 2 == 0 else None)
-        state = np.random.get_state()
-        if walkers % 2:
-            np.random.seed(seed)
-        try:
-            g.derive_posteriors(fit=True, max_steps=max_steps, walkers=walkers, progress=progress,
-                                device_sampler=walkers % 2 == 0)
-        finally:
-            if walkers % 2:
-                np.random.set_state(state)
-        return g
-
-    import threading
-    import time
-    clock = [time.perf_counter()]
+    shard = None
+    if sharded:
+        from .distributed import LightcurveShard
+        shard = LightcurveShard(nsims, group=group)
+    plan = _plan_protassov(nsims, walkers, sim_walkers, shard.rank if sharded else 0, shard.world if sharded else 1,
+                           sharded, split, reproducible, observed_split, observed_side_by_side, concurrent_refits)
+    run = _ProtassovRun(plan, lightcurve, (null_kernel, alt_kernel), device, group)
+    timer = PhaseTimer()
     # the simulator's transform plan is built beside the observed chains (its grid depends on the sampling alone)
     # (``pdf``: the flux PDF of the simulated light curves, simulator.py:149-150 -- "Lognormal" / "Uniform" go through the
     # E13 adjustment on the device, csrc/mtg_e13.hip, ``max_iter`` iterations at most: the loop still never leaves the GPU)
@@ -517,245 +514,248 @@ def protassov_test(lightcurve, null_kernel, alt_kernel, nsims=100, walkers=12, m
                     lightcurve.bkg_rate, lightcurve.bkg_rate_err, sigma_noise=sigma_noise,
                     extension_factor=extension_factor, max_iter=max_iter, random_state=0, device=device)
     sim.warm_up()
-    shard = None
-    if sharded:
-        from .distributed import LightcurveShard, all_gather_rows, block_bounds, broadcast_array
-        shard = LightcurveShard(nsims, group=group)
-    by_model = shard is not None and shard.world >= 2 and bool(observed_split)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        if by_model:
-            # one model's chain per rank (0: null, 1: alternative), on the process's own context
-            null = alt = obs_failure = None
-            try:
-                if shard.rank == 0:
-                    null = observed(null_kernel, seeds[0])
-                elif shard.rank == 1:
-                    alt = observed(alt_kernel, seeds[1])
-            except Exception as exc:      # said to everybody below: nobody may wait in a broadcast for a chain that died
-                obs_failure = exc
-            obs_failed = all_gather_rows(np.array([0.0 if obs_failure is None else 1.0]), np.ones(shard.world, dtype=int), group)
-            if obs_failure is not None:
-                raise obs_failure
-            if obs_failed.any():
-                raise RuntimeError("protassov_test: the observed light curve's chain failed on rank(s) %s"
-                                   % np.flatnonzero(obs_failed).tolist())
-        elif walkers % 2 == 0 and observed_side_by_side:
-            # two single-light-curve chains leave the GPU nearly empty: the two models side by side, each on a context
-            # and a generator of its own -- the same chains as one after the other
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=2) as pool:
-                null, alt = pool.map(lambda a: observed(a[0], a[1], own_engine=("side", a[2])),
-                                     ((null_kernel, seeds[0], 0), (alt_kernel, seeds[1], 1)))
-            null.gp.release_engine()
-            alt.gp.release_engine()
-        else:
-            null, alt = observed(null_kernel, seeds[0]), observed(alt_kernel, seeds[1])
-    clock.append(time.perf_counter())
-    # one estimator on both sides of the test: the largest log-posterior over everything the chains
-    # visited (the refits below store no chains and keep exactly that; the maximum over the burned-in,
-    # thinned chain is systematically smaller, the more so the more parameters a model has)
-    if by_model:
-        alt_best = float(broadcast_array(np.array([alt.best_loglikelihood if alt is not None else 0.0]), group, src=1)[0])
-        null_best = float(null.best_loglikelihood) if null is not None else 0.0     # (rank 0's goes out with the head below)
-        ndim_null = null_kernel.vector_size if null is None else null.mcmc_samples.shape[1]
-        samples = null.mcmc_samples[rng.integers(len(null.mcmc_samples), size=nsims)] if null is not None \
-            else np.zeros((nsims, ndim_null))
-    else:
-        null_best, alt_best = float(null.best_loglikelihood), float(alt.best_loglikelihood)
-        samples = null.mcmc_samples[rng.integers(len(null.mcmc_samples), size=nsims)]
-    t_obs = float(lrt_statistic(null_best, alt_best))
-    # (seeds below 2^52: they travel as float64 in the broadcast)
-    sim_seed, fit_seeds = int(rng.integers(0, 2 ** 31 - 1)), [int(rng.integers(0, 2 ** 52)) for _ in range(2)]
-    sw = sim_walkers or walkers
-    lo, hi, models = 0, nsims, (0, 1)
-    if sharded:
-        if reproducible is None:
-            reproducible = _reproducible_is_free(split, nsims, sw, shard.world)
-    reproducible = bool(reproducible)
-    if sharded:
-        # rank 0's test is everybody's test: its T_obs, its posterior samples and its seeds (every rank drew its own
-        # from its own chains' generator state; under the model split two ranks must simulate the SAME light curves)
-        head = broadcast_array(np.concatenate([[null_best, float(sim_seed)], np.asarray(fit_seeds, dtype=np.float64),
-                                               [t_obs], samples.ravel()]), group)
-        sim_seed, fit_seeds = int(head[1]), [int(head[2]), int(head[3])]
-        # split observed chains: rank 0's null maximum with rank 1's alternative maximum; otherwise rank 0's own T_obs
-        t_obs = float(lrt_statistic(float(head[0]), alt_best)) if by_model else float(head[4])
-        samples = head[5:].reshape(samples.shape)
-        if _split_by_model(split, nsims, sw, shard.world):
-            # half of the ranks refit the null model, the other half the alternative, each half over ALL the light
-            # curves: twice the rows per rank and one model's half-steps instead of both one after the other
-            half = shard.world // 2
-            models = (0,) if shard.rank < half else (1,)
-            block = shard.rank % half
-            bounds = block_bounds(nsims, half)
-            lo, hi = int(bounds[block]), int(bounds[block + 1])
-            if shard.rank >= 2 * half:                           # an odd rank out takes no part in the refits
-                models, lo, hi = (), 0, 0
-        else:
-            block, bounds = shard.rank, shard.bounds
-            lo, hi = shard.lo, shard.hi
-        if not reproducible:
-            sim_seed = (sim_seed + 7919 * block) % (2 ** 31 - 1)   # independent noise on every block (the two ranks
-            fit_seeds = [f + 7919 * block for f in fit_seeds]       # of a block under the model split draw the same)
-    out, fits, best, failure, pair_stats = None, [None, None], [np.empty(0), np.empty(0)], None, None
-    # each model on a context of its own ("slices": and on its own half of the compute units, mtg_create_on_slice --
-    # measured no faster: 7.24 against 7.14 ms per iteration)
-    if concurrent_refits not in (True, False, "auto", "unpaired", "slices"):
-        raise ValueError("concurrent_refits must be True, False, 'auto', 'unpaired' or 'slices'")
-    side_by_side = len(models) == 2 and (concurrent_refits in (True, "unpaired", "slices") or
-                                         (concurrent_refits == "auto" and (hi - lo) * (sw // 2) <= 40000 and hi - lo > 1))
-    if side_by_side and concurrent_refits == "slices":
-        side_by_side = "slices"
-    if hi > lo:
+    seeds = _seed_schedule(seed, nsims)
+    null, alt = run.observed_chains(next(seeds), walkers, max_steps, progress)
+    timer.mark("observed_chains")
+    picks, sim_seed, fit_seeds = seeds.send(null)
+    t_obs, samples, sim_seed, fit_seeds = run.exchange_head(null, alt, picks, sim_seed, fit_seeds)
+    out, fits, pair_stats, failure = None, [None, None], None, None
+    if plan.hi > plan.lo:
         try:
-            sim.random_state = np.random.RandomState(sim_seed)
-            if reproducible:
-                # Every series with the partner it has in the whole set (the simulator's transform packs series 2p and
-                # 2p + 1 together): a block that starts or ends inside a pair simulates the partner too -- its parameters
-                # are at hand, every rank holds all the posterior samples -- and drops it.  At most two extra series.
-                lo_e, hi_e = lo - (lo & 1), min(nsims, hi + (hi & 1))
-                out = sim.simulate(samples[lo_e:hi_e, :null_kernel.vector_size], index_base=lo_e, pair_series=True)
-                keep = slice(lo - lo_e, lo - lo_e + (hi - lo))
-                out = {k: (v[keep] if v is not None else None) for k, v in out.items()}
-            else:
-                out = sim.simulate(samples[lo:hi, :null_kernel.vector_size])
-            clock.append(time.perf_counter())
-            meet = threading.Barrier(2) if side_by_side else None
-            # side by side AND paired: from the chains on, the two contexts' pipelined half-steps go out in ONE launch
-            # (mtg_pair_contexts: eight waves per compute unit on one table set, two per SIMD -- a pipelined sweep alone
-            # takes the whole compute unit, so unpaired launches alternate rather than share SIMDs).  Paired between the
-            # starting fits and the chains: the fits' batches come at each model's own pace and must not wait for each other.
-            paired = side_by_side is True and concurrent_refits != "unpaired"
-
-            def meet_then_pair():
-                first = meet.wait() == 0
-                if paired:
-                    if first:
-                        from .gp import get_side_engine
-                        for k in (0, 1):
-                            get_side_engine(device, k).unpair()      # (whatever an interrupted run may have left)
-                        get_side_engine(device, 0).pair_with(get_side_engine(device, 1))
-                    meet.wait()
-
-            def refit(k):
-                kernel = (null_kernel, alt_kernel)[k]
-                try:
-                    return derive_posteriors_batch(lightcurve.times, out["rates"], out["dy"], kernel, walkers=sw,
-                                                   max_steps=sim_steps, fit=True, seed=fit_seeds[k], device=device,
-                                                   store_chain=False, quiet=True,
-                                                   # side by side: model k on the process's k-th extra context (gp.get_side_engine)
-                                                   own_engine=((k, 2) if side_by_side == "slices" else ("side", k) if side_by_side
-                                                               else False),
-                                                   index_base=lo if reproducible else None,
-                                                   total_lightcurves=nsims if reproducible else None,
-                                                   # (no timeout: a partner that fails aborts the barrier, below)
-                                                   before_sampling=meet_then_pair if meet is not None else None)
-                except BaseException:
-                    if meet is not None:
-                        meet.abort()        # the partner thread must not wait at the barrier for a refit that has failed
-                    raise
-
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")
-                if side_by_side:
-                    # The two models' refits are independent: each on its own context and stream, driven by its own host
-                    # thread (the library calls release the GIL).  Measured at configs[3]'s sizes: 26.30 s side by side
-                    # against 8.40 + 17.96 s one after the other -- both sweeps are bound by FP64 issue and a half-step
-                    # leaves no idle issue slots for the other model to fill; on a block that leaves the GPU room (a rank's
-                    # 250 light curves at 8 GPUs) the two chains interleave and gain 16 %: "auto" (docstring).
-                    from concurrent.futures import ThreadPoolExecutor
-                    from .gp import get_side_engine
-                    try:
-                        with ThreadPoolExecutor(max_workers=2) as pool:
-                            futures = [pool.submit(refit, k) for k in (0, 1)]
-                    finally:
-                        if paired:     # (both threads have returned: nobody is inside a paired call)
-                            pair_stats = get_side_engine(device, 0).pair_stats()
-                            get_side_engine(device, 0).unpair()
-                    errors = [f.exception() for f in futures if f.exception() is not None]
-                    if errors:   # the refit that failed, not the partner it left at the barrier
-                        real = [e for e in errors if not isinstance(e, threading.BrokenBarrierError)]
-                        raise (real or errors)[0]
-                    fits = [f.result() for f in futures]
-                    clock += [time.perf_counter()] * 2
-                else:
-                    for k in (0, 1):
-                        if k in models:
-                            fits[k] = refit(k)
-                        clock.append(time.perf_counter())
-                best = [np.empty(0) if f is None else f.max_loglikelihood for f in fits]
-        except BaseException as exc:     # (simulation or refits)
+            out = run.simulate(sim, samples, sim_seed)
+            timer.mark("simulate")
+            fits, pair_stats = run.refit(out, fit_seeds, sim_steps, timer)
+        except BaseException as exc:     # (simulation or refits: one process raises at once, a rank says it to the others first)
             failure = exc
             if not sharded:
                 raise
-    if sharded:
-        # a rank whose refits failed says so BEFORE the gather: the others must not wait in it for maxima that will not come
-        failed = all_gather_rows(np.array([0.0 if failure is None else 1.0]), np.ones(shard.world, dtype=int), group)
-        if failure is not None:
-            raise failure
-        if failed.any():
-            raise RuntimeError("protassov_test: the refits failed on rank(s) %s" % np.flatnonzero(failed).tolist())
-        # the only exchange of the loop: the maxima of lnL, one all-gather per model
-        if len(models) == 2:
-            best = [shard.gather(b) for b in best]
+    t_sim = lrt_statistic(*run.gather(fits, out, failure))
+    if plan.hi > plan.lo:                # (a rank without a block reports its observed chains only)
+        timer.mark("gather")
+    return dict(T_obs=t_obs, T_sim=t_sim, p_value=lrt_pvalue(t_obs, t_sim), p_value_percentile=lrt_pvalue_percentile(t_obs, t_sim), null=null, alt=alt,
+                sim_null=fits[0], sim_alt=fits[1], lightcurves=out, seconds=timer.seconds, reproducible=plan.reproducible,
+                paired_launches=pair_stats, split=plan.split)
+
+
+def _seed_schedule(seed, nsims):
+    """Every random number protassov_test itself draws, from ONE ``default_rng(seed)``, in the order every bit-for-bit
+    guarantee of the sharded run rests on.  A generator of two steps: ``next`` gives the two chain seeds, ``send(null)``
+    -- the null model's observed chain, or None where another rank runs it -- gives (picks or None, sim_seed, fit_seeds).
+
+    1. two ``integers(0, 2**31 - 1)``: the seeds of the null and the alternative model's observed chain;
+    2. the caller runs the observed chains; they do not touch this generator;
+    3. ``integers(len(null.mcmc_samples), size=nsims)``, the posterior samples to simulate from -- ONLY where the null
+       chain is held (under the observed split that is rank 0);
+    4. one ``integers(0, 2**31 - 1)``: the simulator's seed;
+    5. two ``integers(0, 2**52)``: the seeds of the null and the alternative refits (below 2^52: they travel as float64).
+
+    Ranks that skipped 3 are one draw behind from there on, and every rank's chains left it a different step 3 anyway:
+    rank 0's values of 3 to 5 replace everybody's in ``_ProtassovRun.exchange_head``."""
+    rng = np.random.default_rng(seed)
+    null = yield [int(rng.integers(0, 2 ** 31 - 1)) for _ in range(2)]
+    picks = rng.integers(len(null.mcmc_samples), size=nsims) if null is not None else None
+    sim_seed = int(rng.integers(0, 2 ** 31 - 1))
+    fit_seeds = [int(rng.integers(0, 2 ** 52)) for _ in range(2)]
+    yield picks, sim_seed, fit_seeds
+
+
+def _raise_together(plan, failure, what, group):
+    """Say it to everybody before the next collective: every rank tells whether ``what`` failed here (``failure``: the
+    exception or None); the rank it failed on raises its own error, the others a RuntimeError naming the rank(s) --
+    nobody may wait in a broadcast or a gather for values that will not come."""
+    from .distributed import all_gather_rows
+    failed = all_gather_rows(np.array([0.0 if failure is None else 1.0]), np.ones(plan.world, dtype=int), group)
+    if failure is not None:
+        raise failure
+    if failed.any():
+        raise RuntimeError("protassov_test: %s failed on rank(s) %s" % (what, np.flatnonzero(failed).tolist()))
+
+
+def _refit_side_by_side(refit, paired, device):
+    """``refit(k, before_sampling)`` of both models from two host threads (the library calls release the GIL), each on a
+    context and a stream of its own -> ([null's, alternative's], pair statistics or None).  Measured at configs[3]'s
+    sizes: 26.30 s side by side against 8.40 + 17.96 s one after the other -- both sweeps are bound by FP64 issue and a
+    half-step leaves no idle issue slots for the other model to fill; on a block that leaves the GPU room (a rank's 250
+    light curves at 8 GPUs) the two chains interleave and gain 16 %: "auto" (protassov_test's docstring).
+
+    The threads meet between their starting fits and their chains, so that the chains -- the long, regular part --
+    overlap from the first iteration to the last.  ``paired``: from there on the two contexts' pipelined half-steps go out
+    in ONE launch (mtg_pair_contexts: eight waves per compute unit on one table set, two per SIMD -- a pipelined sweep
+    alone takes the whole compute unit, so unpaired launches alternate rather than share SIMDs); not before, because the
+    fits' batches come at each model's own pace and must not wait for each other.  A refit that fails aborts the barrier
+    (no timeout: its partner must not wait there for it) and it is that refit's error that is raised, not the partner's
+    broken barrier."""
+    import threading
+    from concurrent.futures import ThreadPoolExecutor
+    from .gp import get_side_engine
+    meet = threading.Barrier(2)
+
+    def meet_then_pair():
+        first = meet.wait() == 0
+        if paired:
+            if first:
+                for k in (0, 1):
+                    get_side_engine(device, k).unpair()      # (whatever an interrupted run may have left)
+                get_side_engine(device, 0).pair_with(get_side_engine(device, 1))
+            meet.wait()
+
+    def guarded(k):
+        try:
+            return refit(k, meet_then_pair)
+        except BaseException:
+            meet.abort()
+            raise
+
+    pair_stats = None
+    try:
+        with ThreadPoolExecutor(max_workers=2) as pool:
+            futures = [pool.submit(guarded, k) for k in (0, 1)]
+    finally:
+        if paired:     # (both threads have returned: nobody is inside a paired call)
+            pair_stats = get_side_engine(device, 0).pair_stats()
+            get_side_engine(device, 0).unpair()
+    errors = [f.exception() for f in futures if f.exception() is not None]
+    if errors:
+        real = [e for e in errors if not isinstance(e, threading.BrokenBarrierError)]
+        raise (real or errors)[0]
+    return [f.result() for f in futures], pair_stats
+
+
+class _ProtassovRun:
+    """One rank's run of a Protassov test: the stages of protassov_test, in its order, over a ProtassovPlan."""
+
+    def __init__(self, plan, lightcurve, kernels, device, group):
+        self.plan, self.lightcurve, self.kernels, self.device, self.group = plan, lightcurve, kernels, device, group
+
+    def observed_chains(self, seeds, walkers, max_steps, progress):
+        """Step 1 -> [null, alt]: GPModelling of the observed light curve per model, None for a chain another rank runs."""
+        from .gpmodelling import GPModelling
+        plan = self.plan
+
+        def chain(k, own_engine=False):
+            """Model k's chain from a generator of its own (the stream np.random.seed(seed) would give: nothing here
+            touches numpy's global generator unless the walkers are odd -- the host-side sampler copies the global
+            state, as emcee does -- and then it is put back as it was)."""
+            on_device = plan.observed_device_sampler
+            g = GPModelling(self.lightcurve, self.kernels[k], device=self.device, own_engine=own_engine,
+                            random_state=np.random.RandomState(seeds[k]) if on_device else None)
+            state = np.random.get_state()
+            if not on_device:
+                np.random.seed(seeds[k])
+            try:
+                g.derive_posteriors(fit=True, max_steps=max_steps, walkers=walkers, progress=progress, device_sampler=on_device)
+            finally:
+                if not on_device:
+                    np.random.set_state(state)
+            return g
+
+        chains = [None, None]
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            if plan.observed == "by_model":
+                failure = None
+                try:
+                    for k in plan.observed_models:
+                        chains[k] = chain(k)
+                except Exception as exc:
+                    failure = exc
+                _raise_together(plan, failure, "the observed light curve's chain", self.group)
+            elif plan.observed == "side_by_side":
+                from concurrent.futures import ThreadPoolExecutor
+                with ThreadPoolExecutor(max_workers=2) as pool:
+                    chains = list(pool.map(lambda k: chain(k, own_engine=("side", k)), (0, 1)))
+                for g in chains:
+                    g.gp.release_engine()
+            else:
+                chains = [chain(0), chain(1)]
+        return chains
+
+    def exchange_head(self, null, alt, picks, sim_seed, fit_seeds):
+        """The test every rank works on -> (T_obs, samples[nsims], sim_seed, fit_seeds): one process's own; sharded, rank
+        0's (every rank drew its own from its own chains' state; under the model split two ranks must simulate the SAME
+        light curves), sent as ONE float64 array ``[null_best, sim_seed, fit_seeds[0], fit_seeds[1], t_obs, samples...]``.
+        Under the observed split T_obs is rank 0's null maximum with rank 1's alternative maximum (its own broadcast)."""
+        from .stats import lrt_statistic
+        plan = self.plan
+        # one estimator on both sides of the test: the largest log-posterior over everything the chains
+        # visited (the refits store no chains and keep exactly that; the maximum over the burned-in,
+        # thinned chain is systematically smaller, the more so the more parameters a model has)
+        if plan.observed == "by_model":
+            from .distributed import broadcast_array
+            alt_best = float(broadcast_array(np.array([alt.best_loglikelihood if alt is not None else 0.0]), self.group, src=1)[0])
+            null_best = float(null.best_loglikelihood) if null is not None else 0.0
+            samples = null.mcmc_samples[picks] if null is not None else np.zeros((plan.nsims, self.kernels[0].vector_size))
         else:
+            null_best, alt_best = float(null.best_loglikelihood), float(alt.best_loglikelihood)
+            samples = null.mcmc_samples[picks]
+        t_obs = float(lrt_statistic(null_best, alt_best))
+        if plan.sharded:
+            from .distributed import broadcast_array
+            head = broadcast_array(np.concatenate([[null_best, float(sim_seed)], np.asarray(fit_seeds, dtype=np.float64),
+                                                   [t_obs], samples.ravel()]), self.group)
+            sim_seed, fit_seeds = int(head[1]), [int(head[2]), int(head[3])]
+            t_obs = float(lrt_statistic(float(head[0]), alt_best)) if plan.observed == "by_model" else float(head[4])
+            samples = head[5:].reshape(samples.shape)
+            if not plan.reproducible:
+                # independent noise on every block (the two ranks of a block under the model split draw the same)
+                sim_seed = (sim_seed + BLOCK_SEED_STRIDE * plan.block) % (2 ** 31 - 1)
+                fit_seeds = [f + BLOCK_SEED_STRIDE * plan.block for f in fit_seeds]
+        return t_obs, samples, sim_seed, fit_seeds
+
+    def simulate(self, sim, samples, sim_seed):
+        """Step 2 -> the block's light curves, dict(rates[hi - lo][N], dy, ...) (plan.sim_lo .. keep: the pair partners)."""
+        plan = self.plan
+        sim.random_state = np.random.RandomState(sim_seed)
+        out = sim.simulate(samples[plan.sim_lo:plan.sim_hi, :self.kernels[0].vector_size], index_base=plan.sim_index_base,
+                           pair_series=plan.pair_series)
+        return {k: (v[plan.keep] if v is not None else None) for k, v in out.items()}
+
+    def refit(self, out, fit_seeds, sim_steps, timer):
+        """Step 3 -> ([BatchPosteriors of the null refit or None, of the alternative's or None], pair statistics or None)."""
+        plan = self.plan
+
+        def one(k, before_sampling=None):
+            return derive_posteriors_batch(self.lightcurve.times, out["rates"], out["dy"], self.kernels[k],
+                                           walkers=plan.sim_walkers, max_steps=sim_steps, fit=True, seed=fit_seeds[k],
+                                           device=self.device, store_chain=False, quiet=True, own_engine=plan.own_engine[k],
+                                           index_base=plan.fit_index_base, total_lightcurves=plan.total_lightcurves,
+                                           before_sampling=before_sampling)
+
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            if plan.refits_meet:
+                fits, pair_stats = _refit_side_by_side(one, plan.paired, self.device)
+                timer.mark("refit_null")          # the two refits' common wall time
+                timer.mark("refit_alt", 0.0)
+                return fits, pair_stats
+            fits = [None, None]
+            for k in (0, 1):
+                if k in plan.models:
+                    fits[k] = one(k)
+                timer.mark(("refit_null", "refit_alt")[k])
+            return fits, None
+
+    def gather(self, fits, out, failure):
+        """-> [max lnL of the null refits [nsims], of the alternative's]: the only exchange of the loop, one all-gather per
+        model (plan.counts).  A rank whose simulation or refits failed says so first (``failure``)."""
+        plan = self.plan
+        best = [np.empty(0) if f is None else f.max_loglikelihood for f in fits]
+        if not plan.sharded:
+            return best
+        from .distributed import all_gather_rows
+        _raise_together(plan, failure, "the refits", self.group)
+        if plan.split == "models":
             # the null rank and the alternative rank of a block pair lnL values of what must be the same light curves,
             # simulated on two GPUs: a checksum per rank says so, or the test stops here (a block without light curves
             # -- fewer of them than pairs of ranks -- has nothing to compare)
+            half, bounds = plan.world // 2, plan.bounds
             mine = np.array([float(np.sum(out["rates"])) + float(np.sum(out["dy"])) if out is not None else 0.0])
-            sums = all_gather_rows(mine, np.ones(shard.world, dtype=int), group)
-            for b in range(shard.world // 2):
-                if bounds[b + 1] > bounds[b] and sums[b] != sums[b + shard.world // 2]:
+            sums = all_gather_rows(mine, np.ones(plan.world, dtype=int), self.group)
+            for b in range(half):
+                if bounds[b + 1] > bounds[b] and sums[b] != sums[b + half]:
                     raise RuntimeError("ranks %d and %d simulated different light curves for block %d (checksums %r, %r)"
-                                       % (b, b + shard.world // 2, b, sums[b], sums[b + shard.world // 2]))
-            half, sizes = shard.world // 2, np.diff(bounds)
-            counts = [np.concatenate([sizes, 0 * sizes]), np.concatenate([0 * sizes, sizes])]
-            if shard.world % 2:                                  # an odd rank out takes no part in the refits
-                counts = [np.append(c, 0) for c in counts]
-            best = [all_gather_rows(best[k] if k in models else np.empty(0), counts[k], group) for k in (0, 1)]
-    t_sim = lrt_statistic(best[0], best[1])
-    clock.append(time.perf_counter())
-    seconds = dict(zip(("observed_chains", "simulate", "refit_null", "refit_alt", "gather"), np.diff(clock))) \
-        if len(clock) == 6 else {"observed_chains": clock[1] - clock[0]}
-    return dict(T_obs=t_obs, T_sim=t_sim, p_value=lrt_pvalue(t_obs, t_sim), p_value_percentile=lrt_pvalue_percentile(t_obs, t_sim), null=null, alt=alt,
-                sim_null=fits[0], sim_alt=fits[1], lightcurves=out, seconds=seconds, reproducible=reproducible,
-                paired_launches=pair_stats,
-                split=None if not sharded else ("models" if len(models) < 2 else "lightcurves"))
-
-
-def _reproducible_is_free(split, nsims, walkers, world):
-    """protassov_test(sharded=True, reproducible=None): world-size-independent results by default exactly where they do not
-    cost a rank the time-parallel kernels (docstring there): the whole set is within ``REPRODUCIBLE_TP_ROWS`` rows per
-    half-step -- every block then runs the batch-independent time-parallel kernel --, or every rank's own share is beyond
-    the time-parallel range (8192 rows), where the sweep is what it would run anyway."""
-    by_model = _split_by_model(split, nsims, walkers, world)
-    rows_per_rank = -(-nsims // (world // 2 if by_model else world)) * (walkers // 2)
-    return bool(nsims * (walkers // 2) <= REPRODUCIBLE_TP_ROWS or rows_per_rank > 8192)
-
-
-def _split_by_model(split, nsims, walkers, world):
-    """How protassov_test(sharded=True) divides the refits: by light curve (every rank refits both models on its block)
-    or by model (half of the ranks each).  By light curve whenever a rank's half-step fits the pipelined sweep (at most
-    32 768 rows: one workgroup of 128 rows per compute unit): the two models' chains then run side by side on the rank
-    and its share of BASELINE configs[3] at 8 GPUs takes 3.8 s.  Beyond that a half-step of the
-    one-lane sweep costs one wave's latency over the N samples until a rank has about one wave per SIMD (65 536 rows),
-    so two half-steps of both models one after the other take twice as long as one half-step of one model on twice
-    the rows: by model, when asked for, or -- "auto" -- when the rows of a half-step per rank stay under that mark
-    either way (at 8 GPUs that share is ~4.2 s: the alternative's 64 000-row half-steps at 3.7 ms)."""
-    if split == "models":
-        if world < 2:
-            raise ValueError("split='models' needs at least two ranks")
-        return True
-    if split == "lightcurves" or world < 2:
-        return False
-    if split != "auto":
-        raise ValueError("split must be 'auto', 'lightcurves' or 'models'")
-    rows_by_lightcurve = -(-nsims // world) * (walkers // 2)
-    if rows_by_lightcurve <= 32768:
-        return False
-    rows_by_model = -(-nsims // (world // 2)) * (walkers // 2)
-    return rows_by_model <= 70000
+                                       % (b, b + half, b, sums[b], sums[b + half]))
+        return [all_gather_rows(best[k], plan.counts[k], self.group) for k in (0, 1)]
 
 
 def derive_posteriors_sharded(times, Y, DY, kernel, group=None, device=None, **kwargs):
@@ -775,7 +775,7 @@ def derive_posteriors_sharded(times, Y, DY, kernel, group=None, device=None, **k
     DY = np.atleast_2d(np.asarray(DY, dtype=np.float64))
     shard = LightcurveShard(Y.shape[0], group=group)
     if kwargs.get("seed") is not None:
-        kwargs["seed"] = int(kwargs["seed"]) + 7919 * shard.rank
+        kwargs["seed"] = int(kwargs["seed"]) + BLOCK_SEED_STRIDE * shard.rank
     local = None
     best = np.empty(0)
     if len(shard):

@@ -140,7 +140,8 @@ def rows():
          "O(N·J²) instead of celerite's dense N × N; new times O((N + 64 M)·J²) instead of its dense M × N "
          "(`profiles/predict_at_probe.txt`)"),
         ("f4 LRT / IO", "`stats.py`, `lightcurves.py`, `ppp.protassov_test`",
-         "`test_stats_io` (bit for bit vs reference `stats.py` outputs), `test_ppp_gpu`, `test_distributed`",
+         "`test_stats_io` (bit for bit vs reference `stats.py` outputs), `test_ppp_gpu`, `test_ppp_golden_gpu`, `test_ppp_trace_cpu`, "
+         "`test_distributed`",
          "configs[3] as a workflow: **%.1f s** (observed chains %.2f, simulation %.2f, refits %.1f + %.1f), p = %.6f, %s refit "
          "evaluations/s end to end" % (wf["whole_test_s"], wf["seconds"]["observed_chains"], wf["seconds"]["simulate"],
                                        wf["seconds"]["refit_null"], wf["seconds"]["refit_alt"], wf["p_value"],

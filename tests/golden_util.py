@@ -124,6 +124,22 @@ def dispatch_case(eng, case):
         eng.set_sort(2)
 
 
+def protassov_problem():
+    """The small Protassov test that tests/test_distributed.py's workers and tests/golden/ppp_end_to_end.json run:
+    (light curve, null kernel, alternative kernel, the arguments every mode shares).  N = 400 is long enough for the
+    time-parallel kernels to be an option."""
+    from mind_the_gaps_amd import synthetic as synth
+    from mind_the_gaps_amd.lightcurves import GappyLightcurve
+    from mind_the_gaps_amd.models import DampedRandomWalk, Lorentzian
+    th = synth.truth(synth.ALT_MODEL)
+    t, y, dy = synth.make_lightcurves(400, 1, seed=43)
+    lc = GappyLightcurve(t, y[0] + 50.0, dy[0], exposures=0.5 * np.diff(t).min())
+    null = DampedRandomWalk(th[0], th[1], bounds=[(-10, 50), (-10, 10)])
+    alt = DampedRandomWalk(th[0], th[1], bounds=[(-10, 50), (-10, 10)]) + Lorentzian(
+        th[5], th[6], th[7], bounds=[(-10, 50), (-10, 10), (-10, 10)])
+    return lc, null, alt, dict(nsims=5, walkers=16, max_steps=60, sim_steps=40, seed=11)
+
+
 def new_times(t, seed):
     """predict_golden.npz's 48 new times: 24 between samples, 12 on samples, 6 before the first and 6 after the last"""
     rng = np.random.default_rng(seed)

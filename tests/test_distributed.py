@@ -368,23 +368,17 @@ def _protassov_worker(rank, world, port, out_dir, split="lightcurves"):
     guard = _watchdog(out_dir, "ppp%d_%d" % (world, rank))
     import warnings
     import torch.distributed as dist
-    from mind_the_gaps_amd.lightcurves import GappyLightcurve
-    from mind_the_gaps_amd.models import DampedRandomWalk, Lorentzian
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from golden_util import protassov_problem
     from mind_the_gaps_amd.ppp import protassov_test
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     if world > 1:
         dist.init_process_group("gloo", rank=rank, world_size=world)   # both ranks share the one GPU of the box
-    th = synth.truth(synth.ALT_MODEL)
-    t, y, dy = synth.make_lightcurves(400, 1, seed=43)     # (long enough for the time-parallel kernels to be an option)
-    lc = GappyLightcurve(t, y[0] + 50.0, dy[0], exposures=0.5 * np.diff(t).min())
-    null = DampedRandomWalk(th[0], th[1], bounds=[(-10, 50), (-10, 10)])
-    alt = DampedRandomWalk(th[0], th[1], bounds=[(-10, 50), (-10, 10)]) + Lorentzian(
-        th[5], th[6], th[7], bounds=[(-10, 50), (-10, 10), (-10, 10)])
+    lc, null, alt, sizes = protassov_problem()     # nsims=5, walkers=16, max_steps=60, sim_steps=40, seed=11
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        res = protassov_test(lc, null, alt, nsims=5, walkers=16, max_steps=60, sim_steps=40, seed=11, sharded=world > 1,
-                             split=split, reproducible=True)
+        res = protassov_test(lc, null, alt, sharded=world > 1, split=split, reproducible=True, **sizes)
     n_local = 0 if res["lightcurves"] is None else len(res["lightcurves"]["rates"])
     both = res["sim_null"] is not None and res["sim_alt"] is not None
     local = (-2.0 * (res["sim_null"].max_loglikelihood - res["sim_alt"].max_loglikelihood)) if both else np.empty(0)
@@ -446,19 +440,14 @@ def _protassov_observed_failure_worker(rank, world, port, out_dir):
     guard = _watchdog(out_dir, "pof%d" % rank)
     import warnings
     import torch.distributed as dist
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from golden_util import protassov_problem
     from mind_the_gaps_amd import gpmodelling
-    from mind_the_gaps_amd.lightcurves import GappyLightcurve
-    from mind_the_gaps_amd.models import DampedRandomWalk, Lorentzian
     from mind_the_gaps_amd.ppp import protassov_test
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    th = synth.truth(synth.ALT_MODEL)
-    t, y, dy = synth.make_lightcurves(400, 1, seed=43)
-    lc = GappyLightcurve(t, y[0] + 50.0, dy[0], exposures=0.5 * np.diff(t).min())
-    null = DampedRandomWalk(th[0], th[1], bounds=[(-10, 50), (-10, 10)])
-    alt = DampedRandomWalk(th[0], th[1], bounds=[(-10, 50), (-10, 10)]) + Lorentzian(
-        th[5], th[6], th[7], bounds=[(-10, 50), (-10, 10), (-10, 10)])
+    lc, null, alt, _ = protassov_problem()
     if rank == 1:       # the alternative model's observed chain dies on the rank that runs it
 
         def broken(self, *a, **k):
@@ -489,6 +478,42 @@ def test_protassov_observed_chain_failure_reaches_every_rank(tmp_path):
     world = 3
     _spawn(_protassov_observed_failure_worker, (world, _free_port(), str(tmp_path)), world, tmp_path)
     assert [open(tmp_path / ("pof%d.txt" % r)).read() for r in range(world)] == ["peer error", "own error", "peer error"]
+
+
+def _protassov_trace_worker(rank, world, port, out_dir):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    guard = _watchdog(out_dir, "trace%d_%d" % (world, rank))
+    import faulthandler
+    import ppp_fakes
+    ppp_fakes.sharded_worker(rank, world, port, out_dir)
+    faulthandler.cancel_dump_traceback_later()
+    guard.close()
+
+
+@pytest.mark.timeout(400)
+@pytest.mark.parametrize("world", [2, 3])
+def test_protassov_test_sharded_host_logic_is_what_it_was(tmp_path, world):
+    """ppp.protassov_test(sharded=True) on 2 and 3 gloo ranks with the GPU work replaced by the recording stand-ins of
+    tests/ppp_fakes.py: for every split, nsims 5 (blocks that start and end inside a pair) and 1 (ranks without a block),
+    reproducible on / off / default, the observed chains split or not, a refit and an observed chain that fail on rank 1
+    -- every rank makes the calls, with the arguments, seeds and rows, and returns the values that the function made
+    before it was cut into a plan and stages (tests/golden/ppp_trace.json), value for value."""
+    import json
+    import ppp_fakes
+    golden = ppp_fakes.load_golden(os.path.join(ROOT, "tests", "golden", "ppp_trace.json"))["world%d" % world]
+    _spawn(_protassov_trace_worker, (world, _free_port(), str(tmp_path)), world, tmp_path)
+    for rank in range(world):
+        got = json.load(open(tmp_path / ("trace%d_%d.json" % (world, rank))))
+        assert sorted(got) == sorted(ppp_fakes.sharded_cases(world)) == sorted(golden[rank])
+        for name in got:
+            ppp_fakes.assert_same_records(got[name], golden[rank][name], "%s, rank %d of %d" % (name, rank, world))
+    # what the cases pin, read off the golden records: the failures reach every rank, each with the error that is its own
+    assert [g["refit_fails_on_rank_1"]["raised"][0] for g in golden] == ["RuntimeError", "ZeroDivisionError", "RuntimeError"][:world]
+    assert golden[0]["refit_fails_on_rank_1"]["raised"][1] == "protassov_test: the refits failed on rank(s) [1]"
+    assert [g["observed_chain_fails_on_rank_1"]["raised"][0] for g in golden] == ["RuntimeError", "ArithmeticError", "RuntimeError"][:world]
+    assert golden[0]["observed_chain_fails_on_rank_1"]["raised"][1] == "protassov_test: the observed light curve's chain failed on rank(s) [1]"
+    assert [g["models_n1_repTrue_obsTrue"]["seconds"] == ["observed_chains"] for g in golden] == [False, False, True][:world]
 
 
 # ---- the device-resident sampler, walker-sharded (mtg_ensemble_shard_*) -------------------------------------
