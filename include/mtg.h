@@ -532,6 +532,26 @@ MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int3
                         const double *normals /* [B][N] or NULL: Philox */, double *y /* [B][N] */, int32_t *status);
 
 /*
+ * celerite.GP.grad_log_likelihood for B parameter vectors at once: out[b] = lnL(theta[b]) of light curve lc_index[b]
+ * (NULL = all 0) and grad[b][p] = d lnL / d theta[b][p] for the model's P free parameters, the derivative of the
+ * float64 recurrence itself (no finite differences).  Against a quad-precision truth every component is within
+ * 70 sqrt(N) u G_p (u = 2^-53, G_p the sum of the magnitudes of the terms that make the component up) on ordinary rows;
+ * where the float64 formulation is itself ill-conditioned the gradient is, like lnL, as good as that formulation and no
+ * better: an SHO term within 1e-3 of Q = 1/2 in ln Q (3e4 in those units: 1e-8 relative in the ln Q component),
+ * amplitudes of e^10 to e^20 over the noise with c dx down to 1e-9 (1e6: 1e-8 relative), and frequencies beyond 1e4 rad
+ * per step, where rounding d to a double already moves the phases (tests/test_loglike_grad_gpu.py).  One lane per (row, free parameter) sweeps the factorisation together with its directional
+ * derivative, state in registers: O(N J^2) per lane, no workspace that grows with N; the coefficient tangents
+ * ([coefficient slots][B P] doubles) belong to the context and grow on demand.  The box prior is flat, so add_prior
+ * only decides which rows are rejected: a row outside the prior gets MTG_ST_PRIOR, out = -inf and a gradient of
+ * NaN; a row with a non-positive pivot MTG_ST_NOTPD, -inf and NaN.  A row's values do not depend on the batch it
+ * travels in.  An SHO term is differentiated on the side of Q = 1/2 the row is on.  Models of rank
+ * J = n_real + 2 n_complex > 6 return MTG_E_UNSUPPORTED (the tangent state no longer fits the register file);
+ * mtg_last_solver names the kernel, "mtg_loglike_grad_kernel<J>".
+ */
+MTG_API int mtg_loglike_grad(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int add_prior,
+                             double *out /* [B] */, double *grad /* [B][P] */, int32_t *status);
+
+/*
  * Accuracy probe of the device elementary functions the recurrence uses
  * (tests only): exp_neg[i] = exp(-x[i]), sin/cos(x[i]), rcp_x[i] = 1 / x[i] for
  * n host values x >= 0.

@@ -153,6 +153,7 @@ struct mtg_ctx {
                       // sampler alternates: the proposals of a half-step are expanded while the other bank is cleared)
     // staging for the host-pointer entry points
     DevBuf theta, lc, out, status;
+    DevBuf grad_dcoef, grad, grad_verdict;  // mtg_loglike_grad: coefficient tangents [nslots][B P], the gradient [B][P], the expansion's status [B]; grown on demand
 
     // small batches: one wave per evaluation, parallel in time (0 never, 1 whenever compiled, 2 auto)
     int tp_mode = 2;   // (3: as 1, but the one-wave-per-evaluation kernel only -- results independent of the batch size)
@@ -471,7 +472,7 @@ int check_lc_index(mtg_ctx *ctx, int64_t B, const int32_t *lc_index)
     return MTG_OK;
 }
 
-// The prologue of the per-row entries (`who`: mtg_predict, mtg_predict_at, mtg_gp_draw, mtg_apply_inverse): workspace
+// The prologue of the per-row entries (`who`: mtg_predict, mtg_predict_at, mtg_gp_draw, mtg_loglike_grad, mtg_apply_inverse): workspace
 // and staging reserved for B rows, theta and lc_index uploaded, theta expanded on stream s -- the prior's verdict in
 // ctx->status, the structure of every row in ctx->sig -- and the head of the kernels' arguments filled for the whole
 // batch.  (ctx->sig, like ctx->coef, is rewritten by every expansion and read by nothing before the next one.)
@@ -2469,6 +2470,51 @@ MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int3
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     else (void)hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_gp_draw: %s", hipGetErrorString(e));
+    return MTG_OK;
+}
+
+MTG_API int mtg_loglike_grad(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int add_prior,
+                             double *out, double *grad, int32_t *status)
+{
+    int rc = check_ready(ctx, true);
+    if (rc) return rc;
+    const int P = ctx->model.P;
+    if (B <= 0 || !theta || !out || !grad || !status) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: bad arguments");
+    if (P <= 0) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: the model has no free parameter");
+    rc = check_lc_index(ctx, B, lc_index);
+    if (rc) return rc;
+    const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
+    if (J > MTG_GRAD_MAX_J)
+        return fail(ctx, MTG_E_UNSUPPORTED, "mtg_loglike_grad: rank %d > %d (the tangent sweep keeps its state in registers)", J,
+                    MTG_GRAD_MAX_J);
+    if (B * P > ((int64_t)1 << 36)) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: B * P = %lld is too large", (long long)(B * P));
+    rc = use_device(ctx);
+    if (rc) return rc;
+    CTX_STREAM(ctx, s);
+    MtgGradArgs qa;
+    rc = stage_rows(ctx, "mtg_loglike_grad", B, theta, lc_index, add_prior ? 1 : 0, s, qa);
+    if (rc) return rc;
+    const int64_t lanes = B * P, dstride = (lanes + 63) / 64 * 64;
+    hipError_t e = ctx->grad_dcoef.reserve_n<double>(dstride * qa.lay.nslots());
+    if (e == hipSuccess) e = ctx->grad.reserve_n<double>(lanes);
+    if (e == hipSuccess) e = ctx->grad_verdict.reserve_n<int32_t>(B);
+    if (e == hipSuccess) {
+        qa.model = ctx->model; qa.theta = ctx->theta.as<double>(); qa.P = P;
+        qa.dcoef = ctx->grad_dcoef.as<double>(); qa.dstride = dstride;
+        qa.out = ctx->out.as<double>(); qa.grad = ctx->grad.as<double>(); qa.verdict = ctx->grad_verdict.as<int32_t>();
+        e = hipEventRecord(ctx->ev0, s);     // mtg_last_kernel_ms: the coefficient tangents and the sweep (not stage_rows' expansion)
+        if (e == hipSuccess && !mtg_launch_loglike_grad(qa, s)) e = hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, s);
+        if (e == hipSuccess) ctx->timed = true;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, ctx->out.p, (size_t)B * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(grad, ctx->grad.p, (size_t)lanes * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    else (void)hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_loglike_grad: %s", hipGetErrorString(e));
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_loglike_grad_kernel<%d>", J);
     return MTG_OK;
 }
 

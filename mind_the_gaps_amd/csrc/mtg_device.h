@@ -184,8 +184,28 @@ struct MtgGpDrawArgs : MtgRowArgs {     // of yv only the sigma^2 half is read
 };
 // one slab of draws; 0 = rank outside 0 .. MTG_MAX_J
 int mtg_launch_gp_draw(const MtgGpDrawArgs &, hipStream_t);
+
+// highest rank the gradient's tangent sweep is compiled for (mtg_loglike_grad.hip): primal and tangent state of a
+// lane live in registers, and beyond this rank they no longer fit without scratch
+#ifndef MTG_GRAD_MAX_J
+#define MTG_GRAD_MAX_J 6
+#endif
+
+struct MtgGradArgs : MtgRowArgs {       // the whole batch in one launch: row0 = 0; lane l = e P + p
+    MtgModel model;         // the coefficient tangents are expanded from it (mtg_prepare_tangent.h)
+    const double *theta;    // [B][P]
+    int P;                  // free parameters (>= 1)
+    double *dcoef;          // [nslots][dstride]: d coef[slot] / d theta[p] of row e at column e P + p
+    int64_t dstride;
+    double *out;            // [B] lnL (written by the lane p = 0 of a row; -inf from the expansion for a rejected row)
+    double *grad;           // [B][P]
+    int32_t *verdict;       // [B] the expansion's status, copied by the tangent kernel: what the sweep reads (it writes `status`)
+};
+// coefficient tangents, then the tangent sweep; 0 = rank outside 0 .. MTG_GRAD_MAX_J
+int mtg_launch_loglike_grad(const MtgGradArgs &, hipStream_t);
 static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivially_copyable<MtgPredictAtArgs>::value &&
-              std::is_trivially_copyable<MtgGpDrawArgs>::value, "passed by value as kernel arguments");
+              std::is_trivially_copyable<MtgGpDrawArgs>::value && std::is_trivially_copyable<MtgGradArgs>::value,
+              "passed by value as kernel arguments");
 
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).

@@ -36,7 +36,7 @@ EXPORTS = (
     "mtg_chain_autocorr", "mtg_fft_warmup", "mtg_simulate_plan", "mtg_ensemble_restore", "mtg_set_sort", "mtg_set_pipeline", "mtg_set_stream_base", "mtg_set_speculation", "mtg_last_solver", "mtg_pair_contexts", "mtg_unpair_contexts", "mtg_pair_stats", "mtg_set_simulate_pairs", "mtg_set_simulate_transform", "mtg_set_simulate_pdf", "mtg_set_simulate_kraft", "mtg_set_simulate_pdf_draws", "mtg_simulate_pdf_report", "mtg_set_pair_patience", "mtg_chain_autocorr_plans_built",
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
-    "mtg_predict_at", "mtg_gp_draw",
+    "mtg_predict_at", "mtg_gp_draw", "mtg_loglike_grad",
 )
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
@@ -315,6 +315,8 @@ def load_library():
     lib.mtg_predict_at.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, _dp, _dp, _ip]
     lib.mtg_gp_draw.restype = c_int
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
+    lib.mtg_loglike_grad.restype = c_int
+    lib.mtg_loglike_grad.argtypes = [c_vp, c_i64, _dp, _ip, c_int, _dp, _dp, _ip]
     lib.mtg_math_probe.restype = c_int
     lib.mtg_math_probe.argtypes = [c_vp, c_i64, _dp, _dp, _dp, _dp, _dp]
     lib.mtg_structure_supported.restype = c_int
@@ -776,6 +778,26 @@ class Engine:
                                           _ptr(y), _iptr(status)))
         return y, status
 
+    def loglike_grad(self, theta, lc_index=None, add_prior=False):
+        """theta [B][P] -> (lnL[B], grad[B][P], status[B]): the log-likelihood and its analytic gradient by the free
+        parameters from one launch (mtg_loglike_grad).  The box prior is flat: ``add_prior`` only decides which rows are
+        rejected.  A rejected or not positive-definite row has -inf and a gradient of NaN.  ``EngineError`` with
+        ``code == E_UNSUPPORTED`` for a model whose rank the tangent sweep is not compiled for."""
+        theta = np.atleast_2d(_f64(theta))
+        B = theta.shape[0]
+        if self.P is None:
+            raise EngineError(E_STATE, "set_model has not been called")
+        if theta.shape[1] != self.P:
+            raise ValueError("theta has %d columns, the model has %d free parameters" % (theta.shape[1], self.P))
+        lc = None if lc_index is None else np.ascontiguousarray(lc_index, dtype=np.int32)
+        if lc is not None and lc.shape != (B,):
+            raise ValueError("lc_index must have one entry per theta row")
+        out, grad = np.empty(B), np.empty((B, self.P))
+        status = np.empty(B, dtype=np.int32)
+        self._check(self._lib.mtg_loglike_grad(self._ctx, B, _ptr(theta), _iptr(lc), int(bool(add_prior)), _ptr(out),
+                                               _ptr(grad), _iptr(status)))
+        return out, grad, status
+
     def apply_inverse(self, theta, rhs, lc_index=0):
         """K^-1 rhs for rhs[N] or rhs[N][M] at parameter vector ``theta`` -> (x, status)."""
         rhs = _f64(rhs)
@@ -918,6 +940,6 @@ class Engine:
 
 for _name in ("set_lightcurves", "set_lightcurves_device", "set_model", "loglike", "loglike_device", "loglike_coeffs",
               "ensemble_init", "ensemble_run", "ensemble_restore", "ensemble_state", "chain_autocorr", "simulate_tk95",
-              "tk95_observe_series", "predict", "predict_at", "gp_draw", "apply_inverse", "math_probe"):
+              "tk95_observe_series", "predict", "predict_at", "gp_draw", "loglike_grad", "apply_inverse", "math_probe"):
     setattr(Engine, _name, _one_thread_at_a_time(getattr(Engine, _name)))
 del _name

@@ -295,6 +295,25 @@ class GP(ModelSet):
             raise LinAlgError("failed to factorize or solve matrix")
         return float(out[0])
 
+    def grad_log_likelihood(self, y, quiet=False):
+        """``(lnL, d lnL / d theta)`` of the current parameter vector, the gradient by the free parameters in
+        ``get_parameter_vector``'s order (celerite.GP.grad_log_likelihood): analytic, from one launch of the device's
+        tangent sweep (``Engine.loglike_grad``).  A covariance that is not positive definite raises ``LinAlgError``, or
+        with ``quiet`` returns ``(-inf, zeros)`` as celerite does."""
+        eng, model = self._bound_engine(y)
+        out, grad, status = eng.loglike_grad(model.full[model.free_index][None, :], add_prior=False)
+        if status[0] == _engine.ST_NOTPD:
+            if quiet:
+                return -np.inf, np.zeros(len(model.free_index))
+            raise LinAlgError("failed to factorize or solve matrix")
+        return float(out[0]), grad[0]
+
+    def log_probability_grad_batch(self, theta, y, add_prior=True):
+        """lnP and its gradient for B free-parameter vectors at once -> (lnP[B], grad[B][P], status[B]); the box prior
+        is flat, so it only rejects rows (-inf, a gradient of NaN).  Pure in theta."""
+        eng, _ = self._bound_engine(y)
+        return eng.loglike_grad(np.atleast_2d(np.asarray(theta, dtype=np.float64)), add_prior=add_prior)
+
     def log_probability_batch(self, theta, y, add_prior=True):
         """lnP of B free-parameter vectors at once -> (lnP[B], status[B]); pure in theta."""
         ev = self._ensure_evaluator(y)

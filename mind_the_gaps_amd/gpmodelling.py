@@ -151,16 +151,61 @@ class GPModelling:
             grad = np.where((dx != 0.0) & np.isfinite(vals[1:]), (vals[1:] - f0) / dx, 0.0)
         return f0, grad
 
-    def fit(self, initial_params=None):
+    def _neg_log_like_and_grad_analytic(self, x, lower, upper):
+        """-lnL and its analytic gradient from one launch of the device's tangent sweep (``Engine.loglike_grad``);
+        a point that cannot be factorised is treated as in ``_neg_log_like_and_grad``."""
+        x = np.asarray(x, dtype=np.float64)
+        out, grad, status = self.gp.log_probability_grad_batch(x[None, :], self._y, add_prior=False)
+        if status[0] != _engine.ST_OK or not np.isfinite(out[0]):
+            if self._fit_evaluations == 0 and not self._quiet:
+                raise LinAlgError("failed to factorize or solve matrix")
+            self._fit_evaluations += 1
+            return 1e300, np.zeros_like(x)
+        self._fit_evaluations += 1
+        return -float(out[0]), -grad[0]
+
+    def _analytic_gradient_usable(self, x):
+        """None when ``fit(gradient="analytic")`` can run on this model, else why not"""
+        model = self.gp._device_model()
+        if not model.device_terms:
+            return "a term has no device expansion"
+        if model.mean_kind is None:
+            return "the mean model is evaluated on the host"
+        try:
+            self.gp.log_probability_grad_batch(np.asarray(x, dtype=np.float64)[None, :], self._y, add_prior=False)
+        except _engine.EngineError as exc:
+            if exc.code != _engine.E_UNSUPPORTED:
+                raise
+            return "the model's rank is beyond the device's tangent sweep"
+        return None
+
+    def fit(self, initial_params=None, gradient="fd"):
         """L-BFGS-B minimisation of the negative log-likelihood within the
-        parameter bounds (gpmodelling.py:172-194).  Returns scipy's OptimizeResult."""
+        parameter bounds (gpmodelling.py:172-194).  Returns scipy's OptimizeResult.
+
+        ``gradient`` (new, optional): "fd", the default, gives L-BFGS-B forward differences of step 1e-8 from one
+        batched launch; "analytic" the exact gradient from the device's tangent sweep (one launch of one lane per
+        free parameter): free of the differences' rounding noise, u |lnL| / 1e-8, but 50 to 740 times their kernel
+        time (profiles/grad_probe.txt).  It does not by itself end the search higher: at N = 1e6 scipy's default
+        ``ftol`` (a relative reduction of 2.2e-9, 8e-3 in -lnL there) stops both modes first, the analytic run 3.6
+        above the other in -lnL.  A model the sweep does not cover (a host-evaluated term or mean, a rank
+        it is not compiled for) warns and uses "fd"."""
+        if gradient not in ("fd", "analytic"):
+            raise ValueError("gradient must be 'fd' or 'analytic', not %r" % (gradient,))
         if initial_params is None:
             initial_params = self.initial_params
+        fun = self._neg_log_like_and_grad
+        if gradient == "analytic":
+            why_not = self._analytic_gradient_usable(initial_params)
+            if why_not is None:
+                fun = self._neg_log_like_and_grad_analytic
+            else:
+                warnings.warn("fit(gradient='analytic'): %s; using finite differences" % why_not)
         bounds = self.gp.get_parameter_bounds()
         lower = np.array([-np.inf if b[0] is None else b[0] for b in bounds], dtype=np.float64)
         upper = np.array([np.inf if b[1] is None else b[1] for b in bounds], dtype=np.float64)
         self._fit_evaluations = 0
-        solution = minimize(self._neg_log_like_and_grad, initial_params, args=(lower, upper), jac=True,
+        solution = minimize(fun, initial_params, args=(lower, upper), jac=True,
                             method="L-BFGS-B", bounds=bounds)
         if not np.isfinite(solution.fun) or solution.fun >= 1e300:   # quiet mode: say so instead of "success"
             solution.success = False

@@ -150,7 +150,7 @@ class EnsembleBatchSampler:
         return self.n_accepted / float(max(self.iteration, 1))
 
 
-def batched_minimize(fun, x0, lower, upper, max_iter=60, history=8, fd_step=1e-6, gtol=1e-5, ftol=1e-10):
+def batched_minimize(fun, x0, lower, upper, max_iter=60, history=8, fd_step=1e-6, gtol=1e-5, ftol=1e-10, value_and_grad=None):
     """Projected L-BFGS for L independent box-constrained problems in lock-step.
 
     ``fun(X[M, P], lc[M]) -> f[M]``; ``x0`` [L, P]; ``lower``/``upper`` [P].  Each
@@ -159,18 +159,23 @@ def batched_minimize(fun, x0, lower, upper, max_iter=60, history=8, fd_step=1e-6
     ``scipy.optimize.minimize(method="L-BFGS-B")`` in GPModelling.fit (gpmodelling.py:192)
     for the lock-step driver: a good starting point for the walkers, not a bit-identical
     optimiser path.  Returns (x[L, P], f[L], iterations).
+
+    ``value_and_grad``: an optional callable ``(x[L, P]) -> (f[L], g[L, P])``, row l on problem l, used in place of
+    the forward differences (an analytic gradient: one launch of L rows); ``fun`` then serves the line search alone.
     """
     x = np.clip(np.array(x0, dtype=np.float64), lower, upper)
     L, P = x.shape
     lcs = np.arange(L, dtype=np.int32)
 
-    def value_and_grad(x):
+    def forward_differences(x):
         h = np.where(x + fd_step > upper, -fd_step, fd_step)            # step inward at the upper bound
         pts = np.repeat(x[:, None, :], P + 1, axis=1)                   # [L, P+1, P]
         pts[:, 1:, :] += np.eye(P)[None] * h[:, None, :]
         vals = fun(pts.reshape(-1, P), np.repeat(lcs, P + 1)).reshape(L, P + 1)
         return vals[:, 0], (vals[:, 1:] - vals[:, :1]) / h
 
+    if value_and_grad is None:
+        value_and_grad = forward_differences
     f, g = value_and_grad(x)
     S, Y = [], []
     active = np.ones(L, dtype=bool)
@@ -310,7 +315,7 @@ class _DeviceBatch:
 def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit=True, seed=None,
                             device=0, store_chain=True, initial_params=None, quiet=False,
                             evaluate=None, device_sampler=True, own_engine=False, index_base=None, before_sampling=None,
-                            total_lightcurves=None):
+                            total_lightcurves=None, fit_gradient="fd"):
     """GPModelling(lc, kernel).derive_posteriors(...) for L light curves at once.
 
     times [N] (shared sampling, gpmodelling.py:538); Y, DY [L, N]; ``kernel`` a
@@ -338,7 +343,15 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
     block, whatever the split, is inside the range where the time-parallel kernel is the fast one (0.35-3.6 ms against
     2.4-3.4 ms for the sweep at N = 1e4); unknown or larger, the sweep.  Models of rank above 6 keep the sweep in
     either mode (their time-parallel path sizes its chunks by the batch).
+
+    ``fit_gradient``: "fd" (default), the starting fit's forward differences; "analytic", the exact gradient of every
+    light curve's -lnL from one launch of the evaluator's engine (``Engine.loglike_grad``; needs this call's own
+    evaluator, ``evaluate=None``).  A model of a rank the tangent sweep is not compiled for warns and uses "fd".
     """
+    if fit_gradient not in ("fd", "analytic"):
+        raise ValueError("fit_gradient must be 'fd' or 'analytic', not %r" % (fit_gradient,))
+    if fit_gradient == "analytic" and evaluate is not None:
+        raise ValueError("fit_gradient='analytic' runs on this call's own evaluator: evaluate must be None")
     Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
     DY = np.atleast_2d(np.asarray(DY, dtype=np.float64))
     L = Y.shape[0]
@@ -361,6 +374,12 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
             raise LinAlgError("failed to factorize or solve matrix")
         return out
 
+    def analytic(x):            # -lnL and its gradient, row l on light curve l
+        out, grad, status = ev._bind(model).loglike_grad(x, np.arange(len(x), dtype=np.int32), add_prior=False)
+        if not quiet and np.any(status == _engine.ST_NOTPD):
+            raise LinAlgError("failed to factorize or solve matrix")
+        return -out, -grad
+
     P = len(model.free_index)
     lower, upper = model.bounds[model.free_index, 0], model.bounds[model.free_index, 1]
     start = model.full[model.free_index] if initial_params is None else np.asarray(initial_params, float)
@@ -380,7 +399,17 @@ def derive_posteriors_batch(times, Y, DY, kernel, walkers=12, max_steps=500, fit
     try:
         if fit:
             kernels(3)
-            fit_x, fit_f, _ = batched_minimize(lambda x, lc: -checked(x, lc, False), centers, lower, upper)
+            hook = analytic if fit_gradient == "analytic" else None
+            if hook is not None:
+                try:
+                    hook(centers)       # a model the tangent sweep is not compiled for (rank above 6) says so here
+                except _engine.EngineError as exc:
+                    if exc.code != _engine.E_UNSUPPORTED:
+                        raise
+                    warnings.warn("derive_posteriors_batch(fit_gradient='analytic'): the model's rank is beyond the device's "
+                                  "tangent sweep; using finite differences")
+                    hook = None
+            fit_x, fit_f, _ = batched_minimize(lambda x, lc: -checked(x, lc, False), centers, lower, upper, value_and_grad=hook)
             centers, fit_f = fit_x, -fit_f
             timer.mark("fit")
         kernels(chain_mode)
