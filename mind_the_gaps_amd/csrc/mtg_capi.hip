@@ -161,30 +161,61 @@ struct mtg_ctx {
     int pipe_mode = 2;  // two-wave pipeline of the serial sweep (mtg_set_pipeline): 0 never, 1 whenever compiled, 2 auto
     int cus = 0;        // compute units of the device
 
-    // device-resident ensembles (mtg_ensemble_*)
-    int64_t ens_E = 0;
-    int ens_W = 0, ens_P = 0;
-    uint64_t ens_seed = 0;
     int64_t stream_base = 0;      // mtg_set_stream_base: global index of the context's first ensemble / simulated series
-    int64_t ens_base = 0;         // ... as it was when the resident ensembles were made
-    uint32_t ens_iteration = 0;
-    int64_t ens_L = 0, ens_N = 0;  // shape of the resident set the ensembles index into
-    DevBuf ens_coords, ens_lnp, ens_perm, ens_q, ens_factor, ens_new, ens_st, ens_lc_full, ens_lc_half,
-        ens_naccept, ens_best_lnp, ens_best_coords, ens_notpd, ens_chain, ens_lnp_chain;
-    DevBuf ens_lc_spec;                 // light-curve index of the 3 E W/2 rows of a speculative iteration
-    DevBuf ens_perm_all;                // the splits of a whole speculative run, made before it ([steps][E][W])
-    // walker sharding (mtg_ensemble_shard_*): this rank evaluates rows [shard_lo, shard_hi) of every
-    // half-step's proposals; the exchange brings everybody's log-probabilities before the accept step
-    int shard_kind = 0;  // 0 none, 1 RCCL all-gather on the stream, 2 host callback
-    std::atomic<int> shard_generation{0};   // bumped by every (un)sharding: a communicator that comes up late is dropped
-    int shard_rank = 0, shard_world = 1;
-    int64_t shard_chunk = 0, shard_lo = 0, shard_hi = 0;
-    void *shard_comm = nullptr;         // ncclComm_t
-    mtg_exchange_fn shard_fn = nullptr;
-    void *shard_user = nullptr;
-    double *shard_h_lnp = nullptr;      // pinned staging of the host exchange
-    int32_t *shard_h_st = nullptr;
-    int64_t shard_h_rows = 0;
+    // device-resident ensembles (mtg_ensemble_*)
+    struct Ensembles {
+        int64_t E = 0, L = 0, N = 0;  // ensembles; shape of the resident set they index into
+        int W = 0, P = 0;
+        uint64_t seed = 0;
+        int64_t base = 0;             // stream_base as it was when the ensembles were made
+        uint32_t iteration = 0;
+        DevBuf coords, lnp, perm, naccept, best_lnp, best_coords, notpd;   // the state: [E][W][P], [E][W] ..., one counter
+        // the rows of a solve -- proposals, their factors, log-probabilities, statuses, light curves --: room for the
+        // 3 E W/2 of a speculative iteration, a half-step uses the first E W/2; lc_full: the light curve of every walker
+        DevBuf q, factor, new_lnp, st, lc_spec, lc_full;
+        DevBuf chain, lnp_chain;      // a run's [steps][E][W][P] and [steps][E][W]
+        DevBuf perm_all;              // the splits of a whole speculative run, made before it ([steps][E][W])
+        // the bytes each buffer holds for E ensembles of W walkers in P dimensions
+        struct Sizes { size_t coords, lnp, perm, naccept, best_lnp, best_coords, notpd, q, factor, new_lnp, st, lc_spec, lc_full; };
+        static Sizes sizes(int64_t E, int W, int P)
+        {
+            const size_t EW = (size_t)E * W, EH = (size_t)E * (W / 2), d = sizeof(double), i = sizeof(int32_t);
+            Sizes z;
+            z.coords = EW * P * d; z.lnp = EW * d; z.best_lnp = (size_t)E * d; z.best_coords = (size_t)E * P * d;
+            z.perm = z.naccept = z.lc_full = EW * i; z.notpd = i;
+            z.q = 3 * EH * P * d; z.factor = 2 * EH * d; z.new_lnp = 3 * EH * d; z.st = z.lc_spec = 3 * EH * i;
+            return z;
+        }
+        Sizes sizes() const { return sizes(E, W, P); }
+        hipError_t reserve(const Sizes &z)
+        {
+            const struct { DevBuf &buf; size_t bytes; } rooms[] = {
+                {coords, z.coords}, {lnp, z.lnp}, {perm, z.perm}, {q, z.q}, {factor, z.factor}, {new_lnp, z.new_lnp}, {st, z.st},
+                {lc_spec, z.lc_spec}, {lc_full, z.lc_full}, {naccept, z.naccept}, {best_lnp, z.best_lnp},
+                {best_coords, z.best_coords}, {notpd, z.notpd}};
+            hipError_t e = hipSuccess;
+            for (const auto &r : rooms) e = e == hipSuccess ? r.buf.reserve(r.bytes) : e;
+            return e;
+        }
+
+        // walker sharding (mtg_ensemble_shard_*): this rank evaluates rows [lo, hi) of every half-step's proposals; the
+        // exchange brings everybody's log-probabilities before the accept step.  What shard_release resets; the generation
+        // counter and the profile's events after it stay
+        struct Shard {
+            int kind = 0;  // 0 none, 1 RCCL all-gather on the stream, 2 host callback
+            int rank = 0, world = 1;
+            int64_t chunk = 0, lo = 0, hi = 0;
+            void *comm = nullptr;         // ncclComm_t
+            mtg_exchange_fn fn = nullptr;
+            void *user = nullptr;
+            double *h_lnp = nullptr;      // pinned staging of the host exchange: h_rows rows
+            int32_t *h_st = nullptr;
+            int64_t h_rows = 0;
+        } shard;
+        std::atomic<int> shard_generation{0};   // bumped by every (un)sharding: a communicator that comes up late is dropped
+        std::vector<hipEvent_t> shard_ev;       // mtg_ensemble_shard_profile: event pairs around the first exchanges of a run
+        int shard_ev_cap = 0, shard_ev_n = 0;
+    } ens;
     int64_t live_rows = 0;              // rows the next solve really evaluates (0: all) -- kernel choice only
     bool no_prior_batch = false;        // the batch being solved was expanded WITHOUT the prior (run_model_batch): kernel choice only
 
@@ -265,10 +296,6 @@ struct mtg_ctx {
     bool own_dirty = false;         // the context's stream has had work since the last foreign call waited for it
     hipStream_t last_foreign = nullptr;
 
-    // timing of the walker-sharded exchange (mtg_ensemble_shard_profile): event pairs around the first exchanges of a run
-    std::vector<hipEvent_t> shard_ev;
-    int shard_ev_cap = 0, shard_ev_n = 0;
-
     // mtg_pair_contexts: the partner whose pipelined half-steps share a launch with this context's (MtgPair below)
     // Shared ownership: a thread inside pair_launch holds a reference of its own, so that mtg_unpair_contexts /
     // mtg_destroy on the partner's thread cannot free the rendezvous under it.  Read and written with
@@ -324,7 +351,6 @@ inline int *bank_lists(const mtg_ctx *ctx) { return ctx->lists.as<int>() + (int6
 inline int *bank_counts(const mtg_ctx *ctx) { return ctx->counts.as<int>() + ctx->bank * 64; }
 
 void shard_release(mtg_ctx *ctx);
-int shard_exchange(mtg_ctx *ctx, int64_t EH, hipStream_t s);
 
 int fail(mtg_ctx *ctx, int code, const char *fmt, ...)
 {
@@ -959,7 +985,7 @@ MTG_API void mtg_destroy(mtg_ctx *ctx)
     shard_release(ctx);
     ctx->reset_plans();
     for (hipEvent_t e : ctx->prof_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->shard_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ens.shard_ev) (void)hipEventDestroy(e);
     if (ctx->foreign_done) (void)hipEventDestroy(ctx->foreign_done);
     if (ctx->own_done) (void)hipEventDestroy(ctx->own_done);
     for (hipStream_t st : ctx->side) if (st) (void)hipStreamDestroy(st);
@@ -1337,48 +1363,32 @@ MTG_API int mtg_ensemble_init(mtg_ctx *ctx, int64_t E, int W, uint64_t seed, con
     rc = use_device(ctx);
     if (rc) return rc;
     const int64_t EW = E * W, EH = E * (W / 2);
-    std::vector<int32_t> lc_full((size_t)EW), lc_half((size_t)EH), lc_spec((size_t)(3 * EH));
+    std::vector<int32_t> lc_full((size_t)EW), lc_spec((size_t)(3 * EH));
     for (int64_t e = 0; e < E; ++e) {
         const int32_t l = lc_of_ensemble ? lc_of_ensemble[e] : (ctx->L == 1 ? 0 : (int32_t)e);
         if (l < 0 || l >= ctx->L) return fail(ctx, MTG_E_ARG, "mtg_ensemble_init: light curve %d out of range", l);
         for (int w = 0; w < W; ++w) lc_full[(size_t)(e * W + w)] = l;
         for (int k = 0; k < W / 2; ++k)
-            lc_half[(size_t)(e * (W / 2) + k)] = lc_spec[(size_t)(e * (W / 2) + k)] = lc_spec[(size_t)(EH + e * (W / 2) + k)] =
-                lc_spec[(size_t)(2 * EH + e * (W / 2) + k)] = l;
+            lc_spec[(size_t)(e * (W / 2) + k)] = lc_spec[(size_t)(EH + e * (W / 2) + k)] = lc_spec[(size_t)(2 * EH + e * (W / 2) + k)] = l;
     }
     CTX_STREAM(ctx, s);
-    HIP_TRY(ctx, ctx->ens_coords.reserve((size_t)EW * P * 8));
-    HIP_TRY(ctx, ctx->ens_lnp.reserve((size_t)EW * 8));
-    HIP_TRY(ctx, ctx->ens_perm.reserve((size_t)EW * 4));
-    // (proposals, their factors, log-probabilities and statuses: room for the 3 E W/2 rows of a speculative iteration)
-    HIP_TRY(ctx, ctx->ens_q.reserve((size_t)3 * EH * P * 8));
-    HIP_TRY(ctx, ctx->ens_factor.reserve((size_t)2 * EH * 8));
-    HIP_TRY(ctx, ctx->ens_new.reserve((size_t)3 * EH * 8));
-    HIP_TRY(ctx, ctx->ens_st.reserve((size_t)3 * EH * 4));
-    HIP_TRY(ctx, ctx->ens_lc_spec.reserve((size_t)3 * EH * 4));
-    HIP_TRY(ctx, ctx->ens_lc_full.reserve((size_t)EW * 4));
-    HIP_TRY(ctx, ctx->ens_lc_half.reserve((size_t)EH * 4));
-    HIP_TRY(ctx, ctx->ens_naccept.reserve((size_t)EW * 4));
-    HIP_TRY(ctx, ctx->ens_best_lnp.reserve((size_t)E * 8));
-    HIP_TRY(ctx, ctx->ens_best_coords.reserve((size_t)E * P * 8));
-    HIP_TRY(ctx, ctx->ens_notpd.reserve(64));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_coords.p, coords, (size_t)EW * P * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_lc_full.p, lc_full.data(), (size_t)EW * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_lc_half.p, lc_half.data(), (size_t)EH * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_lc_spec.p, lc_spec.data(), (size_t)3 * EH * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ens_naccept.p, 0, (size_t)EW * 4, s));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ens_notpd.p, 0, 4, s));
+    mtg_ctx::Ensembles &en = ctx->ens;
+    const mtg_ctx::Ensembles::Sizes z = mtg_ctx::Ensembles::sizes(E, W, P);
+    HIP_TRY(ctx, en.reserve(z));
+    HIP_TRY(ctx, hipMemcpyAsync(en.coords.p, coords, z.coords, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(en.lc_full.p, lc_full.data(), z.lc_full, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(en.lc_spec.p, lc_spec.data(), z.lc_spec, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemsetAsync(en.naccept.p, 0, z.naccept, s));
+    HIP_TRY(ctx, hipMemsetAsync(en.notpd.p, 0, z.notpd, s));
     // log-probability of the initial state (emcee evaluates p0 once); the rows are grouped by ensemble, hence by light curve
     ctx->lc_grouped_hint = 1;
-    rc = run_model_batch(ctx, EW, ctx->ens_coords.as<double>(), ctx->ens_lc_full.as<int32_t>(), 1,
-                         ctx->ens_lnp.as<double>(), ctx->ens_st.as<int32_t>(), s);
+    rc = run_model_batch(ctx, EW, en.coords.as<double>(), en.lc_full.as<int32_t>(), 1, en.lnp.as<double>(), en.st.as<int32_t>(), s);
     if (rc) return rc;
-    mtg_launch_initial_best((int)E, W, P, ctx->ens_coords.as<double>(), ctx->ens_lnp.as<double>(),
-                            ctx->ens_best_lnp.as<double>(), ctx->ens_best_coords.as<double>(), s);
+    mtg_launch_initial_best((int)E, W, P, en.coords.as<double>(), en.lnp.as<double>(), en.best_lnp.as<double>(),
+                            en.best_coords.as<double>(), s);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(s));  // lc_full / lc_half live on this stack frame
-    ctx->ens_E = E; ctx->ens_W = W; ctx->ens_P = P; ctx->ens_seed = seed; ctx->ens_iteration = 0; ctx->ens_base = ctx->stream_base;
-    ctx->ens_L = ctx->L; ctx->ens_N = ctx->N;
+    HIP_TRY(ctx, hipStreamSynchronize(s));  // lc_full / lc_spec live on this stack frame
+    en.E = E; en.W = W; en.P = P; en.seed = seed; en.iteration = 0; en.base = ctx->stream_base; en.L = ctx->L; en.N = ctx->N;
     shard_release(ctx);  // a new set of ensembles starts unsharded (mtg_ensemble_shard_* after this call)
     return MTG_OK;
 }
@@ -1449,55 +1459,55 @@ bool rccl_load(const char *path)
 
 void shard_release(mtg_ctx *ctx)
 {
-    if (ctx->shard_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->shard_comm);
-    if (ctx->shard_h_lnp) (void)hipHostFree(ctx->shard_h_lnp);
-    if (ctx->shard_h_st) (void)hipHostFree(ctx->shard_h_st);
-    ctx->shard_comm = nullptr; ctx->shard_h_lnp = nullptr; ctx->shard_h_st = nullptr; ctx->shard_h_rows = 0;
-    ctx->shard_kind = 0; ctx->shard_rank = 0; ctx->shard_world = 1;
-    ctx->shard_generation.fetch_add(1);
-    ctx->shard_chunk = ctx->shard_lo = ctx->shard_hi = 0;
-    ctx->shard_fn = nullptr; ctx->shard_user = nullptr;
+    mtg_ctx::Ensembles::Shard &sh = ctx->ens.shard;
+    if (sh.comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(sh.comm);
+    if (sh.h_lnp) (void)hipHostFree(sh.h_lnp);
+    if (sh.h_st) (void)hipHostFree(sh.h_st);
+    sh = {};
+    ctx->ens.shard_generation.fetch_add(1);
 }
 
 // rows of the half-step batch this rank evaluates, and buffers large enough for the padded all-gather
 int shard_layout(mtg_ctx *ctx, int rank, int world)
 {
-    if (ctx->ens_E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
+    mtg_ctx::Ensembles &en = ctx->ens;
+    if (en.E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
     if (world < 1 || rank < 0 || rank >= world) return fail(ctx, MTG_E_ARG, "mtg_ensemble_shard: rank %d of %d", rank, world);
-    const int64_t EH = ctx->ens_E * (ctx->ens_W / 2);
+    const int64_t EH = en.E * (en.W / 2);
     const int64_t chunk = (EH + world - 1) / world;
     int rc = use_device(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     shard_release(ctx);
     // (DevBuf::reserve keeps the contents only when it does not grow: the buffers hold nothing between runs)
-    HIP_TRY(ctx, ctx->ens_new.reserve((size_t)std::max<int64_t>(ctx->ens_E * ctx->ens_W, chunk * world) * 8));
-    HIP_TRY(ctx, ctx->ens_st.reserve((size_t)std::max<int64_t>(ctx->ens_E * ctx->ens_W, chunk * world) * 4));
-    ctx->shard_rank = rank; ctx->shard_world = world; ctx->shard_chunk = chunk;
-    ctx->shard_lo = std::min<int64_t>((int64_t)rank * chunk, EH);
-    ctx->shard_hi = std::min<int64_t>(ctx->shard_lo + chunk, EH);
+    const mtg_ctx::Ensembles::Sizes z = en.sizes();
+    HIP_TRY(ctx, en.new_lnp.reserve(std::max(z.new_lnp, (size_t)(chunk * world) * sizeof(double))));
+    HIP_TRY(ctx, en.st.reserve(std::max(z.st, (size_t)(chunk * world) * sizeof(int32_t))));
+    en.shard.rank = rank; en.shard.world = world; en.shard.chunk = chunk;
+    en.shard.lo = std::min<int64_t>((int64_t)rank * chunk, EH);
+    en.shard.hi = std::min<int64_t>(en.shard.lo + chunk, EH);
     return MTG_OK;
 }
 
-// after the solve of a half-step: everybody's log-probabilities and status words into ens_new / ens_st
+// after the solve of a half-step: everybody's log-probabilities and status words into ens.new_lnp / ens.st
 int shard_exchange(mtg_ctx *ctx, int64_t EH, hipStream_t s)
 {
-    double *lnp = ctx->ens_new.as<double>();
-    int32_t *st = ctx->ens_st.as<int32_t>();
-    const int64_t chunk = ctx->shard_chunk, lo = ctx->shard_lo, hi = ctx->shard_hi;
-    if (ctx->shard_kind == 1) {
+    double *lnp = ctx->ens.new_lnp.as<double>();
+    int32_t *st = ctx->ens.st.as<int32_t>();
+    const int64_t chunk = ctx->ens.shard.chunk, lo = ctx->ens.shard.lo, hi = ctx->ens.shard.hi;
+    if (ctx->ens.shard.kind == 1) {
         mtg_trace::Range range("mtg:all-gather of the half-step's log-probabilities (RCCL)");
         // in place: this rank's block already sits at rank * chunk of the receive buffer
-        const int64_t at = (int64_t)ctx->shard_rank * chunk;
-        const bool timed = ctx->shard_ev_n < ctx->shard_ev_cap;
-        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->shard_ev[2 * (size_t)ctx->shard_ev_n], s));
+        const int64_t at = (int64_t)ctx->ens.shard.rank * chunk;
+        const bool timed = ctx->ens.shard_ev_n < ctx->ens.shard_ev_cap;
+        if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ens.shard_ev[2 * (size_t)ctx->ens.shard_ev_n], s));
         struct Stamp {  // the closing event, whatever way the block is left
             mtg_ctx *c; hipStream_t st; bool on;
-            ~Stamp() { if (on) { (void)hipEventRecord(c->shard_ev[2 * (size_t)c->shard_ev_n + 1], st); c->shard_ev_n += 1; } }
+            ~Stamp() { if (on) { (void)hipEventRecord(c->ens.shard_ev[2 * (size_t)c->ens.shard_ev_n + 1], st); c->ens.shard_ev_n += 1; } }
         } stamp{ctx, s, timed};
         RCCL_TRY(ctx, g_rccl.GroupStart());
-        int r1 = g_rccl.AllGather(lnp + at, lnp, (size_t)chunk, RCCL_FLOAT64, ctx->shard_comm, s);
-        int r2 = r1 ? r1 : g_rccl.AllGather(st + at, st, (size_t)chunk, RCCL_INT32, ctx->shard_comm, s);
+        int r1 = g_rccl.AllGather(lnp + at, lnp, (size_t)chunk, RCCL_FLOAT64, ctx->ens.shard.comm, s);
+        int r2 = r1 ? r1 : g_rccl.AllGather(st + at, st, (size_t)chunk, RCCL_INT32, ctx->ens.shard.comm, s);
         const int r3 = g_rccl.GroupEnd();   // (always closed, whatever the calls inside it said)
         if (r2 || r3)
             return fail(ctx, MTG_E_HIP, "ncclAllGather of the half-step's log-probabilities failed: %s",
@@ -1506,23 +1516,23 @@ int shard_exchange(mtg_ctx *ctx, int64_t EH, hipStream_t s)
     }
     // host callback: stage this rank's rows, let the caller fill in the others, upload everything
     mtg_trace::Range range("mtg:exchange of the half-step's log-probabilities (host callback)");
-    if (ctx->shard_h_rows < EH) {
-        if (ctx->shard_h_lnp) (void)hipHostFree(ctx->shard_h_lnp);
-        if (ctx->shard_h_st) (void)hipHostFree(ctx->shard_h_st);
-        ctx->shard_h_lnp = nullptr; ctx->shard_h_st = nullptr; ctx->shard_h_rows = 0;
-        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->shard_h_lnp, (size_t)EH * 8));
-        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->shard_h_st, (size_t)EH * 4));
-        ctx->shard_h_rows = EH;
+    if (ctx->ens.shard.h_rows < EH) {
+        if (ctx->ens.shard.h_lnp) (void)hipHostFree(ctx->ens.shard.h_lnp);
+        if (ctx->ens.shard.h_st) (void)hipHostFree(ctx->ens.shard.h_st);
+        ctx->ens.shard.h_lnp = nullptr; ctx->ens.shard.h_st = nullptr; ctx->ens.shard.h_rows = 0;
+        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->ens.shard.h_lnp, (size_t)EH * 8));
+        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->ens.shard.h_st, (size_t)EH * 4));
+        ctx->ens.shard.h_rows = EH;
     }
     if (hi > lo) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->shard_h_lnp + lo, lnp + lo, (size_t)(hi - lo) * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->shard_h_st + lo, st + lo, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ens.shard.h_lnp + lo, lnp + lo, (size_t)(hi - lo) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->ens.shard.h_st + lo, st + lo, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    const int rc = ctx->shard_fn(ctx->shard_user, ctx->shard_h_lnp, ctx->shard_h_st, EH, lo, hi);
+    const int rc = ctx->ens.shard.fn(ctx->ens.shard.user, ctx->ens.shard.h_lnp, ctx->ens.shard.h_st, EH, lo, hi);
     if (rc) return fail(ctx, MTG_E_STATE, "the exchange callback of the walker-sharded ensemble returned %d", rc);
-    HIP_TRY(ctx, hipMemcpyAsync(lnp, ctx->shard_h_lnp, (size_t)EH * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->shard_h_st, (size_t)EH * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(lnp, ctx->ens.shard.h_lnp, (size_t)EH * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->ens.shard.h_st, (size_t)EH * 4, hipMemcpyHostToDevice, s));
     return MTG_OK;
 }
 
@@ -1549,16 +1559,16 @@ MTG_API int mtg_ensemble_shard_rccl(mtg_ctx *ctx, const void *id128, int rank, i
     Id128 id;
     memcpy(id.b, id128, sizeof id.b);
     void *comm = nullptr;
-    const int generation = ctx->shard_generation.load();
+    const int generation = ctx->ens.shard_generation.load();
     RCCL_TRY(ctx, g_rccl.CommInitRank(&comm, world, id, rank));
-    if (ctx->shard_generation.load() != generation) {
+    if (ctx->ens.shard_generation.load() != generation) {
         // ncclCommInitRank took so long that the caller gave up and (un)sharded the context another way meanwhile
         // (distributed.shard_device_ensemble's fall-back to the host-staged exchange): this communicator is nobody's
         (void)g_rccl.CommDestroy(comm);
         return fail(ctx, MTG_E_STATE, "mtg_ensemble_shard_rccl: the context was re-sharded while ncclCommInitRank was running");
     }
-    ctx->shard_comm = comm;
-    ctx->shard_kind = 1;
+    ctx->ens.shard.comm = comm;
+    ctx->ens.shard.kind = 1;
     return MTG_OK;
 }
 
@@ -1567,21 +1577,21 @@ MTG_API int mtg_ensemble_shard_host(mtg_ctx *ctx, int rank, int world, mtg_excha
     if (!ctx || !fn) return MTG_E_ARG;
     int rc = shard_layout(ctx, rank, world);
     if (rc) return rc;
-    ctx->shard_fn = fn;
-    ctx->shard_user = user;
-    ctx->shard_kind = 2;
+    ctx->ens.shard.fn = fn;
+    ctx->ens.shard.user = user;
+    ctx->ens.shard.kind = 2;
     return MTG_OK;
 }
 
 MTG_API int mtg_ensemble_shard_info(const mtg_ctx *ctx, int *kind, int *rank, int *world, int *comm_ranks)
 {
     if (!ctx) return MTG_E_ARG;
-    if (kind) *kind = ctx->shard_kind;
-    if (rank) *rank = ctx->shard_rank;
-    if (world) *world = ctx->shard_world;
+    if (kind) *kind = ctx->ens.shard.kind;
+    if (rank) *rank = ctx->ens.shard.rank;
+    if (world) *world = ctx->ens.shard.world;
     if (comm_ranks) {
         *comm_ranks = 0;
-        if (ctx->shard_kind == 1 && ctx->shard_comm && g_rccl.CommCount) (void)g_rccl.CommCount(ctx->shard_comm, comm_ranks);
+        if (ctx->ens.shard.kind == 1 && ctx->ens.shard.comm && g_rccl.CommCount) (void)g_rccl.CommCount(ctx->ens.shard.comm, comm_ranks);
     }
     return MTG_OK;
 }
@@ -1591,27 +1601,27 @@ MTG_API int mtg_ensemble_shard_profile(mtg_ctx *ctx, int capacity)
     if (!ctx || capacity < 0) return MTG_E_ARG;
     int rc = use_device(ctx);
     if (rc) return rc;
-    while ((int)ctx->shard_ev.size() < 2 * capacity) {
+    while ((int)ctx->ens.shard_ev.size() < 2 * capacity) {
         hipEvent_t e;
         HIP_TRY(ctx, hipEventCreate(&e));
-        ctx->shard_ev.push_back(e);
+        ctx->ens.shard_ev.push_back(e);
     }
-    ctx->shard_ev_cap = capacity;
-    ctx->shard_ev_n = 0;
+    ctx->ens.shard_ev_cap = capacity;
+    ctx->ens.shard_ev_n = 0;
     return MTG_OK;
 }
 
 MTG_API int mtg_ensemble_shard_profile_read(mtg_ctx *ctx, int capacity, double *exchange_ms)
 {
     if (!ctx || capacity < 0) return MTG_E_ARG;
-    const int n = ctx->shard_ev_n < capacity ? ctx->shard_ev_n : capacity;
+    const int n = ctx->ens.shard_ev_n < capacity ? ctx->ens.shard_ev_n : capacity;
     for (int i = 0; i < n; ++i) {
         float ms = 0.f;
-        HIP_TRY(ctx, hipEventSynchronize(ctx->shard_ev[2 * (size_t)i + 1]));
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->shard_ev[2 * (size_t)i], ctx->shard_ev[2 * (size_t)i + 1]));
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ens.shard_ev[2 * (size_t)i + 1]));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ens.shard_ev[2 * (size_t)i], ctx->ens.shard_ev[2 * (size_t)i + 1]));
         if (exchange_ms) exchange_ms[i] = ms;
     }
-    ctx->shard_ev_cap = 0;
+    ctx->ens.shard_ev_cap = 0;
     return n;
 }
 
@@ -1625,138 +1635,145 @@ MTG_API int mtg_ensemble_unshard(mtg_ctx *ctx)
     return MTG_OK;
 }
 
+namespace {
+
+// One mtg_ensemble_run in flight.  The entry runs the stages in order -- check (which plans the run:
+// mtg_plan_ensemble_run), stage, then for every solve of the plan solve and launch as the schedule says
+// (mtg_ensemble_step) -- and returns at the first that fails; the chain's way back to the caller is the entry's own end.
+// Between two solves ONE launch does the accept step of the solve just made and the proposals (with their expansion) of
+// the next: mtg_sampler_step_kernel, or mtg_sampler_spec_kernel for a speculative iteration.  The structure lists have
+// two banks: the proposals of solve k + 1 are appended to one while workgroup 0 clears the counters of the other, which
+// solve k has just used.
+struct EnsembleRun {
+    mtg_ctx *ctx;
+    mtg_ctx::Ensembles &en;
+    int steps;
+    double *chain, *lnp_chain;
+    hipStream_t s = nullptr;
+    int64_t EW = 0;
+    uint32_t iteration0 = 0;       // of the ensembles when the run began
+    MtgEnsembleRunPlan plan{};
+    MtgEnsembleArgs g{};
+    int32_t *perm_all = nullptr;   // plan.splits_up_front: [steps][E][W]
+
+    int check();
+    int stage();
+    int solve(const MtgEnsembleStep &st);
+    void launch(const MtgEnsembleStep &st);
+};
+
+int EnsembleRun::check()
+{
+    if (const int rc = check_ready(ctx, true)) return rc;
+    if (en.E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
+    if (steps < 0) return fail(ctx, MTG_E_ARG, "mtg_ensemble_run: negative step count");
+    if (en.P != ctx->model.P) return fail(ctx, MTG_E_STATE, "the model changed since mtg_ensemble_init");
+    if (en.L != ctx->L || en.N != ctx->N)
+        return fail(ctx, MTG_E_STATE, "the resident light curves changed shape since mtg_ensemble_init");
+    if (const int rc = use_device(ctx)) return rc;
+    CTX_STREAM(ctx, own);
+    s = own;
+    EW = en.E * en.W;
+    iteration0 = en.iteration;
+    plan = mtg_plan_ensemble_run(en.E, en.W, steps, ctx->tp_mode, ctx->spec_mode, ctx->model.nr0 + 2 * ctx->model.nc0, ctx->N,
+                                 en.shard.kind, en.shard.lo, en.shard.hi);
+    return MTG_OK;
+}
+
+// room for the chain and the plan's solves, both banks' counters cleared, the splits where the plan makes them up front
+int EnsembleRun::stage()
+{
+    if (chain) HIP_TRY(ctx, en.chain.reserve((size_t)steps * en.sizes().coords));
+    if (lnp_chain) HIP_TRY(ctx, en.lnp_chain.reserve((size_t)steps * en.sizes().lnp));
+    if (const int rc = check_model_workspace(ctx, plan.rows_per_solve)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counts.p, 0, 2 * 64 * sizeof(int), s));
+    g.E = (int)en.E; g.W = en.W; g.P = en.P;
+    g.e_base = (uint32_t)en.base; g.seed_lo = (uint32_t)en.seed; g.seed_hi = (uint32_t)(en.seed >> 32); g.a = 2.0;
+    g.perm = en.perm.as<int32_t>(); g.coords = en.coords.as<double>(); g.lnp = en.lnp.as<double>();
+    g.factor = en.factor.as<double>(); g.naccept = en.naccept.as<int32_t>(); g.n_notpd = en.notpd.as<int32_t>();
+    g.best_lnp = en.best_lnp.as<double>(); g.best_coords = en.best_coords.as<double>();
+    if (plan.splits_up_front) {
+        HIP_TRY(ctx, en.perm_all.reserve(plan.perm_bytes));
+        perm_all = en.perm_all.as<int32_t>();
+        mtg_launch_split_all(g, iteration0, steps, perm_all, s);
+    }
+    return MTG_OK;
+}
+
+// the proposals in the bank the last launch filled; sharded: then everybody's log-probabilities and status words
+int EnsembleRun::solve(const MtgEnsembleStep &st)
+{
+    ctx->bank = st.bank_used;
+    const int rc = solve_prepared(ctx, plan.rows_per_solve, en.lc_spec.as<int32_t>(), en.new_lnp.as<double>(), en.st.as<int32_t>(), s);
+    return rc || !en.shard.kind ? rc : shard_exchange(ctx, plan.rows_per_solve, s);
+}
+
+void EnsembleRun::launch(const MtgEnsembleStep &st)
+{
+    g.perm = st.perm >= 0 ? perm_all + st.perm * EW : en.perm.as<int32_t>();
+    g.perm_next = st.perm_next >= 0 ? perm_all + st.perm_next * EW : nullptr;
+    MtgSamplerLaunch l;
+    l.do_accept = st.do_accept; l.half = st.half; l.iteration = st.iteration;
+    l.do_propose = st.do_propose; l.next_half = st.next_half; l.next_iteration = st.next_iteration;
+    if (st.do_accept) {
+        ctx->bank = st.bank_used;
+        l.new_lnp = en.new_lnp.as<double>(); l.status = en.st.as<int32_t>(); l.clear_counts = bank_counts(ctx);
+    }
+    if (st.chain_row >= 0 && chain) l.chain_row = en.chain.as<double>() + st.chain_row * EW * en.P;
+    if (st.chain_row >= 0 && lnp_chain) l.lnp_chain_row = en.lnp_chain.as<double>() + st.chain_row * EW;
+    ctx->bank = st.bank_next;
+    MtgPrepArgs pa = make_prep_args(ctx, plan.rows_per_solve, en.q.as<double>(), 1, en.new_lnp.as<double>(), en.st.as<int32_t>(),
+                                    ctx->model.nsho + 1);
+    if (en.shard.kind) { pa.row_lo = en.shard.lo; pa.row_hi = en.shard.hi; }
+    (plan.speculative ? mtg_launch_sampler_spec : mtg_launch_sampler_step)(g, l, pa, s);
+    en.iteration = st.next_iteration;
+}
+
+// mtg_ensemble_get / mtg_ensemble_restore: the state a caller may read or put back as (host pointer, buffer, bytes),
+// copied to the host or from it -- NULL host pointers skipped -- and the stream waited for
+int ens_copy_state(mtg_ctx *ctx, hipMemcpyKind kind, const double *coords, const double *lnp, const double *best_lnp,
+                   const double *best_coords, const int32_t *naccept, const int32_t *n_notpd)
+{
+    if (const int rc = use_device(ctx)) return rc;
+    CTX_STREAM(ctx, s);
+    mtg_ctx::Ensembles &en = ctx->ens;
+    const mtg_ctx::Ensembles::Sizes z = en.sizes();
+    const struct { const void *host; DevBuf &buf; size_t bytes; } state[] = {
+        {coords, en.coords, z.coords}, {lnp, en.lnp, z.lnp}, {best_lnp, en.best_lnp, z.best_lnp},
+        {best_coords, en.best_coords, z.best_coords}, {naccept, en.naccept, z.naccept}, {n_notpd, en.notpd, z.notpd}};
+    for (const auto &r : state) {
+        if (!r.host) continue;
+        if (kind == hipMemcpyHostToDevice) HIP_TRY(ctx, hipMemcpyAsync(r.buf.p, r.host, r.bytes, kind, s));
+        else HIP_TRY(ctx, hipMemcpyAsync(const_cast<void *>(r.host), r.buf.p, r.bytes, kind, s));   // (mtg_ensemble_get's own pointers)
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    return MTG_OK;
+}
+
+}  // namespace
+
 MTG_API int mtg_ensemble_run(mtg_ctx *ctx, int steps, double *chain, double *lnp_chain)
 {
-    int rc = check_ready(ctx, true);
+    if (!ctx) return MTG_E_ARG;
+    EnsembleRun r{ctx, ctx->ens, steps, chain, lnp_chain};
+    int rc = r.check();
     if (rc) return rc;
-    if (ctx->ens_E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
-    if (steps < 0) return fail(ctx, MTG_E_ARG, "mtg_ensemble_run: negative step count");
-    if (ctx->ens_P != ctx->model.P) return fail(ctx, MTG_E_STATE, "the model changed since mtg_ensemble_init");
-    if (ctx->ens_L != ctx->L || ctx->ens_N != ctx->N)
-        return fail(ctx, MTG_E_STATE, "the resident light curves changed shape since mtg_ensemble_init");
-    rc = use_device(ctx);
-    if (rc) return rc;
-    const int E = (int)ctx->ens_E, W = ctx->ens_W, P = ctx->ens_P, H = W / 2;
-    const int64_t EW = (int64_t)E * W, EH = (int64_t)E * H;
-    CTX_STREAM(ctx, s);
     mtg_trace::Range range("mtg:ensemble_run (stretch moves, device resident)");
-    if (chain) HIP_TRY(ctx, ctx->ens_chain.reserve((size_t)steps * EW * P * 8));
-    if (lnp_chain) HIP_TRY(ctx, ctx->ens_lnp_chain.reserve((size_t)steps * EW * 8));
-    rc = check_model_workspace(ctx, EH);
-    if (rc) return rc;
-    // Between two solves ONE launch does the accept step of the half-step just evaluated and the proposals (with
-    // their expansion) of the next: mtg_sampler_step_kernel.  The structure lists have two banks: the proposals of
-    // half-step h + 1 are appended to one while workgroup 0 clears the counters of the other, which the solver of
-    // half-step h has just used.
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counts.p, 0, 2 * 64 * sizeof(int), s));
-    struct BankGuard {  // everybody else uses bank 0
-        mtg_ctx *c;
-        ~BankGuard() { c->bank = 0; }
-    } bank_guard{ctx};
-    const bool sharded = ctx->shard_kind != 0;
-    struct LiveRows {  // the solver's kernel choice looks at the rows this rank evaluates
-        mtg_ctx *c;
-        LiveRows(mtg_ctx *ctx_, int64_t n) : c(ctx_) { c->live_rows = n; }
-        ~LiveRows() { c->live_rows = 0; }
-    } live_rows(ctx, sharded ? (ctx->shard_hi > ctx->shard_lo ? ctx->shard_hi - ctx->shard_lo : 1) : 0);
-    auto prep_args = [&](int bank) {
-        ctx->bank = bank;
-        MtgPrepArgs pa = make_prep_args(ctx, EH, ctx->ens_q.as<double>(), 1, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>(), ctx->model.nsho + 1);
-        if (sharded) {
-            pa.row_lo = ctx->shard_lo;
-            pa.row_hi = ctx->shard_hi;
-        }
-        return pa;
-    };
-    MtgEnsembleArgs g;
-    g.E = E; g.W = W; g.P = P;
-    g.e_base = (uint32_t)ctx->ens_base;
-    g.seed_lo = (uint32_t)ctx->ens_seed; g.seed_hi = (uint32_t)(ctx->ens_seed >> 32);
-    g.a = 2.0;
-    g.perm = ctx->ens_perm.as<int32_t>();
-    g.coords = ctx->ens_coords.as<double>();
-    g.lnp = ctx->ens_lnp.as<double>();
-    g.factor = ctx->ens_factor.as<double>();
-    g.naccept = ctx->ens_naccept.as<int32_t>();
-    g.best_lnp = ctx->ens_best_lnp.as<double>();
-    g.best_coords = ctx->ens_best_coords.as<double>();
-    g.n_notpd = ctx->ens_notpd.as<int32_t>();
-    int bank = 0;
-    // A small ensemble leaves most of the GPU idle and its solve takes as long for 3 H rows as for H: both half-steps of
-    // an iteration then go into one batch (mtg_sampler.hip: speculative iteration).  Where: the time-parallel kernels
-    // with every row on a workgroup of its own in one occupancy round -- 256 workgroups of four waves for long light
-    // curves (one per CU: their elements fill the LDS; two per CU up to rank 3, and for ranks 4 and 5 with two waves
-    // each), 1024 single-wave ones for short.  Same chain either way where both forms run the same kernel.
-    const int64_t rows3 = 3 * EH;
-    const bool spec = steps > 0 && ctx->spec_mode != 0 && !sharded &&
-                      mtg_plan_speculate(ctx->tp_mode, ctx->model.nr0 + 2 * ctx->model.nc0, ctx->N, rows3);
-    if (spec) {
-        rc = check_model_workspace(ctx, rows3);
-        if (rc) return rc;
-        auto prep3 = [&](int bank_) {
-            ctx->bank = bank_;
-            return make_prep_args(ctx, rows3, ctx->ens_q.as<double>(), 1, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>(), ctx->model.nsho + 1);
-        };
-        // the splits of the whole run in one launch over the whole GPU, where they are small (an ensemble or a few): the
-        // sampler kernel of an iteration is one workgroup's chain of latencies and ranking W keys is 2-5 us of it
-        int32_t *perm_all = nullptr;
-        const size_t perm_bytes = (size_t)steps * EW * sizeof(int32_t);
-        if (perm_bytes <= ((size_t)64 << 20) && steps <= 65535 && ctx->spec_mode != 2) {
-            HIP_TRY(ctx, ctx->ens_perm_all.reserve(perm_bytes));
-            perm_all = ctx->ens_perm_all.as<int32_t>();
-            mtg_launch_split_all(g, ctx->ens_iteration, steps, perm_all, s);
-        }
-        g.perm_next = perm_all;   // (slice 0: the iteration the first launch proposes)
-        mtg_launch_sampler_spec(g, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, ctx->ens_iteration, prep3(bank), s);
-        for (int it = 0; it < steps; ++it) {
-            const uint32_t iter = ctx->ens_iteration;
-            ctx->bank = bank;
-            if (perm_all) {
-                g.perm = perm_all + (size_t)it * EW;                                   // this iteration's split, for the accept step
-                g.perm_next = it + 1 < steps ? perm_all + (size_t)(it + 1) * EW : nullptr;  // the next one's, for its proposals
-            }
-            rc = solve_prepared(ctx, rows3, ctx->ens_lc_spec.as<int32_t>(), ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>(), s);
-            if (rc) return rc;
-            const bool more = it + 1 < steps;
-            int *used_counts = bank_counts(ctx);
-            mtg_launch_sampler_spec(g, 1, iter, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>(), used_counts,
-                                    chain ? ctx->ens_chain.as<double>() + (size_t)it * EW * P : nullptr,
-                                    lnp_chain ? ctx->ens_lnp_chain.as<double>() + (size_t)it * EW : nullptr, more ? 1 : 0, iter + 1,
-                                    prep3(bank ^ 1), s);
-            bank ^= 1;
-            ctx->ens_iteration += 1;
-        }
-    }
-    if (steps > 0 && !spec)  // the first proposals of the run
-        mtg_launch_sampler_step(g, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, ctx->ens_iteration, prep_args(bank), s);
-    for (int it = 0; it < steps && !spec; ++it) {
-        const uint32_t iter = ctx->ens_iteration;
-        for (int half = 0; half < 2; ++half) {
-            ctx->bank = bank;
-            rc = solve_prepared(ctx, EH, ctx->ens_lc_half.as<int32_t>(), ctx->ens_new.as<double>(),
-                                ctx->ens_st.as<int32_t>(), s);
-            if (rc) return rc;
-            if (sharded) {
-                rc = shard_exchange(ctx, EH, s);
-                if (rc) return rc;
-            }
-            const bool last = half == 1;
-            const bool more = !(last && it + 1 == steps);   // another half-step follows in this call
-            int *used_counts = bank_counts(ctx);
-            mtg_launch_sampler_step(g, 1, half, iter, ctx->ens_new.as<double>(), ctx->ens_st.as<int32_t>(), used_counts,
-                                    last && chain ? ctx->ens_chain.as<double>() + (size_t)it * EW * P : nullptr,
-                                    last && lnp_chain ? ctx->ens_lnp_chain.as<double>() + (size_t)it * EW : nullptr,
-                                    more ? 1 : 0, last ? 0 : 1, last ? iter + 1 : iter, prep_args(bank ^ 1), s);
-            bank ^= 1;
-        }
-        ctx->ens_iteration += 1;
+    struct BankGuard { mtg_ctx *c; ~BankGuard() { c->bank = 0; } } bank_guard{ctx};   // everybody else uses bank 0
+    struct LiveRows { mtg_ctx *c; ~LiveRows() { c->live_rows = 0; } } live_rows{ctx};
+    ctx->live_rows = r.plan.live_rows;   // the solver's kernel choice looks at the rows this rank evaluates
+    if ((rc = r.stage())) return rc;
+    if (r.plan.solves > 0) r.launch(mtg_ensemble_step(r.plan, -1, steps, r.iteration0));   // the first proposals of the run
+    for (int64_t k = 0; k < r.plan.solves; ++k) {
+        const MtgEnsembleStep st = mtg_ensemble_step(r.plan, k, steps, r.iteration0);
+        if ((rc = r.solve(st))) return rc;
+        r.launch(st);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (chain)
-        HIP_TRY(ctx, hipMemcpyAsync(chain, ctx->ens_chain.p, (size_t)steps * EW * P * 8, hipMemcpyDeviceToHost, s));
-    if (lnp_chain)
-        HIP_TRY(ctx, hipMemcpyAsync(lnp_chain, ctx->ens_lnp_chain.p, (size_t)steps * EW * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
+    const mtg_ctx::Ensembles::Sizes z = ctx->ens.sizes();
+    if (chain) HIP_TRY(ctx, hipMemcpyAsync(chain, ctx->ens.chain.p, (size_t)steps * z.coords, hipMemcpyDeviceToHost, r.s));
+    if (lnp_chain) HIP_TRY(ctx, hipMemcpyAsync(lnp_chain, ctx->ens.lnp_chain.p, (size_t)steps * z.lnp, hipMemcpyDeviceToHost, r.s));
+    HIP_TRY(ctx, hipStreamSynchronize(r.s));
     return MTG_OK;
 }
 
@@ -1764,46 +1781,25 @@ MTG_API int mtg_ensemble_restore(mtg_ctx *ctx, int64_t iteration, const double *
                                  const double *best_lnp, const double *best_coords)
 {
     if (!ctx) return MTG_E_ARG;
-    if (ctx->ens_E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
+    if (ctx->ens.E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
     if (iteration < 0 || iteration > 0xffffffffll) return fail(ctx, MTG_E_ARG, "mtg_ensemble_restore: iteration out of range");
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    const int64_t E = ctx->ens_E, EW = E * ctx->ens_W;
-    CTX_STREAM(ctx, s);
     // the saved log-probabilities as they are: mtg_ensemble_init has just evaluated the saved coordinates again, but
     // in ONE batch of E W rows, where the run evaluated them in half-steps of E W/2 (or a rank's share of them) -- the
     // kernel and its summation order follow the row count, so those values may differ in the last bits and flip an
     // accept decision of the continued chain
-    if (lnp) HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_lnp.p, lnp, (size_t)EW * 8, hipMemcpyHostToDevice, s));
-    if (naccept) HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_naccept.p, naccept, (size_t)EW * 4, hipMemcpyHostToDevice, s));
-    if (best_lnp) HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_best_lnp.p, best_lnp, (size_t)E * 8, hipMemcpyHostToDevice, s));
-    if (best_coords)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ens_best_coords.p, best_coords, (size_t)E * ctx->ens_P * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    ctx->ens_iteration = (uint32_t)iteration;
-    return MTG_OK;
+    const int rc = ens_copy_state(ctx, hipMemcpyHostToDevice, nullptr, lnp, best_lnp, best_coords, naccept, nullptr);
+    if (rc == MTG_OK) ctx->ens.iteration = (uint32_t)iteration;
+    return rc;
 }
 
 MTG_API int mtg_ensemble_get(mtg_ctx *ctx, double *coords, double *lnp, double *best_lnp, double *best_coords,
                              int32_t *naccept, int64_t *iteration, int32_t *n_notpd)
 {
     if (!ctx) return MTG_E_ARG;
-    if (ctx->ens_E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    const int64_t E = ctx->ens_E, EW = E * ctx->ens_W;
-    const int P = ctx->ens_P;
-    CTX_STREAM(ctx, s);
-    if (coords) HIP_TRY(ctx, hipMemcpyAsync(coords, ctx->ens_coords.p, (size_t)EW * P * 8, hipMemcpyDeviceToHost, s));
-    if (lnp) HIP_TRY(ctx, hipMemcpyAsync(lnp, ctx->ens_lnp.p, (size_t)EW * 8, hipMemcpyDeviceToHost, s));
-    if (best_lnp) HIP_TRY(ctx, hipMemcpyAsync(best_lnp, ctx->ens_best_lnp.p, (size_t)E * 8, hipMemcpyDeviceToHost, s));
-    if (best_coords)
-        HIP_TRY(ctx, hipMemcpyAsync(best_coords, ctx->ens_best_coords.p, (size_t)E * P * 8, hipMemcpyDeviceToHost, s));
-    if (naccept) HIP_TRY(ctx, hipMemcpyAsync(naccept, ctx->ens_naccept.p, (size_t)EW * 4, hipMemcpyDeviceToHost, s));
-    if (n_notpd) HIP_TRY(ctx, hipMemcpyAsync(n_notpd, ctx->ens_notpd.p, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    if (iteration) *iteration = ctx->ens_iteration;
-    return MTG_OK;
+    if (ctx->ens.E <= 0) return fail(ctx, MTG_E_STATE, "mtg_ensemble_init has not been called");
+    const int rc = ens_copy_state(ctx, hipMemcpyDeviceToHost, coords, lnp, best_lnp, best_coords, naccept, n_notpd);
+    if (rc == MTG_OK && iteration) *iteration = ctx->ens.iteration;
+    return rc;
 }
 
 MTG_API int mtg_fft_warmup(mtg_ctx *ctx)

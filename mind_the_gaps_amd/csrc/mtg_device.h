@@ -260,14 +260,22 @@ struct MtgEnsembleArgs {
 };
 // One launch between two solves: accept of half-step (iteration, half) -- proposals in pa.theta, results in
 // new_lnp / status -- then the proposals of (next_iteration, next_half) expanded through pa (either part optional).
-void mtg_launch_sampler_step(const MtgEnsembleArgs &g, int do_accept, int half, uint32_t iteration, const double *new_lnp,
-                             const int32_t *status, int *clear_counts, double *chain_row, double *lnp_chain_row, int do_propose,
-                             int next_half, uint32_t next_iteration, const MtgPrepArgs &pa, hipStream_t);
+// The defaults are the priming launch of a run: nothing to accept, the first proposals.
+struct MtgSamplerLaunch {
+    int do_accept = 0, half = 0;
+    uint32_t iteration = 0;
+    const double *new_lnp = nullptr;
+    const int32_t *status = nullptr;
+    int *clear_counts = nullptr;                           // counters of the bank the solve has just used
+    double *chain_row = nullptr, *lnp_chain_row = nullptr;  // [E][W][P], [E][W] of the iteration this accept completes, or NULL
+    int do_propose = 1, next_half = 0;
+    uint32_t next_iteration = 0;
+};
+void mtg_launch_sampler_step(const MtgEnsembleArgs &g, const MtgSamplerLaunch &l, const MtgPrepArgs &pa, hipStream_t);
 // A whole iteration speculatively (mtg_sampler.hip): accept of both half-steps of `iteration` from the 3 E W/2 rows
-// in new_lnp / status, then the 3 E W/2 proposals of next_iteration (g.factor holds 2 E W/2 entries).
-void mtg_launch_sampler_spec(const MtgEnsembleArgs &g, int do_accept, uint32_t iteration, const double *new_lnp,
-                             const int32_t *status, int *clear_counts, double *chain_row, double *lnp_chain_row, int do_propose,
-                             uint32_t next_iteration, const MtgPrepArgs &pa, hipStream_t);
+// in new_lnp / status, then the 3 E W/2 proposals of next_iteration (g.factor holds 2 E W/2 entries; half and next_half
+// have no meaning here).
+void mtg_launch_sampler_spec(const MtgEnsembleArgs &g, const MtgSamplerLaunch &l, const MtgPrepArgs &pa, hipStream_t);
 // the splits of `steps` iterations from iteration0 on, perm_all[steps][E][W] (mtg_sampler.hip)
 void mtg_launch_split_all(const MtgEnsembleArgs &g, uint32_t iteration0, int steps, int32_t *perm_all, hipStream_t);
 void mtg_launch_initial_best(int E, int W, int P, const double *coords, const double *lnp, double *best_lnp,

@@ -97,18 +97,16 @@ mtg_initial_best_kernel(int E, int W, int P, const double *__restrict__ coords, 
     for (int d = 0; d < P; ++d) best_coords[(int64_t)e * P + d] = coords[((int64_t)e * W + bi) * P + d];
 }
 
-void mtg_launch_sampler_step(const MtgEnsembleArgs &g, int do_accept, int half, uint32_t iteration, const double *new_lnp,
-                             const int32_t *status, int *clear_counts, double *chain_row, double *lnp_chain_row, int do_propose,
-                             int next_half, uint32_t next_iteration, const MtgPrepArgs &pa, hipStream_t s)
+void mtg_launch_sampler_step(const MtgEnsembleArgs &g, const MtgSamplerLaunch &l, const MtgPrepArgs &pa, hipStream_t s)
 {
     // the proposals need W / 2 threads, the accept step up to 256; the split of a first half-step ranks W keys against
     // each other and takes as many threads as a workgroup of a few ensembles can have (many ensembles: the GPU is
     // full anyway)
     int threads = 256;
-    if (do_propose && next_half == 0 && g.E <= 64) threads = 1024;
+    if (l.do_propose && l.next_half == 0 && g.E <= 64) threads = 1024;
     hipLaunchKernelGGL(mtg_sampler_step_kernel, dim3((unsigned)g.E), dim3(threads), (size_t)g.W * (sizeof(uint64_t) + sizeof(int)), s,
-                       g, do_accept, half, iteration, new_lnp, status, clear_counts, chain_row, lnp_chain_row, do_propose, next_half,
-                       next_iteration, pa);
+                       g, l.do_accept, l.half, l.iteration, l.new_lnp, l.status, l.clear_counts, l.chain_row, l.lnp_chain_row,
+                       l.do_propose, l.next_half, l.next_iteration, pa);
 }
 
 // The red/blue splits of `steps` consecutive iterations, one workgroup per (ensemble, iteration): perm_all[s][e][W].
@@ -133,26 +131,25 @@ void mtg_launch_split_all(const MtgEnsembleArgs &g, uint32_t iteration0, int ste
                        (size_t)g.W * (sizeof(uint64_t) + sizeof(int)), s, g, iteration0, perm_all);
 }
 
-void mtg_launch_sampler_spec(const MtgEnsembleArgs &g, int do_accept, uint32_t iteration, const double *new_lnp,
-                             const int32_t *status, int *clear_counts, double *chain_row, double *lnp_chain_row, int do_propose,
-                             uint32_t next_iteration, const MtgPrepArgs &pa, hipStream_t s)
+void mtg_launch_sampler_spec(const MtgEnsembleArgs &g, const MtgSamplerLaunch &l, const MtgPrepArgs &pa, hipStream_t s)
 {
     // (the split ranks W keys against each other: W^2 comparisons over the threads; a small ensemble is quicker through
     // the barriers of four waves than of sixteen)
     // (measured, iterations/s with 256 / 1024 threads: W = 32 44.1e3 / 43.0e3, W = 128 18.2e3 / 19.0e3, W = 256 6.8e3 / 7.7e3)
-    const int threads = do_propose && g.E <= 64 && g.W > 64 ? 1024 : 256;
+    const int threads = l.do_propose && g.E <= 64 && g.W > 64 ? 1024 : 256;
     // the ensemble's state in LDS for the length of the kernel (mtg_spec_both_lds): small ensembles whose splits were made
     // beforehand, between two solves of a run (MTG_SAMPLER_LDS=0 in an MTG_MEASURE build: never)
     static const bool lds_wanted = !(mtg_measure_env("MTG_SAMPLER_LDS") && atoi(mtg_measure_env("MTG_SAMPLER_LDS")) == 0);
-    const int state_in_lds = lds_wanted && do_accept && do_propose && g.perm_next && g.W / 2 <= 256 && g.W / 2 <= threads &&
+    const int state_in_lds = lds_wanted && l.do_accept && l.do_propose && g.perm_next && g.W / 2 <= 256 && g.W / 2 <= threads &&
                              (int64_t)g.W * g.P <= MTG_SPEC_LDS_DOUBLES ? 1 : 0;
     // keys (8 W), ranks (4 W), accept flags (4 W/2), padding to 8 bytes, then 3 W/2 proposals of P doubles; with the state
     // in LDS also W P coordinates, W log-probabilities, W ints of the next split
     size_t lds = (size_t)(g.W + (3 * g.W / 2 + 1) / 2 + 1) * sizeof(uint64_t) + (size_t)(3 * (g.W / 2)) * g.P * sizeof(double);
     // ... W ints of the next split (padded to doubles), and the iteration's random numbers: 6 H doubles + 3 H ints
     if (state_in_lds) lds += ((size_t)g.W * g.P + g.W + (g.W + 1) / 2 + 6 * (g.W / 2) + (3 * (g.W / 2) + 1) / 2) * sizeof(double);
-    hipLaunchKernelGGL(mtg_sampler_spec_kernel, dim3((unsigned)g.E), dim3(threads), lds, s, g, do_accept, iteration,
-                       new_lnp, status, clear_counts, chain_row, lnp_chain_row, do_propose, next_iteration, pa, state_in_lds);
+    hipLaunchKernelGGL(mtg_sampler_spec_kernel, dim3((unsigned)g.E), dim3(threads), lds, s, g, l.do_accept, l.iteration,
+                       l.new_lnp, l.status, l.clear_counts, l.chain_row, l.lnp_chain_row, l.do_propose, l.next_iteration, pa,
+                       state_in_lds);
 }
 
 void mtg_launch_initial_best(int E, int W, int P, const double *coords, const double *lnp, double *best_lnp,

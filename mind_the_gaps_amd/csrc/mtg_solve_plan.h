@@ -275,3 +275,81 @@ static inline bool mtg_plan_speculate(int tp_mode, int Jmodel, int64_t N, int64_
 {
     return tp_mode != 0 && Jmodel <= 6 && N >= 256 && rows3 <= (N >= 4096 ? (Jmodel <= 5 ? 512 : 256) : 1024);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The run plan of the device-resident sampler (mtg_capi.hip: mtg_ensemble_run)
+
+// The red/blue splits of a whole speculative run are made by ONE launch before it (mtg_launch_split_all) while they are
+// small: the sampler kernel of an iteration is one workgroup's chain of latencies and ranking W keys is 2-5 us of it.
+#define MTG_SPLITS_MAX_BYTES ((size_t)64 << 20)   // [steps][E][W] int32
+#define MTG_SPLITS_MAX_STEPS 65535                // the launch's grid: one row of workgroups per step
+
+struct MtgEnsembleRunPlan {
+    bool speculative = false;       // both half-steps of an iteration in one solve (where: mtg_plan_speculate)
+    bool splits_up_front = false;   // speculative: every split of the run made before it, perm_bytes of them
+    int64_t rows_per_solve = 0;     // E W/2 for a half-step, 3 E W/2 for a speculative iteration
+    int64_t solves = 0;             // 2 steps half-steps, or steps iterations
+    int64_t live_rows = 0;          // rows of a solve this rank evaluates, for the solver's kernel choice (0: all)
+    size_t perm_bytes = 0;
+};
+
+// spec_mode: mtg_set_speculation (0 never, 1 where it pays, 2 = 1 with the splits inside the sampler's launches);
+// shard_kind != 0: every half-step's rows [shard_lo, shard_hi) only (an empty share still counts as one live row:
+// 0 means all).  Walker-sharded runs do not speculate.
+static inline MtgEnsembleRunPlan mtg_plan_ensemble_run(int64_t E, int W, int64_t steps, int tp_mode, int spec_mode, int Jmodel,
+                                                       int64_t N, int shard_kind, int64_t shard_lo, int64_t shard_hi)
+{
+    MtgEnsembleRunPlan p;
+    const int64_t EH = E * (W / 2);
+    const bool sharded = shard_kind != 0;
+    p.speculative = steps > 0 && spec_mode != 0 && !sharded && mtg_plan_speculate(tp_mode, Jmodel, N, 3 * EH);
+    p.rows_per_solve = p.speculative ? 3 * EH : EH;
+    p.solves = p.speculative ? steps : 2 * steps;
+    p.live_rows = sharded ? (shard_hi > shard_lo ? shard_hi - shard_lo : 1) : 0;
+    if (p.speculative) {
+        const size_t bytes = (size_t)steps * (size_t)(E * W) * sizeof(int32_t);
+        p.splits_up_front = bytes <= MTG_SPLITS_MAX_BYTES && steps <= MTG_SPLITS_MAX_STEPS && spec_mode != 2;
+        if (p.splits_up_front) p.perm_bytes = bytes;
+    }
+    return p;
+}
+
+// What the sampler launch after solve k of a run does (k = -1: the priming launch before the first solve).  Solve k
+// reads the structure lists of bank k & 1; the launch accepts (iteration, half), clears that bank's counters and
+// proposes (next_iteration, next_half) into the other bank.  A speculative solve is a whole iteration: half = 0.
+struct MtgEnsembleStep {
+    int bank_used = -1, bank_next = 0;   // -1: no solve came before, nothing to accept or clear
+    int do_accept = 0, half = 0;
+    uint32_t iteration = 0;
+    int do_propose = 1, next_half = 0;
+    uint32_t next_iteration = 0;
+    int64_t chain_row = -1;              // the step of this run whose chain row the launch writes; -1: none
+    // slices [E][W] of the up-front splits: the accepted iteration's and the proposed one's (-1: the split made inside
+    // the launch, in the ensembles' own buffer)
+    int64_t perm = -1, perm_next = -1;
+};
+
+static inline MtgEnsembleStep mtg_ensemble_step(const MtgEnsembleRunPlan &plan, int64_t k, int64_t steps, uint32_t iteration0)
+{
+    MtgEnsembleStep st;
+    st.next_iteration = iteration0;
+    if (k >= 0) {
+        const int per = plan.speculative ? 1 : 2;   // solves per iteration
+        const int64_t it = k / per;
+        const bool closes = k % per == per - 1;      // the iteration is complete after this accept
+        st.bank_used = (int)(k & 1);
+        st.bank_next = st.bank_used ^ 1;
+        st.do_accept = 1;
+        st.half = (int)(k % per);
+        st.iteration = iteration0 + (uint32_t)it;
+        st.do_propose = k + 1 < plan.solves ? 1 : 0;
+        st.next_half = closes ? 0 : 1;
+        st.next_iteration = closes ? st.iteration + 1 : st.iteration;
+        st.chain_row = closes ? it : -1;
+    }
+    if (plan.splits_up_front) {
+        st.perm = k;   // (one solve per iteration)
+        st.perm_next = k + 1 < steps ? k + 1 : -1;
+    }
+    return st;
+}

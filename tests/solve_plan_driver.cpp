@@ -1,6 +1,7 @@
 // Runs the solve planner (mind_the_gaps_amd/csrc/mtg_solve_plan.h) on the host for tests/test_solve_plan_cpu.py: one
 // case per line of standard input as key=value tokens, one line of the plan's decisions per case.  The catalogue is a
-// stub with the compiled ranges of the library; `no=<shape>` takes one kind of kernel out of it.
+// stub with the compiled ranges of the library; `no=<shape>` takes one kind of kernel out of it.  `run=1` asks for the
+// sampler's run plan instead, `sched=1` for that plan's whole schedule, from the priming launch to the last solve.
 #include "mtg_solve_plan.h"
 
 #include <iostream>
@@ -31,7 +32,8 @@ int main()
     std::string line;
     while (std::getline(std::cin, line)) {
         MtgPlanIn in;
-        bool spec = false;
+        bool spec = false, run = false, sched = false;
+        long long E = 1, W = 8, steps = 3, spec_mode = 1, shard = 0, lo = 0, hi = 0, iter0 = 0;
         g_missing.clear();
         std::istringstream tokens(line);
         std::string tok;
@@ -62,11 +64,36 @@ int main()
             else if (k == "gsize") in.tp_gsize = (int)x;
             else if (k == "chunk_target") in.tp_chunk_target = x;
             else if (k == "spec") spec = x != 0;
+            else if (k == "run") run = x != 0;
+            else if (k == "sched") sched = x != 0;
+            else if (k == "E") E = x;
+            else if (k == "W") W = x;
+            else if (k == "steps") steps = x;
+            else if (k == "spec_mode") spec_mode = x;
+            else if (k == "shard") shard = x;
+            else if (k == "lo") lo = x;
+            else if (k == "hi") hi = x;
+            else if (k == "iter0") iter0 = x;
             else { std::cerr << "unknown key " << k << "\n"; return 2; }
         }
         if (in.Bw == 0) in.Bw = in.B;
         if (spec) {
             std::cout << "spec=" << mtg_plan_speculate(in.tp_mode, in.nr0 + 2 * in.nc0, in.N, in.B) << "\n";
+            continue;
+        }
+        if (run || sched) {
+            const MtgEnsembleRunPlan r = mtg_plan_ensemble_run(E, (int)W, steps, in.tp_mode, (int)spec_mode, in.nr0 + 2 * in.nc0, in.N,
+                                                               (int)shard, lo, hi);
+            if (run)
+                std::cout << "speculative=" << r.speculative << " up_front=" << r.splits_up_front << " rows=" << r.rows_per_solve
+                          << " solves=" << r.solves << " live=" << r.live_rows << " perm_bytes=" << r.perm_bytes;
+            for (int64_t k = -1; sched && r.solves > 0 && k < r.solves; ++k) {   // (no solve: no priming launch either)
+                const MtgEnsembleStep st = mtg_ensemble_step(r, k, steps, (uint32_t)iter0);
+                std::cout << (k >= 0 ? " | " : "") << k << " " << st.bank_used << " " << st.bank_next << " " << st.do_accept << " "
+                          << st.half << " " << st.iteration << " " << st.do_propose << " " << st.next_half << " "
+                          << st.next_iteration << " " << st.chain_row << " " << st.perm << " " << st.perm_next;
+            }
+            std::cout << "\n";
             continue;
         }
         const MtgSolvePlan p = mtg_plan_solve(in, g_cat);

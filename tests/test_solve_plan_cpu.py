@@ -1,7 +1,8 @@
 """The solve planner (mind_the_gaps_amd/csrc/mtg_solve_plan.h) on the host: tests/solve_plan_driver.cpp, compiled with
 g++ against the header alone, runs a boundary table -- one step on each side of every crossover, the mode switches,
 and shapes taken out of the catalogue -- and every row's family, sort, fan-out, rank-10 chunk count and kernel name
-are checked."""
+are checked.  The device sampler's run plan (mtg_plan_ensemble_run) gets a table of the same kind, and its schedule
+(mtg_ensemble_step) is compared launch by launch with rows written out by hand from the loops it replaced."""
 import os
 import subprocess
 
@@ -123,6 +124,63 @@ SPEC = [  # (tp_mode, nr0, nc0, N, rows3) -> mtg_ensemble_run speculates
     ((3, 1, 1, 4096, 100), 1), ((2, 1, 3, 4096, 100), 0),
 ]
 
+# mtg_plan_ensemble_run.  Defaults: one ensemble of 8 walkers (half-steps of 4 rows, 12 in a speculative iteration),
+# 3 steps, J = 3, N = 4096, modes auto, unsharded.  3 E W/2 is a multiple of three, so the row limits of
+# mtg_plan_speculate (1024, 512, 256; SPEC above has them to the row) are met from the nearest shapes on either side.
+RUN_DEFAULTS = dict(E=1, W=8, steps=3, tp=2, spec_mode=1, nr0=1, nc0=1, N=4096, shard=0, lo=0, hi=0)
+SEQ = dict(speculative=0, up_front=0, rows=4, solves=6, live=0, perm_bytes=0)
+RUN = [
+    (dict(spec_mode=0), SEQ),
+    (dict(spec_mode=1), dict(speculative=1, up_front=1, rows=12, solves=3, live=0, perm_bytes=3 * 8 * 4)),
+    (dict(spec_mode=2), dict(speculative=1, up_front=0, rows=12, solves=3, live=0, perm_bytes=0)),
+    (dict(tp=0), SEQ),
+    (dict(steps=0), dict(speculative=0, up_front=0, rows=4, solves=0, perm_bytes=0)),
+    (dict(steps=1), dict(speculative=1, up_front=1, solves=1, perm_bytes=32)),
+    # the splits up front: one row of workgroups per step, 64 MiB at the most
+    (dict(steps=65535), dict(speculative=1, up_front=1, solves=65535, perm_bytes=65535 * 32)),
+    (dict(steps=65536), dict(speculative=1, up_front=0, solves=65536, perm_bytes=0)),
+    (dict(N=256, W=512, steps=32768), dict(speculative=1, up_front=1, rows=768, perm_bytes=64 << 20)),
+    # (4 bytes over takes an odd number of walkers, which mtg_ensemble_init refuses and the planner only multiplies)
+    (dict(N=256, W=257, steps=65281), dict(speculative=1, up_front=0, rows=384, perm_bytes=0)),
+    # where speculation pays (mtg_plan_speculate): rows, rank, length
+    (dict(N=256, E=11, W=62), dict(speculative=1, rows=1023, solves=3)),
+    (dict(N=256, E=18, W=38), dict(speculative=0, rows=342, solves=6)),              # 3 x 342 = 1026
+    (dict(nc0=2, E=10, W=34), dict(speculative=1, rows=510)),
+    (dict(nc0=2, E=9, W=38), dict(speculative=0, rows=171)),                          # 3 x 171 = 513
+    (dict(nr0=2, nc0=2), dict(speculative=1, rows=12)),                               # J = 6
+    (dict(nr0=2, nc0=2, E=5, W=34), dict(speculative=1, rows=255)),
+    (dict(nr0=2, nc0=2, E=2, W=86), dict(speculative=0, rows=86)),                    # 3 x 86 = 258
+    (dict(nr0=1, nc0=3), SEQ),                                                        # J = 7
+    (dict(N=256), dict(speculative=1)),
+    (dict(N=255), SEQ),
+    # walker sharding: sequential, the solver sees this rank's rows, an empty share as one
+    (dict(shard=2, lo=0, hi=2), dict(SEQ, live=2)),
+    (dict(shard=1, lo=2, hi=4), dict(SEQ, live=2)),
+    (dict(shard=2, lo=4, hi=4), dict(SEQ, live=1)),
+]
+
+# mtg_ensemble_step from the priming launch (k = -1) to the last solve, the ensembles at iteration 10 when the run begins:
+# (k, bank used, bank filled next, do_accept, half, iteration, do_propose, next_half, next_iteration, chain row, slice of
+# the up-front splits for perm, for perm_next), -1 for none.  Written out from the two loops mtg_ensemble_run had: the
+# priming launch passes iteration 0; the sequential form flips the bank after every half-step and writes a chain row
+# after the second; the last launch of a run proposes nothing and has no perm_next.
+PRIME = (-1, -1, 0, 0, 0, 0, 1, 0, 10, -1, -1, -1)
+SCHEDULES = [
+    (dict(spec_mode=0), [PRIME,
+                         (0, 0, 1, 1, 0, 10, 1, 1, 10, -1, -1, -1), (1, 1, 0, 1, 1, 10, 1, 0, 11, 0, -1, -1),
+                         (2, 0, 1, 1, 0, 11, 1, 1, 11, -1, -1, -1), (3, 1, 0, 1, 1, 11, 1, 0, 12, 1, -1, -1),
+                         (4, 0, 1, 1, 0, 12, 1, 1, 12, -1, -1, -1), (5, 1, 0, 1, 1, 12, 0, 0, 13, 2, -1, -1)]),
+    (dict(spec_mode=1), [(-1, -1, 0, 0, 0, 0, 1, 0, 10, -1, -1, 0),
+                         (0, 0, 1, 1, 0, 10, 1, 0, 11, 0, 0, 1), (1, 1, 0, 1, 0, 11, 1, 0, 12, 1, 1, 2),
+                         (2, 0, 1, 1, 0, 12, 0, 0, 13, 2, 2, -1)]),
+    (dict(spec_mode=2), [PRIME,
+                         (0, 0, 1, 1, 0, 10, 1, 0, 11, 0, -1, -1), (1, 1, 0, 1, 0, 11, 1, 0, 12, 1, -1, -1),
+                         (2, 0, 1, 1, 0, 12, 0, 0, 13, 2, -1, -1)]),
+    (dict(spec_mode=0, steps=1), [PRIME, (0, 0, 1, 1, 0, 10, 1, 1, 10, -1, -1, -1), (1, 1, 0, 1, 1, 10, 0, 0, 11, 0, -1, -1)]),
+    (dict(spec_mode=1, steps=1), [(-1, -1, 0, 0, 0, 0, 1, 0, 10, -1, -1, 0), (0, 0, 1, 1, 0, 10, 0, 0, 11, 0, 0, -1)]),
+    (dict(spec_mode=0, steps=0), []),
+]
+
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
@@ -160,3 +218,24 @@ def test_boundary_table(driver):
 def test_speculation(driver):
     outs = driver(["tp=%d nr0=%d nc0=%d N=%d B=%d spec=1" % args for args, _ in SPEC])
     assert outs == ["spec=%d" % want for _, want in SPEC]
+
+
+def run_line(inputs, what):
+    return " ".join("%s=%s" % kv for kv in dict(RUN_DEFAULTS, **inputs).items()) + " %s=1" % what
+
+
+def test_ensemble_run_plan(driver):
+    outs = driver([run_line(inputs, "run") for inputs, _ in RUN])
+    assert len(outs) == len(RUN)
+    for (inputs, want), out in zip(RUN, outs):
+        got = dict(tok.split("=") for tok in out.split())
+        for key, value in want.items():
+            assert got[key] == str(value), (inputs, key, got)
+
+
+def test_ensemble_schedule(driver):
+    outs = driver([run_line(dict(inputs, iter0=10), "sched") for inputs, _ in SCHEDULES])
+    assert len(outs) == len(SCHEDULES)
+    for (inputs, want), out in zip(SCHEDULES, outs):
+        got = [tuple(int(x) for x in row.split()) for row in out.split("|") if row.strip()]
+        assert got == want, (inputs, got)
