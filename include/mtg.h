@@ -57,6 +57,15 @@ extern "C" {
 
 #define MTG_MEAN_CONSTANT 0   /* celerite.modeling.ConstantModel(value)                 */
 #define MTG_MEAN_LINEAR 1     /* mind_the_gaps/models/mean_models.py:24-31 (slope, intercept) */
+/* The reference's profile means, parameters in the order of their parameter_names, values at the absolute time t:     */
+#define MTG_MEAN_SINE 2       /* mean_models.py:12-16 (constant, amplitude, frequency, phase):
+                                 constant + amplitude sin(frequency t + phase)                                          */
+#define MTG_MEAN_TWOSINE 3    /* mean_models.py:18-22 (constant, amplitude0, phase0, amplitude1, phase1, frequency):
+                                 constant + amplitude0 sin(frequency t + phase0) + amplitude1 sin(2 frequency t + phase1) */
+#define MTG_MEAN_GAUSSIAN 4   /* mean_models.py:6-10 (mean, sigma, amplitude, constant):
+                                 amplitude / (2 pi sigma) exp(-(t - mean)^2 / (2 sigma^2)) + constant -- the
+                                 normalisation is 2 pi sigma, NOT sqrt(2 pi) sigma: the reference's own, kept as is     */
+#define MTG_N_MEAN_KINDS 5
 
 #define MTG_MAX_TERMS 12
 #define MTG_MAX_PARAMS 40     /* full parameter vector: kernel + mean parameters        */
@@ -69,6 +78,8 @@ typedef struct mtg_ctx mtg_ctx;
 MTG_API int mtg_device_count(void);
 MTG_API const char *mtg_version(void);
 MTG_API int mtg_term_nparams(int kind);
+/* Parameters of a mean kind (1, 2, 4, 6, 4 for MTG_MEAN_CONSTANT .. MTG_MEAN_GAUSSIAN); -1 for an unknown kind. */
+MTG_API int mtg_mean_nparams(int kind);
 
 /*
  * Context = one GPU + its light curves + its model + workspaces.
@@ -129,7 +140,18 @@ MTG_API int mtg_set_lightcurves_device(mtg_ctx *ctx, int64_t N, int64_t L, const
  * The model: what `celerite.GP(kernel, mean=..., fit_mean=...)`
  * (gpmodelling.py:51) holds.  The FULL parameter vector is the kernel
  * parameters of every term in `+` order followed by the mean parameters
- * (1 for MTG_MEAN_CONSTANT, 2 for MTG_MEAN_LINEAR), PF entries in all.
+ * (mtg_mean_nparams(mean_kind) of them: 1 for MTG_MEAN_CONSTANT, 2 for
+ * MTG_MEAN_LINEAR, 4 / 6 / 4 for MTG_MEAN_SINE / _TWOSINE / _GAUSSIAN), PF
+ * entries in all.  free_index and bounds cover the mean parameters like any
+ * other, so part of a mean can be frozen.
+ * The profile means (MTG_MEAN_SINE, _TWOSINE, _GAUSSIAN) are evaluated by the
+ * one-lane sweep alone (mtg_kernels_mean.hip): mtg_loglike_batch[_device],
+ * mtg_loglike_coeffs, mtg_ensemble_* (sharded or not) and mtg_apply_inverse
+ * (which does not read the mean) work with them; mtg_predict, mtg_predict_at,
+ * mtg_gp_draw and mtg_loglike_grad return MTG_E_UNSUPPORTED (the host layer
+ * binds y - mean(t) with a zero mean for those, one theta at a time), and a
+ * context paired with mtg_pair_contexts launches alone.  A row whose mean is
+ * not finite at some sample (sigma = 0) gets MTG_ST_NONFINITE.
  *   kinds[nterms]      MTG_TERM_* tags
  *   term_extra[nterms] per-term constant (Matern32Term eps), may be NULL
  *   full_values[PF]    current value of every parameter (used for frozen ones)
@@ -186,7 +208,7 @@ MTG_API int mtg_loglike_batch_device(mtg_ctx *ctx, int64_t B, const double *d_th
  * coefficients are evaluated on the host (celerite_models.py:9,17 override
  * points).  All evaluations share one structure (jr real, jc complex terms).
  * a_real..d_comp: [B][jr] / [B][jc] host, jitter: [B] (NULL = 0),
- * mean_params: [B][1 or 2] (NULL = 0).
+ * mean_params: [B][mtg_mean_nparams(mean_kind)] (NULL = 0; a profile mean needs them).
  */
 MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const double *a_real,
                                const double *c_real, const double *a_comp, const double *b_comp,
@@ -206,6 +228,8 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
  * under 0 (one-lane sweep and its pipelined form, bit-identical to each other) and under 3 a row's result does not
  * depend on what else is in the batch -- what a job that splits its rows over several GPUs needs to reproduce the
  * one-GPU result exactly (ppp.protassov_test(reproducible=True)).
+ * A model with a profile mean (MTG_MEAN_SINE, _TWOSINE, _GAUSSIAN) runs on the one-lane sweep under every mode: a row's
+ * result does not depend on the batch it travels in, whatever this is set to.
  */
 MTG_API int mtg_set_time_parallel(mtg_ctx *ctx, int mode);
 /*

@@ -1,6 +1,7 @@
 // mtg_capi.hip -- host side of the C-ABI declared in include/mtg.h.
 // One context = one MI355X + resident light curves + model + workspaces.
 #include "mtg_device.h"
+#include "mtg_mean.h"
 #include "mtg_sim_plan.h"
 #include "mtg_solve_plan.h"
 #include "mtg_tp_scan.h"
@@ -446,6 +447,27 @@ int reserve_workspace(mtg_ctx *ctx, int64_t B, int nslots, int nsig)
     return MTG_OK;
 }
 
+// coefficient slots of a row of model m: the layout's, and a profile mean's further constants behind them (mtg_mean.h)
+int model_nslots(const MtgModel &m)
+{
+    return MtgCoefLayout{m.nr_max, m.nc_max}.nslots() + mtg_mean_extra_slots(m.mean_kind);
+}
+
+// the sweep of structure (nr, nc) for a model's mean kind
+mtg_solve_launcher find_sweep(int mean_kind, int nr, int nc, int last_b0 = 0)
+{
+    return mtg_mean_is_profile(mean_kind) ? mtg_find_mean_solver(mean_kind, nr, nc, last_b0) : mtg_find_solver(nr, nc, last_b0);
+}
+
+// the entries that read the mean on the device (predict, draw, gradient) know the constant and the linear mean only
+int refuse_profile_mean(mtg_ctx *ctx, const char *who)
+{
+    const int kind = ctx->model.mean_kind;
+    if (!mtg_mean_is_profile(kind)) return MTG_OK;
+    return fail(ctx, MTG_E_UNSUPPORTED, "%s: not available with mean kind %d (%s): bind y - mean(t) with a zero mean instead", who,
+                kind, mtg_mean_name(kind));
+}
+
 // every structure of the model (nr0 + 2k, nc0 - k) must have a compiled kernel; reserves the
 // coefficient workspace for B evaluations
 int check_model_workspace(mtg_ctx *ctx, int64_t B)
@@ -460,8 +482,7 @@ int check_model_workspace(mtg_ctx *ctx, int64_t B)
                         "no compiled kernel for %d real + %d complex terms (J=%d)", nr, nc,
                         nr + 2 * nc);
     }
-    MtgCoefLayout lay{m.nr_max, m.nc_max};
-    return reserve_workspace(ctx, B, lay.nslots(), nsig);
+    return reserve_workspace(ctx, B, model_nslots(m), nsig);
 }
 
 // arguments of the theta -> coefficients expansion into the context's workspace; nsig: structure lists to fill
@@ -508,7 +529,7 @@ int stage_rows(mtg_ctx *ctx, const char *who, int64_t B, const double *theta, co
     const MtgModel &m = ctx->model;
     const int P = m.P;
     const MtgCoefLayout lay{m.nr_max, m.nc_max};
-    int rc = reserve_workspace(ctx, B, lay.nslots(), 1);
+    int rc = reserve_workspace(ctx, B, model_nslots(m), 1);
     if (rc) return rc;
     HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
     HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
@@ -755,6 +776,7 @@ MtgPlanIn plan_input(const mtg_ctx *ctx, int64_t B, bool may_sort, const MtgSolv
     for (int i = 0; i < m.nterms; ++i) in.free_b = in.free_b || m.kinds[i] == MTG_TERM_COMPLEX4 || m.kinds[i] == MTG_TERM_BPL;
     in.in_window = sa.yv_bytes <= sa.window_bytes;
     in.cus = ctx->cus;
+    in.profile_mean = mtg_mean_is_profile(m.mean_kind);
     in.sweep_multi = measure_knob("MTG_SWEEP_MULTI", 1) != 0;
     in.sweep_fan_out = measure_knob("MTG_SWEEP_FANOUT", 1) != 0;
     in.tp_gsize = (int)measure_knob("MTG_TP_GSIZE", 0);
@@ -795,7 +817,7 @@ int launch_structures(mtg_ctx *ctx, const MtgSolvePlan &plan, MtgSolveArgs &sa, 
         const hipStream_t sk = plan.side[k] < 0 ? s : ctx->side[plan.side[k]];
         if (sk != s) HIP_TRY(ctx, hipStreamWaitEvent(sk, ctx->fork, 0));
         if (plan.kernel[k] == MTG_STRUCT_SWEEP) {
-            const int rc = sweep_launch(ctx, mtg_find_solver(nr, nc, m.last_b0), sa, B, k, sk);
+            const int rc = sweep_launch(ctx, find_sweep(m.mean_kind, nr, nc, m.last_b0), sa, B, k, sk);
             if (rc) return rc;
         } else {
             sa.solo = 0; sa.left_list = nullptr; sa.left_count = nullptr;
@@ -911,6 +933,8 @@ MTG_API int mtg_device_count(void)
 MTG_API const char *mtg_version(void) { return "mtg-hip 0.1 (gfx950)"; }
 
 MTG_API int mtg_term_nparams(int kind) { return nparams(kind); }
+
+MTG_API int mtg_mean_nparams(int kind) { return mtg_mean_nparams_of(kind); }
 
 MTG_API int mtg_structure_supported(int jr, int jc) { return mtg_find_solver(jr, jc) ? 1 : 0; }
 
@@ -1103,7 +1127,7 @@ MTG_API int mtg_set_model(mtg_ctx *ctx, int nterms, const int32_t *kinds, const 
     if (!ctx) return MTG_E_ARG;
     if (nterms <= 0 || nterms > MTG_MAX_TERMS || !kinds)
         return fail(ctx, MTG_E_ARG, "mtg_set_model: nterms must be in [1, %d]", MTG_MAX_TERMS);
-    if (mean_kind != MTG_MEAN_CONSTANT && mean_kind != MTG_MEAN_LINEAR)
+    if (mtg_mean_nparams_of(mean_kind) < 0)
         return fail(ctx, MTG_E_ARG, "mtg_set_model: unknown mean kind %d", mean_kind);
     MtgModel m;
     memset(&m, 0, sizeof m);
@@ -1133,7 +1157,7 @@ MTG_API int mtg_set_model(mtg_ctx *ctx, int nterms, const int32_t *kinds, const 
         m.last_b0 = kd == MTG_TERM_LORENTZIAN || kd == MTG_TERM_COMPLEX3 || kd == MTG_TERM_COSINUS;
         break;
     }
-    const int nmean = mean_kind == MTG_MEAN_LINEAR ? 2 : 1;
+    const int nmean = mtg_mean_nparams_of(mean_kind);
     if (PF != off + nmean)
         return fail(ctx, MTG_E_ARG, "mtg_set_model: PF = %d but the terms + mean hold %d parameters",
                     PF, off + nmean);
@@ -1158,7 +1182,7 @@ MTG_API int mtg_set_model(mtg_ctx *ctx, int nterms, const int32_t *kinds, const 
     m.nc_max = m.nc0;
     for (int k = 0; k <= m.nsho; ++k) {
         const int nr = m.nr0 + 2 * k, nc = m.nc0 - k;
-        if (!mtg_find_solver(nr, nc))
+        if (!find_sweep(mean_kind, nr, nc))
             return fail(ctx, MTG_E_UNSUPPORTED,
                         "mtg_set_model: no compiled kernel for %d real + %d complex terms (J = %d > %d?)",
                         nr, nc, nr + 2 * nc, MTG_MAX_J);
@@ -1250,11 +1274,14 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
         return fail(ctx, MTG_E_ARG, "mtg_loglike_coeffs: bad arguments");
     if ((jr > 0 && (!a_real || !c_real)) || (jc > 0 && (!a_comp || !b_comp || !c_comp || !d_comp)))
         return fail(ctx, MTG_E_ARG, "mtg_loglike_coeffs: NULL coefficient array");
-    if (mean_kind != MTG_MEAN_CONSTANT && mean_kind != MTG_MEAN_LINEAR)
+    if (mtg_mean_nparams_of(mean_kind) < 0)
         return fail(ctx, MTG_E_ARG, "mtg_loglike_coeffs: unknown mean kind %d", mean_kind);
+    const bool profile = mtg_mean_is_profile(mean_kind);
+    if (profile && !mean_params)
+        return fail(ctx, MTG_E_ARG, "mtg_loglike_coeffs: mean kind %d (%s) needs mean_params", mean_kind, mtg_mean_name(mean_kind));
     if (B == 0) return MTG_OK;
     if (B > INT32_MAX) return fail(ctx, MTG_E_ARG, "batch too large");
-    mtg_solve_launcher fn = mtg_find_solver(jr, jc);
+    mtg_solve_launcher fn = find_sweep(mean_kind, jr, jc);
     if (!fn)
         return fail(ctx, MTG_E_UNSUPPORTED, "no compiled kernel for %d real + %d complex terms", jr, jc);
     rc = check_lc_index(ctx, B, lc_index);
@@ -1262,15 +1289,16 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
     rc = use_device(ctx);
     if (rc) return rc;
     MtgCoefLayout lay{jr, jc};
-    rc = reserve_workspace(ctx, B, lay.nslots(), 1);
+    const int nslots = lay.nslots() + mtg_mean_extra_slots(mean_kind);
+    rc = reserve_workspace(ctx, B, nslots, 1);
     if (rc) return rc;
     const int64_t cs = ctx->cstride;
     CTX_STREAM(ctx, s);
     // host-side transpose [B][j] -> SoA columns, then one upload
-    const int nmean = mean_kind == MTG_MEAN_LINEAR ? 2 : 1;
-    double *h = (double *)malloc((size_t)cs * lay.nslots() * 8);
+    const int nmean = mtg_mean_nparams_of(mean_kind);
+    double *h = (double *)malloc((size_t)cs * nslots * 8);
     if (!h) return fail(ctx, MTG_E_ARG, "out of host memory");
-    memset(h, 0, (size_t)cs * lay.nslots() * 8);
+    memset(h, 0, (size_t)cs * nslots * 8);
     for (int64_t b = 0; b < B; ++b) {
         double asum = jitter ? jitter[b] : 0.0;
         for (int j = 0; j < jr; ++j) {
@@ -1291,8 +1319,15 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
         const double m0 = mean_params ? mean_params[b * nmean] : 0.0;
         h[lay.mean(0) * cs + b] = nmean == 2 ? m0 : 0.0;
         h[lay.mean(1) * cs + b] = nmean == 2 ? mean_params[b * nmean + 1] : m0;
+        if (profile) {   // the constants mtg_prepare_from derives on the device
+            const double *p = mean_params + b * nmean;
+            const MtgMeanConsts mc = mtg_mean_derive(mean_kind, p[0], p[1], p[2], p[3], nmean > 4 ? p[4] : 0.0, nmean > 5 ? p[5] : 0.0);
+            h[lay.mean(0) * cs + b] = 0.0;
+            h[lay.mean(1) * cs + b] = mc.level;
+            for (int i = 0; i < mtg_mean_extra_slots(mean_kind); ++i) h[lay.mean_extra(i) * cs + b] = mc.ex(i);
+        }
     }
-    hipError_t e = hipMemcpyAsync(ctx->coef.p, h, (size_t)cs * lay.nslots() * 8, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(ctx->coef.p, h, (size_t)cs * nslots * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     free(h);
     if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "coefficient upload failed: %s", hipGetErrorString(e));
@@ -1333,7 +1368,8 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
     sa.sig = nullptr;
     ctx->timed = true;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    mtg_struct_kernel_name(ctx->last_solver, sizeof ctx->last_solver, MTG_STRUCT_SWEEP, jr, jc, 0, " (coefficients)");
+    if (profile) mtg_mean_kernel_name(ctx->last_solver, sizeof ctx->last_solver, jr, jc, 0, " (coefficients)");
+    else mtg_struct_kernel_name(ctx->last_solver, sizeof ctx->last_solver, MTG_STRUCT_SWEEP, jr, jc, 0, " (coefficients)");
     rc = sweep_launch(ctx, fn, sa, B, 0, s);
     if (rc) return rc;
     HIP_TRY(ctx, hipGetLastError());
@@ -1675,7 +1711,8 @@ int EnsembleRun::check()
     s = own;
     EW = en.E * en.W;
     iteration0 = en.iteration;
-    plan = mtg_plan_ensemble_run(en.E, en.W, steps, ctx->tp_mode, ctx->spec_mode, ctx->model.nr0 + 2 * ctx->model.nc0, ctx->N,
+    // (a profile mean runs on the serial sweep alone: nothing to speculate for)
+    plan = mtg_plan_ensemble_run(en.E, en.W, steps, mtg_mean_is_profile(ctx->model.mean_kind) ? 0 : ctx->tp_mode, ctx->spec_mode, ctx->model.nr0 + 2 * ctx->model.nc0, ctx->N,
                                  en.shard.kind, en.shard.lo, en.shard.hi);
     return MTG_OK;
 }
@@ -2087,7 +2124,7 @@ int SimCall::stage()
     const MtgModel &m = psd_table ? m0 : ctx->model;
     P = m.P;
     const MtgCoefLayout lay{m.nr_max, m.nc_max};
-    int rc = reserve_workspace(ctx, S, lay.nslots() > 4 ? lay.nslots() : 4, 1);
+    int rc = reserve_workspace(ctx, S, model_nslots(m) > 4 ? model_nslots(m) : 4, 1);   // (the expansion writes a profile mean's constants too; nothing here reads a mean)
     if (rc) return rc;
     CTX_STREAM(ctx, st);
     s = st;
@@ -2319,6 +2356,7 @@ MTG_API int mtg_predict(mtg_ctx *ctx, int64_t B, const double *theta, const int3
     if (rc) return rc;
     if (B <= 0 || !mu || !var || !status || (!theta && ctx->model.P > 0))
         return fail(ctx, MTG_E_ARG, "mtg_predict: bad arguments");
+    if ((rc = refuse_profile_mean(ctx, "mtg_predict"))) return rc;
     rc = check_lc_index(ctx, B, lc_index);
     if (rc) return rc;
     rc = use_device(ctx);
@@ -2355,6 +2393,7 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
     if (rc) return rc;
     if (B <= 0 || M <= 0 || !ts || !mu || !status || (!theta && ctx->model.P > 0))
         return fail(ctx, MTG_E_ARG, "mtg_predict_at: bad arguments");
+    if ((rc = refuse_profile_mean(ctx, "mtg_predict_at"))) return rc;
     rc = check_lc_index(ctx, B, lc_index);
     if (rc) return rc;
     bool ascending = true;
@@ -2431,6 +2470,7 @@ MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int3
     if (rc) return rc;
     if (B <= 0 || !y || !status || (!theta && ctx->model.P > 0))
         return fail(ctx, MTG_E_ARG, "mtg_gp_draw: bad arguments");
+    if ((rc = refuse_profile_mean(ctx, "mtg_gp_draw"))) return rc;
     rc = check_lc_index(ctx, B, lc_index);
     if (rc) return rc;
     rc = use_device(ctx);
@@ -2476,6 +2516,7 @@ MTG_API int mtg_loglike_grad(mtg_ctx *ctx, int64_t B, const double *theta, const
     if (rc) return rc;
     const int P = ctx->model.P;
     if (B <= 0 || !theta || !out || !grad || !status) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: bad arguments");
+    if ((rc = refuse_profile_mean(ctx, "mtg_loglike_grad"))) return rc;
     if (P <= 0) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: the model has no free parameter");
     rc = check_lc_index(ctx, B, lc_index);
     if (rc) return rc;

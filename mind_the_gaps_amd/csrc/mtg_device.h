@@ -42,6 +42,7 @@ struct MtgModel {
 // lane e reads/writes coef[slot * stride + e] (coalesced).  Slots:
 //   a_real[nr_max] c_real[nr_max] a_comp[nc_max] b_comp[nc_max] c_comp[nc_max]
 //   d_comp[nc_max] asum(= sum a + jitter) mean_slope mean_intercept jitter
+// and, for a model with a profile mean only (mtg_mean.h), that mean's further per-row constants after them
 struct MtgCoefLayout {
     int nr_max, nc_max;
     __host__ __device__ int ar(int j) const { return j; }
@@ -54,6 +55,8 @@ struct MtgCoefLayout {
     __host__ __device__ int mean(int i) const { return 2 * nr_max + 4 * nc_max + 1 + i; }
     __host__ __device__ int jit() const { return 2 * nr_max + 4 * nc_max + 3; }
     __host__ __device__ int nslots() const { return 2 * nr_max + 4 * nc_max + 4; }
+    // profile means (MTG_MEAN_SINE, _TWOSINE, _GAUSSIAN): constant i of mtg_mean_derive, behind every slot above
+    __host__ __device__ int mean_extra(int i) const { return nslots() + i; }
 };
 
 struct MtgPrepArgs {
@@ -210,6 +213,8 @@ static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivi
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);
+// The same sweep with a profile mean subtracted inside the step (mtg_kernels_mean.hip): one table per mean kind
+mtg_solve_launcher mtg_find_mean_solver(int mean_kind, int nr, int nc, int last_b0 = 0);
 // Time-parallel (one wave per evaluation) instantiations, J <= 6 (mtg_timeparallel.hip); the
 // launcher's second argument is the number of evaluations.
 mtg_solve_launcher mtg_find_tp_solver(int nr, int nc);

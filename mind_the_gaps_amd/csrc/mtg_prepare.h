@@ -6,6 +6,7 @@
 // indices are appended to their structure's list with wave-aggregated atomics.
 #pragma once
 #include "mtg_device.h"
+#include "mtg_mean.h"
 
 #include <math.h>
 
@@ -148,8 +149,19 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
         c[lay.asum() * cs] = asum;
         c[lay.jit() * cs] = jit;
         // mean(t) = slope * t + intercept; a constant mean is slope 0 (exactly the value)
-        c[lay.mean(0) * cs] = m.mean_kind == MTG_MEAN_LINEAR ? par(m.nk) : 0.0;
-        c[lay.mean(1) * cs] = m.mean_kind == MTG_MEAN_LINEAR ? par(m.nk + 1) : par(m.nk);
+        double slope = m.mean_kind == MTG_MEAN_LINEAR ? par(m.nk) : 0.0;
+        double icpt = m.mean_kind == MTG_MEAN_LINEAR ? par(m.nk + 1) : par(m.nk);
+        if (mtg_mean_is_profile(m.mean_kind)) {
+            // a profile mean: slope 0, its constant level as the intercept, its further constants behind the last slot
+            const int np = mtg_mean_nparams_of(m.mean_kind);
+            const MtgMeanConsts mc = mtg_mean_derive(m.mean_kind, par(m.nk), par(m.nk + 1), par(m.nk + 2), par(m.nk + 3),
+                                                     np > 4 ? par(m.nk + 4) : 0.0, np > 5 ? par(m.nk + 5) : 0.0);
+            slope = 0.0;
+            icpt = mc.level;
+            for (int i = 0; i < mtg_mean_extra_slots(m.mean_kind); ++i) c[lay.mean_extra(i) * cs] = mc.ex(i);
+        }
+        c[lay.mean(0) * cs] = slope;
+        c[lay.mean(1) * cs] = icpt;
     }
 
     if (a.sig && live) a.sig[e] = nover;

@@ -100,6 +100,7 @@ struct MtgPlanIn {
     bool free_b = false;            // a term with a free b (ComplexTerm with four parameters, BendingPowerlaw)
     bool in_window = true;          // the resident set within one buffer descriptor's reach (yv_bytes <= window_bytes)
     int cus = 0;                    // compute units of the device
+    bool profile_mean = false;      // the model's mean is a profile (MTG_MEAN_SINE, _TWOSINE, _GAUSSIAN): the one-lane sweep only
     // MTG_MEASURE knobs, read from the environment by the caller (shipped builds: these values)
     bool sweep_multi = true;        // MTG_SWEEP_MULTI=0: one launch per structure even where the one-launch kernel exists
     bool sweep_fan_out = true;      // MTG_SWEEP_FANOUT=0: the serial sweep's structures one after the other
@@ -149,6 +150,13 @@ static inline void mtg_struct_kernel_name(char *buf, size_t n, MtgStructKernel k
     else snprintf(buf, n, "mtg_solve_kernel<%d,%d,%d>%s", nr, nc, uses_b0, what);
 }
 
+// the same for the sweep with a profile mean (mtg_kernels_mean.hip)
+static inline void mtg_mean_kernel_name(char *buf, size_t n, int nr, int nc, int uses_b0, const char *what)
+{
+    if (nr + nc == 0) snprintf(buf, n, "mtg_white_mean_kernel%s", what);
+    else snprintf(buf, n, "mtg_solve_mean_kernel<%d,%d,%d>%s", nr, nc, uses_b0, what);
+}
+
 static inline MtgSolvePlan mtg_plan_solve(const MtgPlanIn &in, const MtgCatalogue &cat)
 {
     MtgSolvePlan p;
@@ -179,6 +187,10 @@ static inline MtgSolvePlan mtg_plan_solve(const MtgPlanIn &in, const MtgCatalogu
     // batch (mtg_tp_big_chunks), so under mode 3 such a model keeps the serial sweep
     if (in.tp_mode == 3 && J > 6) small_ok = false;
     if (J == 0) small_ok = false;  // a white kernel: nothing to parallelise over time (mtg_white_kernel)
+    // A profile mean is known to the one-lane sweep of mtg_kernels_mean.hip alone: a launch per structure whatever
+    // tp_mode and pipe_mode say -- no time-parallel kernel, no pipeline (hence no pairing), no multi launch -- so that
+    // a row's bits never depend on the batch; sorting, the window logic and the fan-out work as for the plain sweep.
+    if (in.profile_mean) small_ok = false;
     if (small_ok && J > 6) {
         for (int k = 0; k < nsig; ++k)
             if (!cat.tp(in.nr0 + 2 * k, in.nc0 - k)) small_ok = false;
@@ -217,7 +229,7 @@ static inline MtgSolvePlan mtg_plan_solve(const MtgPlanIn &in, const MtgCatalogu
     // Between the time-parallel kernels' range and ~one wave per SIMD the serial sweep is one lone wave per 64 rows on
     // a fraction of the SIMDs, N dependent steps of ~166 instructions: the pipelined form puts the generators of those
     // rows on a second wave (mtg_kernels_pipe.hip) -- one workgroup of 128 rows per CU, all resident at once.
-    const bool pipe = !small_ok && in.pipe_mode != 0 && in.N >= 64 && in.in_window &&
+    const bool pipe = !small_ok && !in.profile_mean && in.pipe_mode != 0 && in.N >= 64 && in.in_window &&
                       (in.pipe_mode == 1 || (in.N >= 256 && in.B <= (int64_t)MTG_PIPE_ROWS_PER_CU * in.cus)) &&
                       cat.pipe(in.nr0, in.nc0, nsig, in.last_b0);
     // The serial sweep reads each lane's own light curve: sort the evaluations by (structure, light curve) unless the
@@ -234,7 +246,7 @@ static inline MtgSolvePlan mtg_plan_solve(const MtgPlanIn &in, const MtgCatalogu
         snprintf(p.name, sizeof p.name, "mtg_pipe_kernel<%d,%d,%d,%d>", in.nr0, in.nc0, nsig, b0);
         return p;
     }
-    if (p.sort && nsig > 1 && in.in_window && in.sweep_multi && cat.multi(in.nr0, in.nc0, nsig, in.last_b0)) {
+    if (p.sort && nsig > 1 && !in.profile_mean && in.in_window && in.sweep_multi && cat.multi(in.nr0, in.nc0, nsig, in.last_b0)) {
         p.family = MTG_SOLVE_MULTI;
         snprintf(p.name, sizeof p.name, "mtg_solve_kernel_multi<%d,%d,%d,%d>", in.nr0, in.nc0, nsig, b0);
         return p;
@@ -254,7 +266,8 @@ static inline MtgSolvePlan mtg_plan_solve(const MtgPlanIn &in, const MtgCatalogu
         if (!cat.sweep(nr, nc, in.last_b0)) continue;   // not launched, not joined
         if (!small_ok || !cat.tp(nr, nc)) p.kernel[k] = MTG_STRUCT_SWEEP;
         else p.kernel[k] = wide && cat.tp_wide(nr, nc) ? MTG_STRUCT_TP_WIDE : MTG_STRUCT_TP;
-        if (k == 0) mtg_struct_kernel_name(p.name, sizeof p.name, p.kernel[0], nr, nc, cat.sweep_uses_b0(nr, nc, in.last_b0), "");
+        if (k == 0 && in.profile_mean) mtg_mean_kernel_name(p.name, sizeof p.name, nr, nc, cat.sweep_uses_b0(nr, nc, in.last_b0), "");
+        else if (k == 0) mtg_struct_kernel_name(p.name, sizeof p.name, p.kernel[0], nr, nc, cat.sweep_uses_b0(nr, nc, in.last_b0), "");
     }
     return p;
 }

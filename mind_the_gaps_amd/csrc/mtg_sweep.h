@@ -21,9 +21,17 @@ __host__ __device__ constexpr int mtg_waves_for(int J)
     return (J <= 2 ? 5 : J <= 3 ? 3 : J <= 8 ? 2 : 1) + MTG_WAVES_BIAS;
 }
 
+// The mean the sweep subtracts inside its step, as a type the lane derives from.  The affine mean is the sweep's own
+// expression on the lane's slope and intercept (an empty base: the lane is what it was), and a.has_mean says whether a
+// launch has one (or a jitter) at all; a profile mean (mtg_sweep_mean.h) sets `always`, holds its per-lane constants,
+// loads them from the row's coefficient column and gives its value at a sample's absolute time.
+struct MtgMeanAffine {
+    static constexpr bool always = false;
+};
+
 // Per-lane state of one evaluation, all statically indexed -> VGPRs.
-template <int NR, int NC>
-struct MtgLane {
+template <int NR, int NC, class Mean = MtgMeanAffine>
+struct MtgLane : Mean {
     static constexpr int J = NR + 2 * NC;
     double ar[NR > 0 ? NR : 1], cr[NR > 0 ? NR : 1];
     double ac[NC > 0 ? NC : 1], bc[NC > 0 ? NC : 1], cc[NC > 0 ? NC : 1], dc[NC > 0 ? NC : 1];
@@ -49,8 +57,10 @@ struct MtgLane {
 //         upload, and the model has no JitterTerm).
 //   NB0:  the last NB0 complex terms have b = 0 by construction (Lorentzian, three-parameter ComplexTerm,
 //         Cosinus): their U is a (cos, sin) -- a multiplication instead of a multiplication and a multiply-add.
-template <int NR, int NC, bool FAST, bool MEAN, int NB0 = 0, class Tab = MtgMathTablesT<(NC > 0)>>
-__device__ __forceinline__ void mtg_sweep(MtgLane<NR, NC> &L, const MtgSolveArgs &a, const double2 *yv_base,
+//   Mean: what `MEAN` subtracts (the lane's base, deduced from it): MtgMeanAffine, the default, is slope * t + intercept
+//         of the lane; a type with `always` set (mtg_sweep_mean.h) is evaluated in its place.
+template <int NR, int NC, bool FAST, bool MEAN, int NB0 = 0, class Tab = MtgMathTablesT<(NC > 0)>, class Mean = MtgMeanAffine>
+__device__ __forceinline__ void mtg_sweep(MtgLane<NR, NC, Mean> &L, const MtgSolveArgs &a, const double2 *yv_base,
                                           uint32_t yv_records, uint32_t yoff, const double2 *dxt_base,
                                           uint32_t dxt_records, uint32_t toff, const Tab *tab)
 {
@@ -130,6 +140,7 @@ __device__ __forceinline__ void mtg_sweep(MtgLane<NR, NC> &L, const MtgSolveArgs
         // the subtraction V - S U rides on the multiply-add chain and D needs no second pass over q
         double D = MEAN ? vc + L.jit : vc;
         double zn = MEAN ? yc - fma(L.slope, tc, L.icpt) : yc;
+        if constexpr (MEAN && Mean::always) zn = yc - L.value(tc, tab);   // a profile mean instead (mtg_sweep_mean.h)
 #pragma unroll
         for (int i = 0; i < J; ++i) {
             double w = V[i];
@@ -177,14 +188,14 @@ __device__ __forceinline__ void mtg_sweep(MtgLane<NR, NC> &L, const MtgSolveArgs
 
 // One evaluation, row `e` of the batch, on this lane: coefficients -> sweep -> lnL and status.  `tab` is the
 // workgroup's table set (any MtgMathTablesT that has what the structure needs).
-template <int NR, int NC, int NB0, class Tab>
+template <int NR, int NC, int NB0, class Tab, class Mean = MtgMeanAffine>
 __device__ __forceinline__ void mtg_solve_row(const MtgSolveArgs &a, int64_t e, const Tab *tabp)
 {
 #pragma clang fp contract(off)
     constexpr int J = NR + 2 * NC;  // celerite rank
     const Tab &tab = *tabp;
     // ---- coefficients of this evaluation -----------------------------------
-    MtgLane<NR, NC> L;
+    MtgLane<NR, NC, Mean> L;
     const double *cf = a.coef + e;
     const int64_t cs = a.cstride;
     double dmax = 0.0;
@@ -250,7 +261,11 @@ __device__ __forceinline__ void mtg_solve_row(const MtgSolveArgs &a, int64_t e, 
 
     // the table sincos of mtg_phase_step serves every lane of the wave while d_k * dx <= MTG_TRIG_FAST_MAX
     const bool fast = !__any(!(dmax * *a.dxmax <= MTG_TRIG_FAST_MAX));
-    if (fast) {
+    if constexpr (Mean::always) {
+        L.load(a, cf, cs);
+        if (fast) mtg_sweep<NR, NC, true, true, NB0>(L, a, yv_base, yv_rec, yoff, dxt_base, dxt_rec, toff, &tab);
+        else mtg_sweep<NR, NC, false, true, NB0>(L, a, yv_base, yv_rec, yoff, dxt_base, dxt_rec, toff, &tab);
+    } else if (fast) {
         if (a.has_mean) mtg_sweep<NR, NC, true, true, NB0>(L, a, yv_base, yv_rec, yoff, dxt_base, dxt_rec, toff, &tab);
         else mtg_sweep<NR, NC, true, false, NB0>(L, a, yv_base, yv_rec, yoff, dxt_base, dxt_rec, toff, &tab);
     } else {

@@ -20,7 +20,10 @@ LIB_PATH = os.environ.get("MTG_HIP_LIB") or os.path.join(_HERE, "libmtg_hip.so")
 # term kinds / mean kinds / status codes: numerically identical to include/mtg.h
 TERM_REAL, TERM_COMPLEX3, TERM_COMPLEX4, TERM_SHO, TERM_MATERN32, TERM_JITTER, \
     TERM_DRW, TERM_LORENTZIAN, TERM_COSINUS, TERM_BPL = range(10)
-MEAN_CONSTANT, MEAN_LINEAR = 0, 1
+MEAN_CONSTANT, MEAN_LINEAR, MEAN_SINE, MEAN_TWOSINE, MEAN_GAUSSIAN = range(5)
+# parameters of each mean kind (mtg_mean_nparams), in the order of the reference's parameter_names
+MEAN_NPARAMS = {MEAN_CONSTANT: 1, MEAN_LINEAR: 2, MEAN_SINE: 4, MEAN_TWOSINE: 6, MEAN_GAUSSIAN: 4}
+PROFILE_MEANS = (MEAN_SINE, MEAN_TWOSINE, MEAN_GAUSSIAN)     # evaluated by the one-lane sweep alone (csrc/mtg_kernels_mean.hip)
 ST_OK, ST_PRIOR, ST_NOTPD, ST_NONFINITE = 0, 1, 2, 3
 E_ARG, E_NODEVICE, E_HIP, E_STATE, E_UNSUPPORTED = -1, -2, -3, -4, -5
 
@@ -36,7 +39,7 @@ EXPORTS = (
     "mtg_chain_autocorr", "mtg_fft_warmup", "mtg_simulate_plan", "mtg_ensemble_restore", "mtg_set_sort", "mtg_set_pipeline", "mtg_set_stream_base", "mtg_set_speculation", "mtg_last_solver", "mtg_pair_contexts", "mtg_unpair_contexts", "mtg_pair_stats", "mtg_set_simulate_pairs", "mtg_set_simulate_transform", "mtg_set_simulate_pdf", "mtg_set_simulate_kraft", "mtg_set_simulate_pdf_draws", "mtg_simulate_pdf_report", "mtg_set_pair_patience", "mtg_chain_autocorr_plans_built",
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
-    "mtg_predict_at", "mtg_gp_draw", "mtg_loglike_grad",
+    "mtg_predict_at", "mtg_gp_draw", "mtg_loglike_grad", "mtg_mean_nparams",
 )
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
@@ -203,6 +206,8 @@ def load_library():
     lib.mtg_version.restype = ctypes.c_char_p
     lib.mtg_term_nparams.restype = c_int
     lib.mtg_term_nparams.argtypes = [c_int]
+    lib.mtg_mean_nparams.restype = c_int
+    lib.mtg_mean_nparams.argtypes = [c_int]
     lib.mtg_create.restype = c_vp
     lib.mtg_create.argtypes = [c_int]
     lib.mtg_create_on_slice.restype = c_vp
@@ -510,6 +515,9 @@ class Engine:
         jc = a_comp.shape[1] if a_comp.size else 0
         jit = _f64(jitter) if jitter is not None else None
         mp = np.atleast_2d(_f64(mean_params)) if mean_params is not None else None
+        # the library reads B rows of the kind's width (an unknown kind is its own error, MTG_E_ARG): never fewer values
+        if mp is not None and mp.size < B * MEAN_NPARAMS.get(int(mean_kind), 0):
+            raise ValueError("mean_params must hold [%d][%d] values for mean kind %d" % (B, MEAN_NPARAMS[int(mean_kind)], mean_kind))
         lc = None if lc_index is None else np.ascontiguousarray(lc_index, dtype=np.int32)
         out = np.empty(B, dtype=np.float64)
         status = np.empty(B, dtype=np.int32)

@@ -192,12 +192,12 @@ class LogProbEvaluator:
         if not model.device_terms:
             raise ValueError("batched evaluation needs device-expandable terms")
         if model.mean_kind is None:
-            raise NotImplementedError("only constant and linear mean models run on the device")
+            raise NotImplementedError("a mean model without mtg_mean_kind does not run on the device")
         eng = self._bind(model)
         return eng.loglike(theta, lc_index, add_prior=add_prior)
 
     def evaluate_coefficients(self, model, coeffs, jitter, mean_params, lc_index=None):
-        """Host-evaluated celerite coefficients [B][j]; mean_params [B][1 or 2] are the
+        """Host-evaluated celerite coefficients [B][j]; mean_params [B][engine.MEAN_NPARAMS[kind]] are the
         device-side mean parameters (0 for a frozen constant mean, see DeviceModel)."""
         eng = self._bind(model)
         ar, cr, ac, bc, cc, dc = coeffs
@@ -282,7 +282,7 @@ class GP(ModelSet):
         ev = self._ensure_evaluator(y)
         model = self._device_model()
         if model.mean_kind is None:
-            raise NotImplementedError("only constant and linear mean models run on the device")
+            raise NotImplementedError("a mean model without mtg_mean_kind does not run on the device")
         if model.device_terms:
             out, status = ev.evaluate(model, model.full[model.free_index][None, :], add_prior=False)
         else:
@@ -299,7 +299,8 @@ class GP(ModelSet):
         """``(lnL, d lnL / d theta)`` of the current parameter vector, the gradient by the free parameters in
         ``get_parameter_vector``'s order (celerite.GP.grad_log_likelihood): analytic, from one launch of the device's
         tangent sweep (``Engine.loglike_grad``).  A covariance that is not positive definite raises ``LinAlgError``, or
-        with ``quiet`` returns ``(-inf, zeros)`` as celerite does."""
+        with ``quiet`` returns ``(-inf, zeros)`` as celerite does.  The tangent sweep knows the constant and the linear
+        mean: a profile mean (sine, two sines, Gaussian) raises ``NotImplementedError``."""
         eng, model = self._bound_engine(y)
         out, grad, status = eng.loglike_grad(model.full[model.free_index][None, :], add_prior=False)
         if status[0] == _engine.ST_NOTPD:
@@ -353,12 +354,44 @@ class GP(ModelSet):
             out[keep], status[keep] = o, s
         return out, status
 
-    def _bound_engine(self, y):
+    def _bound_engine(self, y, profile_ok=False):
+        """(engine with ``y`` and the model bound, the model).  ``profile_ok``: the caller's device entry works under a
+        profile mean too (``apply_inverse``, which does not read the mean); the others know the constant and the linear
+        mean only, and ``predict`` / ``sample`` go through ``_zero_mean_engine`` instead."""
         ev = self._ensure_evaluator(y)
         model = self._device_model()
         if not model.device_terms or model.mean_kind is None:
-            raise NotImplementedError("needs device-expandable terms and a constant or linear mean")
+            raise NotImplementedError("needs device-expandable terms and a mean model with mtg_mean_kind")
+        if model.mean_kind in _engine.PROFILE_MEANS and not profile_ok:
+            raise NotImplementedError("not available on the device with the %s mean; it evaluates the likelihood, chains, "
+                                      "predict() and sample() only" % type(self.mean).__name__)
         return ev._bind(model), model
+
+    def _has_profile_mean(self):
+        return getattr(self.mean, "mtg_mean_kind", None) in _engine.PROFILE_MEANS
+
+    def _zero_mean_engine(self, y):
+        """A profile mean (sine, two sines, Gaussian) under the device entries that read the mean and know only the
+        constant and the linear one: the residual ``y - mean(t)`` at the current parameters is bound with a frozen
+        constant mean of zero, and the caller adds ``mean.get_value`` back on the host.  -> (engine, that model)."""
+        if self._t is None:
+            raise RuntimeError("you must call 'compute' first")
+        y = np.zeros(len(self._t)) if y is None else np.asarray(y, dtype=np.float64)
+        ev = self._ensure_evaluator(y - self.mean.get_value(self._t))
+        zero = ConstantModel(0.0)
+        zero.freeze_all_parameters()
+        model = DeviceModel(self.kernel, zero, zero.unfrozen_mask)
+        if not model.device_terms:
+            raise NotImplementedError("needs device-expandable terms")
+        return ev._bind(model), model
+
+    def _mean_engine(self, y):
+        """-> (engine, model, what to add to a device mean at times x)"""
+        if self._has_profile_mean():
+            eng, model = self._zero_mean_engine(y)
+            return eng, model, self.mean.get_value
+        eng, model = self._bound_engine(y)
+        return eng, model, lambda x: model.y_offset or 0.0
 
     @staticmethod
     def _raise_for(status):
@@ -373,7 +406,7 @@ class GP(ModelSet):
         y = np.asarray(y, dtype=np.float64)
         if y.shape[0] != len(self._t):
             raise ValueError("dimension mismatch")
-        eng, model = self._bound_engine(self._y_bound if self._y_bound is not None else np.zeros(len(self._t)))
+        eng, model = self._bound_engine(self._y_bound if self._y_bound is not None else np.zeros(len(self._t)), profile_ok=True)
         x, status = eng.apply_inverse(model.full[model.free_index], y)
         self._raise_for(status)
         return x
@@ -390,12 +423,16 @@ class GP(ModelSet):
         n = 1 if size is None else int(size)
         if n == 0:
             return np.empty((0, len(self._t)))          # celerite: an empty [0][N] array
-        eng, model = self._bound_engine(self._y_bound if self._y_bound is not None else np.zeros(len(self._t)))
+        # (a profile mean: drawn around zero, the mean added on the host; only sigma^2 of the bound light curve is read)
+        if self._has_profile_mean():
+            eng, model, mean_at = self._mean_engine(None)
+        else:
+            eng, model, mean_at = self._mean_engine(self._y_bound if self._y_bound is not None else np.zeros(len(self._t)))
         theta = np.tile(model.full[model.free_index][None, :], (n, 1))
         normals = np.random.randn(n, len(self._t)) if seed is None else None
         y, status = eng.gp_draw(theta, seed=0 if seed is None else int(seed), normals=normals)
         self._raise_for(status[0])                      # every row has the same theta, hence the same status
-        y += model.y_offset or 0.0
+        y += mean_at(self._t)
         return y[0] if size is None else y
 
     def predict(self, y, t=None, return_cov=True, return_var=False):
@@ -410,18 +447,19 @@ class GP(ModelSet):
         N_* x N_* object by definition, is assembled on the host from celerite's own expression
         ``cov = K_** - K_* K^-1 K_*^T`` over ``apply_inverse`` (one device call with 1 + N_*
         right-hand sides).  Like celerite's, the variances are those of the noise-free process (no
-        jitter, no measurement errors)."""
-        eng, model = self._bound_engine(y)
+        jitter, no measurement errors).  Under a profile mean (sine, two sines, Gaussian) the device sees the residual
+        ``y - mean(t)`` with a zero mean and ``mean.get_value`` is added back here."""
+        eng, model, mean_at = self._mean_engine(y)
         if t is None and (return_var or not return_cov):
             mu, var, status = eng.predict(model.full[model.free_index][None, :])
             self._raise_for(status[0])
-            mu = mu[0] + (model.y_offset or 0.0)
+            mu = mu[0] + mean_at(self._t)
             return (mu, var[0]) if return_var else mu
         if return_var or not return_cov:
             xs = np.atleast_1d(np.asarray(t, dtype=np.float64))
             mu, var, status = eng.predict_at(model.full[model.free_index][None, :], xs, return_var=return_var)
             self._raise_for(status[0])
-            mu = mu[0] + (model.y_offset or 0.0)
+            mu = mu[0] + mean_at(xs)
             return (mu, var[0]) if return_var else mu
         y = np.asarray(y, dtype=np.float64)
         xs = self._t if t is None else np.atleast_1d(np.asarray(t, dtype=np.float64))

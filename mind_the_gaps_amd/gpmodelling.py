@@ -25,7 +25,7 @@ from . import engine as _engine
 from . import walkers as _walkers
 from .gp import GP, LinAlgError
 from .lightcurves import GappyLightcurve
-from .modeling import ConstantModel
+from .modeling import ConstantModel, Model
 from .models import GaussianModel, LinearModel
 from .device_sampler import DeviceEnsembleSampler
 from .sampler import EnsembleSampler
@@ -39,20 +39,24 @@ class GPModelling:
     meanmodels = ["linear", "constant", "gaussian"]
 
     def __init__(self, lightcurve: GappyLightcurve, kernel, mean_model: str = None, device: int = 0,
-                 quiet: bool = False, random_state=None, own_engine: bool = False):
+                 quiet: bool = False, random_state=None, own_engine: bool = False, meanmodel=None):
         """GP of ``kernel`` (a ``mind_the_gaps_amd.terms.Term``) on ``lightcurve``, factorised once with
         ``yerr = dy + 1e-12`` as the reference does (gpmodelling.py:54).
 
         ``mean_model``: None keeps the mean frozen at the light curve's average; "constant", "linear" or
         "gaussian" name a mean that is fitted along with the kernel (the table in ``_build_mean_model``).
-        New and optional: ``device`` = GPU ordinal; ``quiet`` = a covariance that is not positive definite gives
+        New and optional: ``mean_model`` (or, by the name ``_build_mean_model`` gives it, ``meanmodel``) may also be a
+        mean-model INSTANCE -- ``models.SineModel``, ``TwoSineModel``, ``GaussianModel``, ``LinearModel`` --, which is
+        then fitted along with the kernel from its own starting values within its own bounds; ``device`` = GPU ordinal; ``quiet`` = a covariance that is not positive definite gives
         -inf instead of ``LinAlgError`` (the reference raises, gpmodelling.py:152); ``random_state`` = a
         ``numpy.random.RandomState`` for the walkers' starting points and the device sampler's key instead of numpy's
         global generator (the reference's and emcee's source; a private one lets two models be sampled from two threads
         with the numbers ``np.random.seed`` would have given each); ``own_engine`` = a device context of this object's
         own (``gp.release_engine()`` gives it back)."""
         self._lightcurve = lightcurve
-        meanmodel, fit_mean = self._build_mean_model(mean_model)
+        if meanmodel is not None and mean_model is not None:
+            raise ValueError("give the mean model once, as mean_model or as meanmodel")
+        meanmodel, fit_mean = self._build_mean_model(mean_model if meanmodel is None else meanmodel)
         self.gp = GP(kernel, mean=meanmodel, fit_mean=fit_mean, device=device, own_engine=own_engine)
         self._random = random_state
         self.gp.compute(self._lightcurve.times, np.asarray(self._lightcurve.dy, dtype=np.float64) + 1e-12)
@@ -90,7 +94,9 @@ class GPModelling:
                    "linear": ("_linear_mean", True), "gaussian": ("_gaussian_mean", True)}
 
     def _build_mean_model(self, meanmodel: str = None):
-        """(mean model, fit_mean) for a mean kind (see the table above)."""
+        """(mean model, fit_mean) for a mean kind (see the table above), or for a mean-model instance: itself, fitted."""
+        if isinstance(meanmodel, Model):
+            return meanmodel, True
         kind = meanmodel if meanmodel is None else meanmodel.lower()
         if kind not in self._MEAN_KINDS:
             raise ValueError("Input mean model %s not implemented! Only \n %s \n are available"
@@ -171,6 +177,8 @@ class GPModelling:
             return "a term has no device expansion"
         if model.mean_kind is None:
             return "the mean model is evaluated on the host"
+        if model.mean_kind in _engine.PROFILE_MEANS:
+            return "the device's tangent sweep has no gradient by the parameters of the %s mean" % type(self.gp.mean).__name__
         try:
             self.gp.log_probability_grad_batch(np.asarray(x, dtype=np.float64)[None, :], self._y, add_prior=False)
         except _engine.EngineError as exc:
@@ -325,7 +333,7 @@ class GPModelling:
         ev = self.gp._ensure_evaluator(self._y)
         model = self.gp._device_model()
         if not model.device_terms or model.mean_kind is None:
-            raise ValueError("the device sampler needs device-expandable terms and a constant or linear mean")
+            raise ValueError("the device sampler needs device-expandable terms and a mean model with mtg_mean_kind")
         seed = None if self._random is None else int(self._random.randint(0, 2 ** 62))   # (None: numpy's global generator)
         return DeviceEnsembleSampler(lambda: ev._bind(model), walkers, self._ndim, n_ensembles=1,
                                      shard_group=shard_group, seed=seed)
@@ -363,11 +371,24 @@ class GPModelling:
             parameters = self.max_parameters if self._mcmc_samples is not None else self.gp.get_parameter_vector()
         parameters = np.asarray(parameters, dtype=np.float64)
         theta = np.atleast_2d(parameters)
-        eng, model = self.gp._bound_engine(self._lightcurve.y)
-        mu, var, status = eng.predict_at(theta, times)
-        for st in status:
-            self.gp._raise_for(st)
-        mu += model.y_offset or 0.0
+        if self.gp._has_profile_mean():
+            # the device's entry knows the constant and the linear mean: one vector at a time, the residual
+            # y - mean(t) at that vector bound with a zero mean and the mean added back (GP.predict)
+            saved = self.gp.get_parameter_vector()
+            try:
+                rows = []
+                for b in range(len(theta)):
+                    self.gp.set_parameter_vector(theta[b])
+                    rows.append(self.gp.predict(self._lightcurve.y, t=times, return_var=True))
+            finally:
+                self.gp.set_parameter_vector(saved)
+            mu, var = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+        else:
+            eng, model = self.gp._bound_engine(self._lightcurve.y)
+            mu, var, status = eng.predict_at(theta, times)
+            for st in status:
+                self.gp._raise_for(st)
+            mu += model.y_offset or 0.0
         if include_noise:
             saved = self.gp.get_parameter_vector()
             try:
