@@ -20,6 +20,7 @@
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
+#include <initializer_list>
 #include <memory>
 #include <chrono>
 #include <mutex>
@@ -519,43 +520,6 @@ int check_lc_index(mtg_ctx *ctx, int64_t B, const int32_t *lc_index)
     return MTG_OK;
 }
 
-// The prologue of the per-row entries (`who`: mtg_predict, mtg_predict_at, mtg_gp_draw, mtg_loglike_grad, mtg_apply_inverse): workspace
-// and staging reserved for B rows, theta and lc_index uploaded, theta expanded on stream s -- the prior's verdict in
-// ctx->status, the structure of every row in ctx->sig -- and the head of the kernels' arguments filled for the whole
-// batch.  (ctx->sig, like ctx->coef, is rewritten by every expansion and read by nothing before the next one.)
-int stage_rows(mtg_ctx *ctx, const char *who, int64_t B, const double *theta, const int32_t *lc_index, int add_prior,
-               hipStream_t s, MtgRowArgs &head)
-{
-    const MtgModel &m = ctx->model;
-    const int P = m.P;
-    const MtgCoefLayout lay{m.nr_max, m.nc_max};
-    int rc = reserve_workspace(ctx, B, model_nslots(m), 1);
-    if (rc) return rc;
-    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
-    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
-    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
-    hipError_t e = hipSuccess;
-    const int32_t *d_lc = nullptr;
-    if (P > 0) e = hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && lc_index) {
-        e = ctx->lc.reserve((size_t)B * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s);
-        d_lc = ctx->lc.as<int32_t>();
-    }
-    if (e == hipSuccess) {
-        mtg_launch_prepare(make_prep_args(ctx, B, ctx->theta.as<double>(), add_prior, ctx->out.as<double>(),
-                                          ctx->status.as<int32_t>(), 1), s);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    head.coef = ctx->coef.as<double>(); head.cstride = ctx->cstride; head.lay = lay;
-    head.nr0 = m.nr0; head.nc0 = m.nc0; head.sig = ctx->sig.as<int32_t>();
-    head.row0 = 0; head.B = B; head.lc_index = d_lc; head.status = ctx->status.as<int32_t>();
-    head.dxt = ctx->dxt.as<double2>(); head.yv = ctx->yv.as<double2>();
-    head.N = ctx->N; head.t_stride = ctx->t_per_lc ? ctx->N : 0;
-    return MTG_OK;
-}
-
 // fn(row0, rows) for the slabs [row0, row0 + rows) of a batch of B rows, Bs at a time, until one fails
 template <class F>
 hipError_t for_each_slab(int64_t B, int64_t Bs, F fn)
@@ -704,15 +668,12 @@ int pair_launch(mtg_ctx *ctx, const MtgSolveArgs &sa, int64_t B, const MtgPipeSh
     return MTG_OK;
 }
 
-// What every solver launch of B prepared evaluations takes: the resident light curves, the coefficient columns, the
-// context's tables (made at the first call).
-int solve_args_base(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out, int32_t *d_status, hipStream_t s, MtgSolveArgs &sa)
+// What every solver launch of B evaluations takes from the context alone: the coefficient columns, the resident light
+// curves and the window over them, the context's tables (made at the first call).
+int solve_args_context(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out, int32_t *d_status, hipStream_t s, MtgSolveArgs &sa)
 {
-    const MtgModel &m = ctx->model;
-    MtgCoefLayout lay{m.nr_max, m.nc_max};
     sa.coef = ctx->coef.as<double>();
     sa.cstride = ctx->cstride;
-    sa.lay = lay;
     sa.B = B;
     sa.lc_index = d_lc;
     sa.status = d_status;
@@ -725,12 +686,6 @@ int solve_args_base(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out,
     sa.yv_bytes = (uint64_t)ctx->L * (uint64_t)ctx->N * 16u;
     sa.dxt_bytes = (uint64_t)(ctx->t_per_lc ? ctx->L : 1) * (uint64_t)ctx->N * 16u;
     sa.window_bytes = ctx->window_bytes;
-    sa.mean_kind = m.mean_kind;
-    // the mean vanishes identically when it is a frozen constant equal to 0 (the
-    // per-light-curve frozen mean lives in y_offset)
-    sa.has_mean = !(m.mean_kind == MTG_MEAN_CONSTANT && m.src[m.nk] < 0 && m.defaults[m.nk] == 0.0);
-    for (int i = 0; i < m.nterms; ++i)
-        if (m.kinds[i] == MTG_TERM_JITTER) sa.has_mean = 1;  // the plain sweep variant also skips the jitter add
     if (!ctx->tables_ready) {   // once per context, on the stream of its first batch (every later one is ordered behind it)
         HIP_TRY(ctx, ctx->tables.reserve(mtg_tables_bytes()));
         mtg_launch_tables(ctx->tables.p, s);
@@ -741,6 +696,18 @@ int solve_args_base(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out,
     if (const char *env = mtg_measure_env("MTG_GLOBAL_TABLES"))   // MTG_MEASURE builds only: 0 = every workgroup computes its own
         if (atoi(env) == 0) sa.tables = nullptr;
     return MTG_OK;
+}
+
+// ... and from the model whose expansion filled the columns (mtg_loglike_coeffs, which has none, says these itself)
+void solve_args_model(const MtgModel &m, MtgSolveArgs &sa)
+{
+    sa.lay = MtgCoefLayout{m.nr_max, m.nc_max};
+    sa.mean_kind = m.mean_kind;
+    // the mean vanishes identically when it is a frozen constant equal to 0 (the
+    // per-light-curve frozen mean lives in y_offset)
+    sa.has_mean = !(m.mean_kind == MTG_MEAN_CONSTANT && m.src[m.nk] < 0 && m.defaults[m.nk] == 0.0);
+    for (int i = 0; i < m.nterms; ++i)
+        if (m.kinds[i] == MTG_TERM_JITTER) sa.has_mean = 1;  // the plain sweep variant also skips the jitter add
 }
 
 // an MTG_MEASURE knob's value (shipped builds, or the variable not set: `unset`)
@@ -839,8 +806,9 @@ int solve_prepared(mtg_ctx *ctx, int64_t B, const int32_t *d_lc, double *d_out, 
     const int nsig = m.nsho + 1;
     MtgSolveArgs sa;
     {
-        const int rc = solve_args_base(ctx, B, d_lc, d_out, d_status, s, sa);
+        const int rc = solve_args_context(ctx, B, d_lc, d_out, d_status, s, sa);
         if (rc) return rc;
+        solve_args_model(m, sa);
     }
     const MtgPlanIn in = plan_input(ctx, B, may_sort && d_lc, sa);
     MtgSolvePlan plan = mtg_plan_solve(in, g_catalogue);
@@ -917,6 +885,92 @@ int check_ready(mtg_ctx *ctx, bool need_model)
     if (ctx->N <= 0) return fail(ctx, MTG_E_STATE, "mtg_set_lightcurves has not been called");
     if (need_model && !ctx->has_model) return fail(ctx, MTG_E_STATE, "mtg_set_model has not been called");
     return MTG_OK;
+}
+
+// One host-pointer call over rows of theta in flight (`who`: mtg_loglike_batch, mtg_loglike_coeffs, mtg_predict,
+// mtg_predict_at, mtg_gp_draw, mtg_loglike_grad, mtg_apply_inverse).  The entry runs ready, its own argument checks and
+// begin -- in that order; each returns at once, nothing is queued yet -- then the stages below and its own reservations
+// and launches.  From stage_inputs on nothing returns early: a step runs only while the call is ok(), the first failure
+// is kept -- a HIP error in `e`, or in `rc` the code of a helper that has written its own report -- and finish() is the
+// one way out: it waits for the stream whatever happened, so that the caller's arrays are no longer the target of a
+// queued copy when the call returns, and reports "who: <HIP error>".
+struct RowCall {
+    mtg_ctx *ctx;
+    const char *who;
+    int64_t B;
+    const double *theta;             // [B][P] on the host
+    const int32_t *lc_index;         // [B] on the host, or NULL: light curve 0
+    int add_prior;
+    hipStream_t s = nullptr;
+    const int32_t *d_lc = nullptr;   // stage_inputs: lc_index on the device, NULL when lc_index is (never an earlier call's)
+    hipError_t e = hipSuccess;
+    int rc = MTG_OK;
+    struct Room { DevBuf &buf; size_t bytes; };
+
+    bool ok() const { return rc == MTG_OK && e == hipSuccess; }
+    int ready(bool need_model = true) { return check_ready(ctx, need_model); }
+    int bad_arguments() { return fail(ctx, MTG_E_ARG, "%s: bad arguments", who); }
+    int begin(bool refuse_profile);
+    void stage_inputs(bool with_theta = true);
+    void expand(MtgRowArgs &head);
+    template <class F> void then(F step) { if (ok()) e = step(); }   // step() -> hipError_t
+    void reserve(std::initializer_list<Room> rooms) { for (const Room &r : rooms) then([&] { return r.buf.reserve(r.bytes); }); }
+    void upload(void *dev, const void *host, size_t bytes) { then([&] { return hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s); }); }
+    void gather(void *host, const void *dev, size_t bytes) { then([&] { return hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s); }); }
+    void sync() { then([&] { return hipStreamSynchronize(s); }); }
+    int finish(int32_t *status);
+};
+
+// the model's profile mean refused where the entry cannot read one, the light-curve indices, the device and the context's
+// stream, ordered after whatever ran last on a caller's
+int RowCall::begin(bool refuse_profile)
+{
+    int r = refuse_profile ? refuse_profile_mean(ctx, who) : MTG_OK;
+    if (r || (r = check_lc_index(ctx, B, lc_index)) || (r = use_device(ctx))) return r;
+    s = ctx->stream;
+    return enter_stream(ctx, s);
+}
+
+// room for B rows of theta, results and statuses in the context's staging; theta and lc_index uploaded
+void RowCall::stage_inputs(bool with_theta)
+{
+    const size_t rows = (size_t)B;
+    const int P = ctx->model.P;
+    reserve({{ctx->theta, with_theta ? rows * (P > 0 ? P : 1) * 8 : 0}, {ctx->out, rows * 8}, {ctx->status, rows * 4},
+             {ctx->lc, lc_index ? rows * 4 : 0}});
+    if (with_theta && P > 0) upload(ctx->theta.p, theta, rows * P * 8);
+    if (lc_index) upload(ctx->lc.p, lc_index, rows * 4);
+    d_lc = lc_index ? ctx->lc.as<int32_t>() : nullptr;
+}
+
+// The staged theta expanded into the coefficient workspace -- the prior's verdict in ctx->status, the structure of every
+// row in ctx->sig -- and the head of the per-row kernels' arguments filled for the whole batch.  (ctx->sig, like
+// ctx->coef, is rewritten by every expansion and read by nothing before the next one.)
+void RowCall::expand(MtgRowArgs &head)
+{
+    const MtgModel &m = ctx->model;
+    if (ok()) rc = reserve_workspace(ctx, B, model_nslots(m), 1);
+    then([&] {
+        mtg_launch_prepare(make_prep_args(ctx, B, ctx->theta.as<double>(), add_prior, ctx->out.as<double>(),
+                                          ctx->status.as<int32_t>(), 1), s);
+        return hipGetLastError();
+    });
+    head.coef = ctx->coef.as<double>(); head.cstride = ctx->cstride; head.lay = MtgCoefLayout{m.nr_max, m.nc_max};
+    head.nr0 = m.nr0; head.nc0 = m.nc0; head.sig = ctx->sig.as<int32_t>();
+    head.row0 = 0; head.B = B; head.lc_index = d_lc; head.status = ctx->status.as<int32_t>();
+    head.dxt = ctx->dxt.as<double2>(); head.yv = ctx->yv.as<double2>();
+    head.N = ctx->N; head.t_stride = ctx->t_per_lc ? ctx->N : 0;
+}
+
+// the statuses on their way to the host behind the entry's own results (NULL: the entry has fetched them), then the
+// stream waited for: the end of every row entry, and the only place where one reports a HIP error
+int RowCall::finish(int32_t *status)
+{
+    if (status) gather(status, ctx->status.p, (size_t)B * 4);
+    const hipError_t drained = hipStreamSynchronize(s);
+    if (ok()) e = drained;
+    if (rc) return rc;
+    return e == hipSuccess ? MTG_OK : fail(ctx, MTG_E_HIP, "%s: %s", who, hipGetErrorString(e));
 }
 
 }  // namespace
@@ -1220,14 +1274,13 @@ MTG_API int mtg_loglike_batch_device(mtg_ctx *ctx, int64_t B, const double *d_th
 MTG_API int mtg_loglike_batch(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index,
                               int add_prior, double *out, int32_t *status)
 {
-    int rc = check_ready(ctx, true);
+    RowCall c{ctx, "mtg_loglike_batch", B, theta, lc_index, add_prior};
+    int rc = c.ready();
     if (rc) return rc;
-    if (B < 0 || (B > 0 && (!out || !status || (!theta && ctx->model.P > 0))))
-        return fail(ctx, MTG_E_ARG, "mtg_loglike_batch: bad arguments");
+    if (B < 0 || (B > 0 && (!out || !status || (!theta && ctx->model.P > 0)))) return c.bad_arguments();
     if (B == 0) return MTG_OK;
     if (B > INT32_MAX) return fail(ctx, MTG_E_ARG, "batch too large");
-    rc = check_lc_index(ctx, B, lc_index);
-    if (rc) return rc;
+    if ((rc = c.begin(false))) return rc;
     // is the caller's order already grouped by light curve?  Then the sweep keeps it
     int64_t runs = 1;
     bool ascending = true;
@@ -1235,31 +1288,15 @@ MTG_API int mtg_loglike_batch(mtg_ctx *ctx, int64_t B, const double *theta, cons
         if (lc_index[b] != lc_index[b - 1]) ++runs;
         if (lc_index[b] < lc_index[b - 1]) ascending = false;
     }
-    rc = use_device(ctx);
-    if (rc) return rc;
     // grouped: already in ascending order (sorting changes nothing), or in runs of equal indices long enough that a
     // wave of 64 lanes straddles two or three light curves at most
     ctx->lc_grouped_hint = !lc_index || ascending || B / runs >= 32;
-    const int P = ctx->model.P;
-    CTX_STREAM(ctx, s);
-    HIP_TRY(ctx, ctx->theta.reserve((size_t)B * (P > 0 ? P : 1) * 8));
-    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
-    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
-    if (P > 0) HIP_TRY(ctx, hipMemcpyAsync(ctx->theta.p, theta, (size_t)B * P * 8, hipMemcpyHostToDevice, s));
-    const int32_t *d_lc = nullptr;
-    if (lc_index) {
-        HIP_TRY(ctx, ctx->lc.reserve((size_t)B * 4));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s));
-        d_lc = ctx->lc.as<int32_t>();
-    }
-    rc = run_model_batch(ctx, B, ctx->theta.as<double>(), d_lc, add_prior, ctx->out.as<double>(),
-                         ctx->status.as<int32_t>(), s);
-    if (rc) return rc;
+    c.stage_inputs();
+    if (c.ok()) c.rc = run_model_batch(ctx, B, ctx->theta.as<double>(), c.d_lc, add_prior, ctx->out.as<double>(),
+                                       ctx->status.as<int32_t>(), c.s);
     mtg_trace::Range range("mtg:gather (lnP, status -> host)");
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->out.p, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    return MTG_OK;
+    c.gather(out, ctx->out.p, (size_t)B * 8);
+    return c.finish(status);
 }
 
 MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const double *a_real,
@@ -1268,10 +1305,10 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
                                int mean_kind, const double *mean_params, const int32_t *lc_index,
                                double *out, int32_t *status)
 {
-    int rc = check_ready(ctx, false);
+    RowCall c{ctx, "mtg_loglike_coeffs", B, nullptr, lc_index, 0};
+    int rc = c.ready(false);
     if (rc) return rc;
-    if (B < 0 || jr < 0 || jc < 0 || (B > 0 && (!out || !status)))
-        return fail(ctx, MTG_E_ARG, "mtg_loglike_coeffs: bad arguments");
+    if (B < 0 || jr < 0 || jc < 0 || (B > 0 && (!out || !status))) return c.bad_arguments();
     if ((jr > 0 && (!a_real || !c_real)) || (jc > 0 && (!a_comp || !b_comp || !c_comp || !d_comp)))
         return fail(ctx, MTG_E_ARG, "mtg_loglike_coeffs: NULL coefficient array");
     if (mtg_mean_nparams_of(mean_kind) < 0)
@@ -1284,21 +1321,19 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
     mtg_solve_launcher fn = find_sweep(mean_kind, jr, jc);
     if (!fn)
         return fail(ctx, MTG_E_UNSUPPORTED, "no compiled kernel for %d real + %d complex terms", jr, jc);
-    rc = check_lc_index(ctx, B, lc_index);
-    if (rc) return rc;
-    rc = use_device(ctx);
-    if (rc) return rc;
+    if ((rc = c.begin(false))) return rc;
     MtgCoefLayout lay{jr, jc};
     const int nslots = lay.nslots() + mtg_mean_extra_slots(mean_kind);
-    rc = reserve_workspace(ctx, B, nslots, 1);
-    if (rc) return rc;
+    if ((rc = reserve_workspace(ctx, B, nslots, 1))) return rc;
     const int64_t cs = ctx->cstride;
-    CTX_STREAM(ctx, s);
     // host-side transpose [B][j] -> SoA columns, then one upload
     const int nmean = mtg_mean_nparams_of(mean_kind);
-    double *h = (double *)malloc((size_t)cs * nslots * 8);
-    if (!h) return fail(ctx, MTG_E_ARG, "out of host memory");
-    memset(h, 0, (size_t)cs * nslots * 8);
+    std::vector<double> h;
+    try {
+        h.resize((size_t)cs * nslots);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, MTG_E_ARG, "out of host memory");
+    }
     for (int64_t b = 0; b < B; ++b) {
         double asum = jitter ? jitter[b] : 0.0;
         for (int j = 0; j < jr; ++j) {
@@ -1327,57 +1362,28 @@ MTG_API int mtg_loglike_coeffs(mtg_ctx *ctx, int64_t B, int jr, int jc, const do
             for (int i = 0; i < mtg_mean_extra_slots(mean_kind); ++i) h[lay.mean_extra(i) * cs + b] = mc.ex(i);
         }
     }
-    hipError_t e = hipMemcpyAsync(ctx->coef.p, h, (size_t)cs * nslots * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    free(h);
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "coefficient upload failed: %s", hipGetErrorString(e));
-    HIP_TRY(ctx, ctx->out.reserve((size_t)B * 8));
-    HIP_TRY(ctx, ctx->status.reserve((size_t)B * 4));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->status.p, 0, (size_t)B * 4, s));
-    const int32_t *d_lc = nullptr;
-    if (lc_index) {
-        HIP_TRY(ctx, ctx->lc.reserve((size_t)B * 4));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->lc.p, lc_index, (size_t)B * 4, hipMemcpyHostToDevice, s));
-        d_lc = ctx->lc.as<int32_t>();
-    }
-    MtgSolveArgs sa;
-    sa.coef = ctx->coef.as<double>();
-    sa.cstride = cs;
+    c.upload(ctx->coef.p, h.data(), h.size() * 8);   // (h lives until finish() has waited for the stream)
+    c.stage_inputs(false);
+    c.then([&] { return hipMemsetAsync(ctx->status.p, 0, (size_t)B * 4, c.s); });
+    MtgSolveArgs sa{};   // no lists, no time-parallel workspace, no structure words: one sweep in the caller's order
+    if (c.ok()) c.rc = solve_args_context(ctx, B, c.d_lc, ctx->out.as<double>(), ctx->status.as<int32_t>(), c.s, sa);
     sa.lay = lay;
-    sa.list = nullptr;
-    sa.count_ptr = nullptr;
-    sa.B = B;
-    sa.lc_index = d_lc;
-    sa.status = ctx->status.as<int32_t>();
-    sa.out = ctx->out.as<double>();
-    sa.dxt = ctx->dxt.as<double2>();
-    sa.yv = ctx->yv.as<double2>();
-    sa.N = ctx->N;
-    sa.t_stride = ctx->t_per_lc ? ctx->N : 0;
-    sa.dxmax = ctx->dxmax.as<double>();
-    sa.yv_bytes = (uint64_t)ctx->L * (uint64_t)ctx->N * 16u;
-    sa.dxt_bytes = (uint64_t)(ctx->t_per_lc ? ctx->L : 1) * (uint64_t)ctx->N * 16u;
-    sa.window_bytes = ctx->window_bytes;
     sa.mean_kind = mean_kind;
     sa.has_mean = mean_params != nullptr || jitter != nullptr;
-    sa.tp_ws = nullptr;
-    sa.tp_chunks = 0;
-    sa.tp_gsize = 0;
-    sa.tp_direct = 0;
     sa.tp_nr0 = jr; sa.tp_nc0 = jc;
-    sa.sig = nullptr;
-    ctx->timed = true;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, s));
-    if (profile) mtg_mean_kernel_name(ctx->last_solver, sizeof ctx->last_solver, jr, jc, 0, " (coefficients)");
-    else mtg_struct_kernel_name(ctx->last_solver, sizeof ctx->last_solver, MTG_STRUCT_SWEEP, jr, jc, 0, " (coefficients)");
-    rc = sweep_launch(ctx, fn, sa, B, 0, s);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->out.p, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    return MTG_OK;
+    if (c.ok()) {
+        ctx->timed = true;
+        c.e = hipEventRecord(ctx->ev0, c.s);
+    }
+    if (c.ok()) {
+        if (profile) mtg_mean_kernel_name(ctx->last_solver, sizeof ctx->last_solver, jr, jc, 0, " (coefficients)");
+        else mtg_struct_kernel_name(ctx->last_solver, sizeof ctx->last_solver, MTG_STRUCT_SWEEP, jr, jc, 0, " (coefficients)");
+        c.rc = sweep_launch(ctx, fn, sa, B, 0, c.s);
+    }
+    c.then([&] { return hipGetLastError(); });
+    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+    c.gather(out, ctx->out.p, (size_t)B * 8);
+    return c.finish(status);
 }
 
 MTG_API int mtg_ensemble_init(mtg_ctx *ctx, int64_t E, int W, uint64_t seed, const double *coords,
@@ -2320,82 +2326,59 @@ MTG_API int mtg_tk95_observe_series(mtg_ctx *ctx, int64_t S, int64_t nfft, int64
     for (int64_t n = 0; n < N; ++n)
         if (win_lo[n] < 0 || win_hi[n] < win_lo[n] || win_hi[n] > seg_len)
             return fail(ctx, MTG_E_ARG, "mtg_tk95_observe_series: window %lld outside the segment", (long long)n);
-    rc = use_device(ctx);
-    if (rc) return rc;
-    CTX_STREAM(ctx, s);
-#define OBS_TRY(call)                                                                                             \
-    do {                                                                                                          \
-        hipError_t e__ = (call);                                                                                  \
-        if (e__ != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_tk95_observe_series: %s", hipGetErrorString(e__)); \
-    } while (0)
+    RowCall c{ctx, "mtg_tk95_observe_series", S, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    if ((rc = c.begin(false))) return rc;
     DevBuf d_series, d_lo, d_hi, d_rates, d_dy;
-    OBS_TRY(d_series.reserve_n<double>(S * nfft));
-    OBS_TRY(d_lo.reserve_n<int32_t>(N));
-    OBS_TRY(d_hi.reserve_n<int32_t>(N));
-    OBS_TRY(d_rates.reserve_n<double>(S * N));
-    OBS_TRY(d_dy.reserve_n<double>(S * N));
-    OBS_TRY(hipMemcpyAsync(d_series.p, series, (size_t)S * nfft * 8, hipMemcpyHostToDevice, s));
-    OBS_TRY(hipMemcpyAsync(d_lo.p, win_lo, (size_t)N * 4, hipMemcpyHostToDevice, s));
-    OBS_TRY(hipMemcpyAsync(d_hi.p, win_hi, (size_t)N * 4, hipMemcpyHostToDevice, s));
-    MtgTk95Observe oa;   // scale = dt = 1, mean 0, no noise: the plain window average of the series
-    oa.N = N; oa.nfft = nfft; oa.seg_len = seg_len; oa.fixed_start = start;
-    oa.win_lo = d_lo.as<int32_t>(); oa.win_hi = d_hi.as<int32_t>(); oa.rates = d_rates.as<double>(); oa.dy = d_dy.as<double>();
-    oa.S = S; oa.series = d_series.as<double>();
-    mtg_launch_tk95_observe(oa, s);
-    OBS_TRY(hipGetLastError());
-    OBS_TRY(hipMemcpyAsync(rates, d_rates.p, (size_t)S * N * 8, hipMemcpyDeviceToHost, s));
-    OBS_TRY(hipStreamSynchronize(s));
-#undef OBS_TRY
-    return MTG_OK;
+    c.reserve({{d_series, (size_t)S * nfft * 8}, {d_lo, (size_t)N * 4}, {d_hi, (size_t)N * 4}, {d_rates, (size_t)S * N * 8},
+               {d_dy, (size_t)S * N * 8}});
+    c.upload(d_series.p, series, (size_t)S * nfft * 8);
+    c.upload(d_lo.p, win_lo, (size_t)N * 4);
+    c.upload(d_hi.p, win_hi, (size_t)N * 4);
+    c.then([&] {
+        MtgTk95Observe oa;   // scale = dt = 1, mean 0, no noise: the plain window average of the series
+        oa.N = N; oa.nfft = nfft; oa.seg_len = seg_len; oa.fixed_start = start;
+        oa.win_lo = d_lo.as<int32_t>(); oa.win_hi = d_hi.as<int32_t>(); oa.rates = d_rates.as<double>(); oa.dy = d_dy.as<double>();
+        oa.S = S; oa.series = d_series.as<double>();
+        mtg_launch_tk95_observe(oa, c.s);
+        return hipGetLastError();
+    });
+    c.gather(rates, d_rates.p, (size_t)S * N * 8);
+    return c.finish(nullptr);
 }
 
 MTG_API int mtg_predict(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, double *mu,
                         double *var, int32_t *status)
 {
-    int rc = check_ready(ctx, true);
+    RowCall c{ctx, "mtg_predict", B, theta, lc_index, 1};
+    int rc = c.ready();
     if (rc) return rc;
-    if (B <= 0 || !mu || !var || !status || (!theta && ctx->model.P > 0))
-        return fail(ctx, MTG_E_ARG, "mtg_predict: bad arguments");
-    if ((rc = refuse_profile_mean(ctx, "mtg_predict"))) return rc;
-    rc = check_lc_index(ctx, B, lc_index);
-    if (rc) return rc;
-    rc = use_device(ctx);
-    if (rc) return rc;
+    if (B <= 0 || !mu || !var || !status || (!theta && ctx->model.P > 0)) return c.bad_arguments();
+    if ((rc = c.begin(true))) return rc;
     const int J = ctx->model.nr_max + 2 * ctx->model.nc_max, N = (int)ctx->N;
-    CTX_STREAM(ctx, s);
+    const size_t out_bytes = (size_t)B * N * 8;
     MtgPredictArgs qa;
-    rc = stage_rows(ctx, "mtg_predict", B, theta, lc_index, 1, s, qa);
-    if (rc) return rc;
+    c.stage_inputs();
+    c.expand(qa);
     DevBuf work, d_mu, d_var;
-    hipError_t e = work.reserve((size_t)B * N * (3 * J + 2) * 8);
-    if (e == hipSuccess) e = d_mu.reserve((size_t)B * N * 8);
-    if (e == hipSuccess) e = d_var.reserve((size_t)B * N * 8);
-    if (e == hipSuccess) {
+    c.reserve({{work, (size_t)B * N * (3 * J + 2) * 8}, {d_mu, out_bytes}, {d_var, out_bytes}});
+    c.then([&] {
         qa.work = work.as<double>(); qa.mu = d_mu.as<double>(); qa.var = d_var.as<double>();
-        mtg_launch_predict(qa, s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(mu, d_mu.p, (size_t)B * N * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(var, d_var.p, (size_t)B * N * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_predict: %s", hipGetErrorString(e));
-    return MTG_OK;
+        mtg_launch_predict(qa, c.s);
+        return hipGetLastError();
+    });
+    c.gather(mu, d_mu.p, out_bytes);
+    c.gather(var, d_var.p, out_bytes);
+    return c.finish(status);
 }
-
-// device workspace of one slab of mtg_predict_at: rows whose stored generators (3 J + 3 doubles per sample) stay below this
-#define MTG_PAT_SLAB_BYTES ((size_t)1 << 30)
 
 MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int64_t M,
                            const double *ts, double *mu, double *var, int32_t *status)
 {
-    int rc = check_ready(ctx, true);
+    RowCall c{ctx, "mtg_predict_at", B, theta, lc_index, 1};
+    int rc = c.ready();
     if (rc) return rc;
-    if (B <= 0 || M <= 0 || !ts || !mu || !status || (!theta && ctx->model.P > 0))
-        return fail(ctx, MTG_E_ARG, "mtg_predict_at: bad arguments");
-    if ((rc = refuse_profile_mean(ctx, "mtg_predict_at"))) return rc;
-    rc = check_lc_index(ctx, B, lc_index);
-    if (rc) return rc;
+    if (B <= 0 || M <= 0 || !ts || !mu || !status || (!theta && ctx->model.P > 0)) return c.bad_arguments();
+    if ((rc = c.begin(true))) return rc;
     bool ascending = true;
     for (int64_t m = 0; m < M; ++m) {
         if (!std::isfinite(ts[m])) return fail(ctx, MTG_E_ARG, "mtg_predict_at: ts[%lld] is not finite", (long long)m);
@@ -2409,148 +2392,102 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
         for (int64_t m = 0; m < M; ++m) order[(size_t)m] = m;
         std::sort(order.begin(), order.end(), [ts](int64_t i, int64_t j) { return ts[i] < ts[j] || (ts[i] == ts[j] && i < j); });
     }
-    rc = use_device(ctx);
-    if (rc) return rc;
     const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
     const int64_t N = ctx->N;
     if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_predict_at: rank %d > %d", J, MTG_MAX_J);
-    CTX_STREAM(ctx, s);
-    // rows per slab: the stored generators within MTG_PAT_SLAB_BYTES, and the grid of the second stage within 2^30 blocks
-    const size_t row_bytes = (size_t)N * (3 * J + 3) * 8;
-    int64_t Bs = (int64_t)(MTG_PAT_SLAB_BYTES / row_bytes);
-    const int64_t mblocks = (M + 63) / 64;
-    if (Bs > ((int64_t)1 << 30) / mblocks) Bs = ((int64_t)1 << 30) / mblocks;
-    if (Bs < 1) Bs = 1;
-    if (Bs > B) Bs = B;
-    if (mblocks > ((int64_t)1 << 30)) return fail(ctx, MTG_E_ARG, "mtg_predict_at: M = %lld is too large", (long long)M);
+    const int64_t Bs = mtg_plan_predict_at_slab(N, J, M, B);
+    if (Bs == 0) return fail(ctx, MTG_E_ARG, "mtg_predict_at: M = %lld is too large", (long long)M);
+    const size_t row_bytes = (size_t)N * (3 * J + 3) * 8, tri_bytes = (size_t)(J * (J + 1) / 2) * 8;
     const int64_t nck = (N + MTG_PAT_C - 1) / MTG_PAT_C;
-    const size_t ck_bytes = (size_t)nck * (J * (J + 1) / 2 + J) * 8;
+    const size_t ck_bytes = (size_t)nck * (tri_bytes + J * 8), ts_bytes = (size_t)M * 8;
     MtgPredictAtArgs qa;
-    rc = stage_rows(ctx, "mtg_predict_at", B, theta, lc_index, 1, s, qa);
-    if (rc) return rc;
+    c.stage_inputs();
+    c.expand(qa);
     DevBuf work, ckf, ckb, ckr, d_mu, d_var, d_ts, d_order;
-    hipError_t e = work.reserve((size_t)Bs * row_bytes + 8);
-    if (e == hipSuccess) e = ckf.reserve((size_t)Bs * ck_bytes + 8);
-    if (e == hipSuccess) e = ckb.reserve((size_t)Bs * ck_bytes + 8);
-    if (e == hipSuccess) e = ckr.reserve((size_t)Bs * (J * (J + 1) / 2) * 8 + 8);
-    if (e == hipSuccess) e = d_mu.reserve((size_t)Bs * M * 8);
-    if (e == hipSuccess && var) e = d_var.reserve((size_t)Bs * M * 8);
-    if (e == hipSuccess) e = d_ts.reserve((size_t)M * 8);
-    if (e == hipSuccess && !ascending) e = d_order.reserve((size_t)M * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ts.p, ts, (size_t)M * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && !ascending) e = hipMemcpyAsync(d_order.p, order.data(), (size_t)M * 8, hipMemcpyHostToDevice, s);
+    c.reserve({{work, (size_t)Bs * row_bytes + 8}, {ckf, (size_t)Bs * ck_bytes + 8}, {ckb, (size_t)Bs * ck_bytes + 8},
+               {ckr, (size_t)Bs * tri_bytes + 8}, {d_mu, (size_t)Bs * ts_bytes}, {d_var, var ? (size_t)Bs * ts_bytes : 0},
+               {d_ts, ts_bytes}, {d_order, ascending ? 0 : ts_bytes}});
+    c.upload(d_ts.p, ts, ts_bytes);
+    if (!ascending) c.upload(d_order.p, order.data(), ts_bytes);
     qa.work = work.as<double>();
     qa.nck = nck; qa.ckf = ckf.as<double>(); qa.ckb = ckb.as<double>(); qa.ckr = ckr.as<double>(); qa.want_var = var ? 1 : 0;
     qa.M = M; qa.ts = d_ts.as<double>(); qa.order = ascending ? nullptr : d_order.as<int64_t>();
     qa.mu = d_mu.as<double>(); qa.var = var ? d_var.as<double>() : nullptr;
-    if (e == hipSuccess) e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
+    if (c.ok()) c.e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
         qa.row0 = row0; qa.B = rows;
-        if (!mtg_launch_predict_at(qa, s)) return hipErrorInvalidValue;
-        hipError_t e = hipGetLastError();
+        c.then([&] { return mtg_launch_predict_at(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
         // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
-        if (e == hipSuccess) e = hipMemcpyAsync(mu + row0 * M, d_mu.p, (size_t)rows * M * 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && var) e = hipMemcpyAsync(var + row0 * M, d_var.p, (size_t)rows * M * 8, hipMemcpyDeviceToHost, s);
-        return e;
+        c.gather(mu + row0 * M, d_mu.p, (size_t)rows * ts_bytes);
+        if (var) c.gather(var + row0 * M, d_var.p, (size_t)rows * ts_bytes);
+        return c.e;
     });
-    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    else (void)hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_predict_at: %s", hipGetErrorString(e));
-    return MTG_OK;
+    return c.finish(status);
 }
-
-// device memory of one slab of mtg_gp_draw: rows (a multiple of 64) whose draws stay below this, and as much again for
-// the caller's normals
-#define MTG_DRAW_SLAB_BYTES ((size_t)1 << 28)
 
 MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, uint64_t seed,
                         const double *normals, double *y, int32_t *status)
 {
-    int rc = check_ready(ctx, true);
+    RowCall c{ctx, "mtg_gp_draw", B, theta, lc_index, 1};
+    int rc = c.ready();
     if (rc) return rc;
-    if (B <= 0 || !y || !status || (!theta && ctx->model.P > 0))
-        return fail(ctx, MTG_E_ARG, "mtg_gp_draw: bad arguments");
-    if ((rc = refuse_profile_mean(ctx, "mtg_gp_draw"))) return rc;
-    rc = check_lc_index(ctx, B, lc_index);
-    if (rc) return rc;
-    rc = use_device(ctx);
-    if (rc) return rc;
+    if (B <= 0 || !y || !status || (!theta && ctx->model.P > 0)) return c.bad_arguments();
+    if ((rc = c.begin(true))) return rc;
     const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
     const int64_t N = ctx->N;
     if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_gp_draw: rank %d > %d", J, MTG_MAX_J);
-    CTX_STREAM(ctx, s);
     const size_t row_bytes = (size_t)N * 8;
-    int64_t Bs = (int64_t)(MTG_DRAW_SLAB_BYTES / row_bytes) / 64 * 64;
-    if (Bs < 64) Bs = 64;
-    if (Bs > B) Bs = B;
+    const int64_t Bs = mtg_plan_draw_slab(N, B);
     MtgGpDrawArgs qa;
-    rc = stage_rows(ctx, "mtg_gp_draw", B, theta, lc_index, 1, s, qa);
-    if (rc) return rc;
+    c.stage_inputs();
+    c.expand(qa);
     DevBuf d_y, d_q;
-    hipError_t e = d_y.reserve((size_t)Bs * row_bytes);
-    if (e == hipSuccess && normals) e = d_q.reserve((size_t)Bs * row_bytes);
+    c.reserve({{d_y, (size_t)Bs * row_bytes}, {d_q, normals ? (size_t)Bs * row_bytes : 0}});
     qa.normals = normals ? d_q.as<double>() : nullptr;
     qa.seed_lo = (uint32_t)seed; qa.seed_hi = (uint32_t)(seed >> 32); qa.draw0 = ctx->stream_base;
     qa.y = d_y.as<double>();
-    if (e == hipSuccess) e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
+    if (c.ok()) c.e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
         qa.row0 = row0; qa.B = rows;
         // (the copies are ordered on the stream: the next slab's upload and kernel touch the buffers only after them)
-        hipError_t e = normals ? hipMemcpyAsync(d_q.p, normals + row0 * N, (size_t)rows * row_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-        if (e != hipSuccess) return e;
-        if (!mtg_launch_gp_draw(qa, s)) return hipErrorInvalidValue;
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(y + row0 * N, d_y.p, (size_t)rows * row_bytes, hipMemcpyDeviceToHost, s);
-        return e;
+        if (normals) c.upload(d_q.p, normals + row0 * N, (size_t)rows * row_bytes);
+        c.then([&] { return mtg_launch_gp_draw(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        c.gather(y + row0 * N, d_y.p, (size_t)rows * row_bytes);
+        return c.e;
     });
-    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    else (void)hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_gp_draw: %s", hipGetErrorString(e));
-    return MTG_OK;
+    return c.finish(status);
 }
 
 MTG_API int mtg_loglike_grad(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int add_prior,
                              double *out, double *grad, int32_t *status)
 {
-    int rc = check_ready(ctx, true);
+    RowCall c{ctx, "mtg_loglike_grad", B, theta, lc_index, add_prior ? 1 : 0};
+    int rc = c.ready();
     if (rc) return rc;
     const int P = ctx->model.P;
-    if (B <= 0 || !theta || !out || !grad || !status) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: bad arguments");
-    if ((rc = refuse_profile_mean(ctx, "mtg_loglike_grad"))) return rc;
+    if (B <= 0 || !theta || !out || !grad || !status) return c.bad_arguments();
+    // (the refusal here and not in begin: the check of P has always stood between it and the light-curve indices)
+    if ((rc = refuse_profile_mean(ctx, c.who))) return rc;
     if (P <= 0) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: the model has no free parameter");
-    rc = check_lc_index(ctx, B, lc_index);
-    if (rc) return rc;
+    if ((rc = c.begin(false))) return rc;
     const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
     if (J > MTG_GRAD_MAX_J)
         return fail(ctx, MTG_E_UNSUPPORTED, "mtg_loglike_grad: rank %d > %d (the tangent sweep keeps its state in registers)", J,
                     MTG_GRAD_MAX_J);
     if (B * P > ((int64_t)1 << 36)) return fail(ctx, MTG_E_ARG, "mtg_loglike_grad: B * P = %lld is too large", (long long)(B * P));
-    rc = use_device(ctx);
-    if (rc) return rc;
-    CTX_STREAM(ctx, s);
     MtgGradArgs qa;
-    rc = stage_rows(ctx, "mtg_loglike_grad", B, theta, lc_index, add_prior ? 1 : 0, s, qa);
-    if (rc) return rc;
+    c.stage_inputs();
+    c.expand(qa);
     const int64_t lanes = B * P, dstride = (lanes + 63) / 64 * 64;
-    hipError_t e = ctx->grad_dcoef.reserve_n<double>(dstride * qa.lay.nslots());
-    if (e == hipSuccess) e = ctx->grad.reserve_n<double>(lanes);
-    if (e == hipSuccess) e = ctx->grad_verdict.reserve_n<int32_t>(B);
-    if (e == hipSuccess) {
-        qa.model = ctx->model; qa.theta = ctx->theta.as<double>(); qa.P = P;
-        qa.dcoef = ctx->grad_dcoef.as<double>(); qa.dstride = dstride;
-        qa.out = ctx->out.as<double>(); qa.grad = ctx->grad.as<double>(); qa.verdict = ctx->grad_verdict.as<int32_t>();
-        e = hipEventRecord(ctx->ev0, s);     // mtg_last_kernel_ms: the coefficient tangents and the sweep (not stage_rows' expansion)
-        if (e == hipSuccess && !mtg_launch_loglike_grad(qa, s)) e = hipErrorInvalidValue;
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, s);
-        if (e == hipSuccess) ctx->timed = true;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, ctx->out.p, (size_t)B * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(grad, ctx->grad.p, (size_t)lanes * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, (size_t)B * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    else (void)hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_loglike_grad: %s", hipGetErrorString(e));
+    c.reserve({{ctx->grad_dcoef, (size_t)dstride * qa.lay.nslots() * 8}, {ctx->grad, (size_t)lanes * 8}, {ctx->grad_verdict, (size_t)B * 4}});
+    qa.model = ctx->model; qa.theta = ctx->theta.as<double>(); qa.P = P;
+    qa.dcoef = ctx->grad_dcoef.as<double>(); qa.dstride = dstride;
+    qa.out = ctx->out.as<double>(); qa.grad = ctx->grad.as<double>(); qa.verdict = ctx->grad_verdict.as<int32_t>();
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });   // mtg_last_kernel_ms: the coefficient tangents and the sweep (not the expansion)
+    c.then([&] { return mtg_launch_loglike_grad(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+    if (c.ok()) ctx->timed = true;
+    c.gather(out, ctx->out.p, (size_t)B * 8);
+    c.gather(grad, ctx->grad.p, (size_t)lanes * 8);
+    if ((rc = c.finish(status))) return rc;
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_loglike_grad_kernel<%d>", J);
     return MTG_OK;
 }
@@ -2558,69 +2495,58 @@ MTG_API int mtg_loglike_grad(mtg_ctx *ctx, int64_t B, const double *theta, const
 MTG_API int mtg_apply_inverse(mtg_ctx *ctx, const double *theta, int32_t lc_index, int64_t M, double *x,
                               int32_t *status)
 {
-    int rc = check_ready(ctx, true);
+    RowCall c{ctx, "mtg_apply_inverse", 1, theta, &lc_index, 1};
+    int rc = c.ready();
     if (rc) return rc;
-    if (M <= 0 || !x || !status || (!theta && ctx->model.P > 0))
-        return fail(ctx, MTG_E_ARG, "mtg_apply_inverse: bad arguments");
+    if (M <= 0 || !x || !status || (!theta && ctx->model.P > 0)) return c.bad_arguments();
     if (lc_index < 0 || lc_index >= ctx->L)
         return fail(ctx, MTG_E_ARG, "lc_index = %d outside [0, %lld)", lc_index, (long long)ctx->L);
-    rc = use_device(ctx);
-    if (rc) return rc;
+    if ((rc = c.begin(false))) return rc;
     const MtgModel &m = ctx->model;
     const int Jws = m.nr_max + 2 * m.nc_max, J = m.nr0 + 2 * m.nc0;
     const int64_t N = ctx->N;
-    CTX_STREAM(ctx, s);
+    const size_t x_bytes = (size_t)N * M * 8;
     // the factorisation of this parameter vector: the forward sweep of mtg_predict_kernel leaves
     // U_n, W_n, phi_n, D_n of every sample in `work`
     MtgPredictArgs qa;
-    rc = stage_rows(ctx, "mtg_apply_inverse", 1, theta, &lc_index, 1, s, qa);
-    if (rc) return rc;
+    c.stage_inputs();
+    c.expand(qa);
     DevBuf work, d_mu, d_var, d_x;
-    hipError_t e = work.reserve((size_t)N * (3 * Jws + 2) * 8);
-    if (e == hipSuccess) e = d_mu.reserve((size_t)N * 8);
-    if (e == hipSuccess) e = d_var.reserve((size_t)N * 8);
-    if (e == hipSuccess) e = d_x.reserve((size_t)N * M * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_x.p, x, (size_t)N * M * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
+    c.reserve({{work, (size_t)N * (3 * Jws + 2) * 8}, {d_mu, (size_t)N * 8}, {d_var, (size_t)N * 8}, {d_x, x_bytes}});
+    c.upload(d_x.p, x, x_bytes);
+    c.then([&] {
         qa.work = work.as<double>(); qa.mu = d_mu.as<double>(); qa.var = d_var.as<double>();
-        mtg_launch_predict(qa, s);
-        e = hipGetLastError();
+        mtg_launch_predict(qa, c.s);
+        return hipGetLastError();
+    });
+    // the verdict first: the solve is launched, and x overwritten, only for a row the factorisation accepted
+    c.gather(status, ctx->status.p, 4);
+    c.sync();
+    if (c.ok() && *status == MTG_ST_OK) {
+        mtg_launch_apply_inverse(work.as<double>(), N, J, M, d_x.as<double>(), c.s);
+        c.e = hipGetLastError();
+        c.gather(x, d_x.p, x_bytes);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(status, ctx->status.p, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && *status == MTG_ST_OK) {
-        mtg_launch_apply_inverse(work.as<double>(), N, J, M, d_x.as<double>(), s);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(x, d_x.p, (size_t)N * M * 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_apply_inverse: %s", hipGetErrorString(e));
-    return MTG_OK;
+    return c.finish(nullptr);
 }
 
 MTG_API int mtg_math_probe(mtg_ctx *ctx, int64_t n, const double *x, double *exp_neg, double *sin_x,
                            double *cos_x, double *rcp_x)
 {
     if (!ctx || n <= 0 || !x || !exp_neg || !sin_x || !cos_x || !rcp_x) return MTG_E_ARG;
-    int rc = use_device(ctx);
-    if (rc) return rc;
+    RowCall c{ctx, "mtg_math_probe", n, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    if (const int rc = c.begin(false)) return rc;
     DevBuf buf;
-    HIP_TRY(ctx, buf.reserve((size_t)n * 8 * 5));
+    c.reserve({{buf, (size_t)n * 8 * 5}});
     double *d = buf.as<double>();
-    CTX_STREAM(ctx, s);
-    hipError_t e = hipMemcpyAsync(d, x, (size_t)n * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        mtg_launch_math_probe(n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(exp_neg, d + n, (size_t)n * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(sin_x, d + 2 * n, (size_t)n * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cos_x, d + 3 * n, (size_t)n * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(rcp_x, d + 4 * n, (size_t)n * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    buf.release();
-    if (e != hipSuccess) return fail(ctx, MTG_E_HIP, "mtg_math_probe: %s", hipGetErrorString(e));
-    return MTG_OK;
+    c.upload(d, x, (size_t)n * 8);
+    c.then([&] {
+        mtg_launch_math_probe(n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, c.s);
+        return hipGetLastError();
+    });
+    double *const outs[4] = {exp_neg, sin_x, cos_x, rcp_x};
+    for (int i = 0; i < 4; ++i) c.gather(outs[i], d + (i + 1) * n, (size_t)n * 8);
+    return c.finish(nullptr);
 }
 
 MTG_API int mtg_set_time_parallel(mtg_ctx *ctx, int mode)

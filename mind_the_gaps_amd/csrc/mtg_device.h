@@ -133,8 +133,9 @@ size_t mtg_tables_bytes();
 // serialised 64-fold -- measured as 5.6 us per scan round instead of ~1)
 #define MTG_TP_ELEM(J) (((J) * (J) + 2 * (J) + (J) * ((J) + 1) + 5) | 1)
 
-// What every per-row entry (mtg_predict, mtg_predict_at, mtg_gp_draw, mtg_apply_inverse) hands its kernels: the expanded
-// coefficients of the whole batch and the resident light curves (stage_rows of mtg_capi.hip fills it)
+// What every per-row entry (mtg_predict, mtg_predict_at, mtg_gp_draw, mtg_loglike_grad, mtg_apply_inverse) hands its
+// kernels: the expanded coefficients of the whole batch and the resident light curves (RowCall::expand of mtg_capi.hip
+// fills it)
 struct MtgRowArgs {
     const double *coef;     // SoA coefficient workspace (mtg_prepare_kernel), indexed by the row of the batch
     int64_t cstride;

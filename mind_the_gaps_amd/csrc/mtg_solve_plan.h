@@ -1,6 +1,7 @@
 // mtg_solve_plan.h -- which kernels solve a batch of prepared evaluations, decided from shapes alone: mtg_capi.hip's
 // solve_prepared builds an MtgPlanIn, asks mtg_plan_solve and launches the plan.  Plain C++17 without HIP, so that the
-// measured crossovers can be read in one place and run on the host (tests/solve_plan_driver.cpp).
+// measured crossovers can be read in one place and run on the host (tests/solve_plan_driver.cpp).  The sampler's run plan
+// and the rows per slab of mtg_predict_at and mtg_gp_draw are decided here in the same way.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -287,6 +288,38 @@ static inline void mtg_plan_name_paired(MtgSolvePlan &p, const MtgPlanIn &in)
 static inline bool mtg_plan_speculate(int tp_mode, int Jmodel, int64_t N, int64_t rows3)
 {
     return tp_mode != 0 && Jmodel <= 6 && N >= 256 && rows3 <= (N >= 4096 ? (Jmodel <= 5 ? 512 : 256) : 1024);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Rows per slab of the host-pointer entries that keep a whole row of device memory per evaluation (mtg_capi.hip)
+
+// device workspace of one slab of mtg_predict_at: rows whose stored generators (3 J + 3 doubles per sample) stay below this
+#define MTG_PAT_SLAB_BYTES ((size_t)1 << 30)
+// device memory of one slab of mtg_gp_draw: rows (a multiple of 64) whose draws stay below this, and as much again for
+// the caller's normals
+#define MTG_DRAW_SLAB_BYTES ((size_t)1 << 28)
+
+// mtg_predict_at: the stored generators within MTG_PAT_SLAB_BYTES, and the grid of the second stage -- rows x
+// ceil(M / 64) blocks -- within 2^30 blocks; at least one row, at most B.  0: M alone has more than 2^30 blocks
+static inline int64_t mtg_plan_predict_at_slab(int64_t N, int J, int64_t M, int64_t B)
+{
+    const size_t row_bytes = (size_t)N * (3 * J + 3) * 8;
+    int64_t Bs = (int64_t)(MTG_PAT_SLAB_BYTES / row_bytes);
+    const int64_t mblocks = (M + 63) / 64;
+    if (mblocks > ((int64_t)1 << 30)) return 0;
+    if (Bs > ((int64_t)1 << 30) / mblocks) Bs = ((int64_t)1 << 30) / mblocks;
+    if (Bs < 1) Bs = 1;
+    if (Bs > B) Bs = B;
+    return Bs;
+}
+
+// mtg_gp_draw: a multiple of 64 rows (a workgroup's tile) within MTG_DRAW_SLAB_BYTES, at least 64; or all B rows
+static inline int64_t mtg_plan_draw_slab(int64_t N, int64_t B)
+{
+    int64_t Bs = (int64_t)(MTG_DRAW_SLAB_BYTES / ((size_t)N * 8)) / 64 * 64;
+    if (Bs < 64) Bs = 64;
+    if (Bs > B) Bs = B;
+    return Bs;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

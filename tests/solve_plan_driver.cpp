@@ -1,7 +1,8 @@
 // Runs the solve planner (mind_the_gaps_amd/csrc/mtg_solve_plan.h) on the host for tests/test_solve_plan_cpu.py: one
 // case per line of standard input as key=value tokens, one line of the plan's decisions per case.  The catalogue is a
 // stub with the compiled ranges of the library; `no=<shape>` takes one kind of kernel out of it.  `run=1` asks for the
-// sampler's run plan instead, `sched=1` for that plan's whole schedule, from the priming launch to the last solve.
+// sampler's run plan instead, `sched=1` for that plan's whole schedule, from the priming launch to the last solve,
+// `slab=1` for the rows per slab of mtg_predict_at (N, the rank nr0 + 2 nc0, M, B) and of mtg_gp_draw (N, B).
 #include "mtg_solve_plan.h"
 
 #include <iostream>
@@ -32,8 +33,8 @@ int main()
     std::string line;
     while (std::getline(std::cin, line)) {
         MtgPlanIn in;
-        bool spec = false, run = false, sched = false;
-        long long E = 1, W = 8, steps = 3, spec_mode = 1, shard = 0, lo = 0, hi = 0, iter0 = 0;
+        bool spec = false, run = false, sched = false, slab = false;
+        long long E = 1, W = 8, steps = 3, spec_mode = 1, shard = 0, lo = 0, hi = 0, iter0 = 0, M = 1;
         g_missing.clear();
         std::istringstream tokens(line);
         std::string tok;
@@ -66,6 +67,8 @@ int main()
             else if (k == "spec") spec = x != 0;
             else if (k == "run") run = x != 0;
             else if (k == "sched") sched = x != 0;
+            else if (k == "slab") slab = x != 0;
+            else if (k == "M") M = x;
             else if (k == "E") E = x;
             else if (k == "W") W = x;
             else if (k == "steps") steps = x;
@@ -79,6 +82,11 @@ int main()
         if (in.Bw == 0) in.Bw = in.B;
         if (spec) {
             std::cout << "spec=" << mtg_plan_speculate(in.tp_mode, in.nr0 + 2 * in.nc0, in.N, in.B) << "\n";
+            continue;
+        }
+        if (slab) {
+            std::cout << "predict_at=" << mtg_plan_predict_at_slab(in.N, in.nr0 + 2 * in.nc0, M, in.B)
+                      << " draw=" << mtg_plan_draw_slab(in.N, in.B) << "\n";
             continue;
         }
         if (run || sched) {

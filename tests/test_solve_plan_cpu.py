@@ -2,7 +2,9 @@
 g++ against the header alone, runs a boundary table -- one step on each side of every crossover, the mode switches,
 and shapes taken out of the catalogue -- and every row's family, sort, fan-out, rank-10 chunk count and kernel name
 are checked.  The device sampler's run plan (mtg_plan_ensemble_run) gets a table of the same kind, and its schedule
-(mtg_ensemble_step) is compared launch by launch with rows written out by hand from the loops it replaced."""
+(mtg_ensemble_step) is compared launch by launch with rows written out by hand from the loops it replaced.  The rows per
+slab of mtg_predict_at and mtg_gp_draw (mtg_plan_predict_at_slab, mtg_plan_draw_slab) get a boundary table worked out by
+hand from the formulas the two entries carried inline."""
 import os
 import subprocess
 
@@ -181,6 +183,33 @@ SCHEDULES = [
     (dict(spec_mode=0, steps=0), []),
 ]
 
+# mtg_plan_draw_slab(N, B): floor(2^28 / 8 N) rows rounded down to a multiple of 64, at least 64, at most B.
+DRAW_SLAB = [  # (N, B) -> rows per slab
+    ((200000, 1000), 128),        # 167 rows fit: two tiles of 64 (tests/test_gp_draw_gpu.py crosses this boundary on the device)
+    ((200000, 128), 128), ((200000, 127), 127), ((200000, 100), 100),   # B below the slab: B
+    ((262144, 1000), 128),        # 2^28 / 2^21 = 128 exactly
+    ((262145, 1000), 64),         # 127 fit: one tile
+    ((524288, 1000), 64),         # a row of 2^28 / 64 bytes: 64 fit exactly
+    ((524289, 1000), 64),         # 8 bytes more: 63 fit, none after the rounding, the floor of one tile
+    ((1000000, 1000), 64),        # 33 fit: the floor
+    ((524289, 63), 63), ((1000000, 10), 10), ((100, 5), 5),             # B below 64: B
+]
+
+# mtg_plan_predict_at_slab(N, J, M, B): floor(2^30 / (8 N (3 J + 3))) rows, at most floor(2^30 / ceil(M / 64)) (the
+# second stage's grid), at least 1, at most B; 0 when ceil(M / 64) > 2^30.  N = 10^4, J = 5: rows of 1 440 000 bytes,
+# floor(1 073 741 824 / 1 440 000) = 745; the grid allows 745 rows up to 1 441 264 blocks (2^30 / 1 441 264 = 745.0001)
+# and 744 from 1 441 265 on (744.9996).
+PAT_SLAB = [  # (N, nr0, nc0, M, B) -> rows per slab
+    ((10000, 1, 2, 65, 1000), 745), ((10000, 1, 2, 65, 745), 745), ((10000, 1, 2, 65, 744), 744), ((10000, 1, 2, 65, 1), 1),
+    ((10000, 1, 2, 64 * 1441264, 1000), 745),          # 1 441 264 blocks: the memory still binds
+    ((10000, 1, 2, 64 * 1441264 + 1, 1000), 744),      # 1 441 265 blocks: the grid binds
+    ((10000, 1, 2, 64 * 1441264 + 1, 700), 700),
+    ((1000, 0, 0, 1, 100000), 44739),                  # J = 0: rows of 24 000 bytes
+    ((10000000, 1, 2, 65, 1000), 1),                   # a row of 1.44 GB, larger than the slab: one at a time
+    ((10000, 1, 2, 64 << 30, 1000), 1),                # 2^30 blocks: the last M the grid takes, a row at a time
+    ((10000, 1, 2, (64 << 30) + 1, 1000), 0),          # one more: refused (the entry's "M ... is too large")
+]
+
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
@@ -239,3 +268,10 @@ def test_ensemble_schedule(driver):
     for (inputs, want), out in zip(SCHEDULES, outs):
         got = [tuple(int(x) for x in row.split()) for row in out.split("|") if row.strip()]
         assert got == want, (inputs, got)
+
+
+def test_slab_sizes(driver):
+    outs = driver(["N=%d B=%d slab=1" % args for args, _ in DRAW_SLAB])
+    assert [o.split()[1] for o in outs] == ["draw=%d" % want for _, want in DRAW_SLAB]
+    outs = driver(["N=%d nr0=%d nc0=%d M=%d B=%d slab=1" % args for args, _ in PAT_SLAB])
+    assert [o.split()[0] for o in outs] == ["predict_at=%d" % want for _, want in PAT_SLAB]
