@@ -148,7 +148,7 @@ MTG_API int mtg_set_lightcurves_device(mtg_ctx *ctx, int64_t N, int64_t L, const
  * one-lane sweep alone (mtg_kernels_mean.hip): mtg_loglike_batch[_device],
  * mtg_loglike_coeffs, mtg_ensemble_* (sharded or not) and mtg_apply_inverse
  * (which does not read the mean) work with them; mtg_predict, mtg_predict_at,
- * mtg_gp_draw and mtg_loglike_grad return MTG_E_UNSUPPORTED (the host layer
+ * mtg_gp_draw, mtg_gp_cond_draw and mtg_loglike_grad return MTG_E_UNSUPPORTED (the host layer
  * binds y - mean(t) with a zero mean for those, one theta at a time), and a
  * context paired with mtg_pair_contexts launches alone.  A row whose mean is
  * not finite at some sample (sigma = 0) gets MTG_ST_NONFINITE.
@@ -554,6 +554,33 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
  */
 MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, uint64_t seed,
                         const double *normals /* [B][N] or NULL: Philox */, double *y /* [B][N] */, int32_t *status);
+
+/*
+ * celerite.GP.sample_conditional(y, t): B draws of the process GIVEN the resident data, at M new times ts[M] (any
+ * order, duplicates allowed, shared by all rows; a non-finite one is MTG_E_ARG; M == 0 is MTG_OK and writes nothing).
+ * celerite forms the dense M x N cross-covariance and factors the dense M x M conditional covariance; here Matheron's
+ * rule makes it two linear sweeps.  A joint prior draw (y~, f*) at the light curve's epochs (noisy: sigma^2 + jitter on
+ * the diagonal) and at the unique new times (latent: diagonal 0) comes from the factor step of mtg_gp_draw on the merged
+ * series, a new time equal to an epoch after it; then y*[b][m] = f* + mu, mu the conditional mean of mtg_predict_at
+ * for the light curve y - y~.  O((N + 64 M) J^2) per draw, device memory O(slab (N J + N J^2 / 64 + N + M)), nothing of
+ * size N x M or M x M.  y*[b][m] includes a fitted constant or linear mean and EXCLUDES the per-light-curve y_offset
+ * (as mtg_predict_at); entries of ts with the same time receive the same value.
+ *   normals  [B][N + M] standard normals of the caller (host): row b holds those of the N epochs in epoch order, then
+ *            one per entry of ts; a time given more than once takes the normal of its first entry and the others are
+ *            not read.  NULL: drawn on the device from Philox4x32-10 keyed by `seed`, counter (k, purpose, low word,
+ *            high word of first_index + b), first_index that of mtg_set_stream_base: block k of purpose
+ *            MTG_PURPOSE_GP_COND_EPOCH gives the Box-Muller pair of epochs 2k, 2k + 1, block k of
+ *            MTG_PURPOSE_GP_COND_NEW that of the unique new times of rank 2k, 2k + 1 in ascending order.  Draw b
+ *            therefore depends on (seed, first_index + b, theta[b], its light curve, the set of new times) alone: not
+ *            on B, on slabs, or on the order of ts.
+ * Statuses as mtg_predict_at: rows outside the prior or with a non-positive pivot (of K, or of the merged series) get
+ * their status and read back NaN.  mtg_last_solver names the sweep, "mtg_gp_cond_draw_kernel<J>".
+ */
+#define MTG_PURPOSE_GP_COND_EPOCH 13 /* Philox counter word c1; 12 is mtg_gp_draw's */
+#define MTG_PURPOSE_GP_COND_NEW 14
+MTG_API int mtg_gp_cond_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int64_t M,
+                             const double *ts, uint64_t seed, const double *normals /* [B][N + M] or NULL: Philox */,
+                             double *y /* [B][M] */, int32_t *status);
 
 /*
  * celerite.GP.grad_log_likelihood for B parameter vectors at once: out[b] = lnL(theta[b]) of light curve lc_index[b]

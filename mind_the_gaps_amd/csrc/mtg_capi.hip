@@ -888,7 +888,7 @@ int check_ready(mtg_ctx *ctx, bool need_model)
 }
 
 // One host-pointer call over rows of theta in flight (`who`: mtg_loglike_batch, mtg_loglike_coeffs, mtg_predict,
-// mtg_predict_at, mtg_gp_draw, mtg_loglike_grad, mtg_apply_inverse).  The entry runs ready, its own argument checks and
+// mtg_predict_at, mtg_gp_draw, mtg_gp_cond_draw, mtg_loglike_grad, mtg_apply_inverse).  The entry runs ready, its own argument checks and
 // begin -- in that order; each returns at once, nothing is queued yet -- then the stages below and its own reservations
 // and launches.  From stage_inputs on nothing returns early: a step runs only while the call is ok(), the first failure
 // is kept -- a HIP error in `e`, or in `rc` the code of a helper that has written its own report -- and finish() is the
@@ -972,6 +972,31 @@ int RowCall::finish(int32_t *status)
     if (rc) return rc;
     return e == hipSuccess ? MTG_OK : fail(ctx, MTG_E_HIP, "%s: %s", who, hipGetErrorString(e));
 }
+
+// The workspace of one slab of Bs rows of the new-time prediction (mtg_predict_at, mtg_gp_cond_draw) and everything of
+// its kernels' arguments but the slab's rows: the M times uploaded, with the order to visit them in unless they ascend
+// as given (order == NULL)
+struct PredictAtRoom {
+    DevBuf work, ckf, ckb, ckr, mu, var, ts, order;
+    void reserve(RowCall &c, MtgPredictAtArgs &qa, int64_t Bs, int J, int64_t M, const double *h_ts, const int64_t *h_order,
+                 bool want_var)
+    {
+        const int64_t N = c.ctx->N;
+        const size_t row_bytes = (size_t)N * (3 * J + 3) * 8, tri_bytes = (size_t)(J * (J + 1) / 2) * 8;
+        const int64_t nck = (N + MTG_PAT_C - 1) / MTG_PAT_C;
+        const size_t ck_bytes = (size_t)nck * (tri_bytes + J * 8), ts_bytes = (size_t)M * 8;
+        c.reserve({{work, (size_t)Bs * row_bytes + 8}, {ckf, (size_t)Bs * ck_bytes + 8}, {ckb, (size_t)Bs * ck_bytes + 8},
+                   {ckr, (size_t)Bs * tri_bytes + 8}, {mu, (size_t)Bs * ts_bytes}, {var, want_var ? (size_t)Bs * ts_bytes : 0},
+                   {ts, ts_bytes}, {order, h_order ? ts_bytes : 0}});
+        c.upload(ts.p, h_ts, ts_bytes);
+        if (h_order) c.upload(order.p, h_order, ts_bytes);
+        qa.work = work.as<double>();
+        qa.nck = nck; qa.ckf = ckf.as<double>(); qa.ckb = ckb.as<double>(); qa.ckr = ckr.as<double>(); qa.want_var = want_var ? 1 : 0;
+        qa.M = M; qa.ts = ts.as<double>(); qa.order = h_order ? order.as<int64_t>() : nullptr;
+        qa.mu = mu.as<double>(); qa.var = want_var ? var.as<double>() : nullptr;
+        qa.data = nullptr;
+    }
+};
 
 }  // namespace
 
@@ -2397,28 +2422,18 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
     if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_predict_at: rank %d > %d", J, MTG_MAX_J);
     const int64_t Bs = mtg_plan_predict_at_slab(N, J, M, B);
     if (Bs == 0) return fail(ctx, MTG_E_ARG, "mtg_predict_at: M = %lld is too large", (long long)M);
-    const size_t row_bytes = (size_t)N * (3 * J + 3) * 8, tri_bytes = (size_t)(J * (J + 1) / 2) * 8;
-    const int64_t nck = (N + MTG_PAT_C - 1) / MTG_PAT_C;
-    const size_t ck_bytes = (size_t)nck * (tri_bytes + J * 8), ts_bytes = (size_t)M * 8;
+    const size_t ts_bytes = (size_t)M * 8;
     MtgPredictAtArgs qa;
     c.stage_inputs();
     c.expand(qa);
-    DevBuf work, ckf, ckb, ckr, d_mu, d_var, d_ts, d_order;
-    c.reserve({{work, (size_t)Bs * row_bytes + 8}, {ckf, (size_t)Bs * ck_bytes + 8}, {ckb, (size_t)Bs * ck_bytes + 8},
-               {ckr, (size_t)Bs * tri_bytes + 8}, {d_mu, (size_t)Bs * ts_bytes}, {d_var, var ? (size_t)Bs * ts_bytes : 0},
-               {d_ts, ts_bytes}, {d_order, ascending ? 0 : ts_bytes}});
-    c.upload(d_ts.p, ts, ts_bytes);
-    if (!ascending) c.upload(d_order.p, order.data(), ts_bytes);
-    qa.work = work.as<double>();
-    qa.nck = nck; qa.ckf = ckf.as<double>(); qa.ckb = ckb.as<double>(); qa.ckr = ckr.as<double>(); qa.want_var = var ? 1 : 0;
-    qa.M = M; qa.ts = d_ts.as<double>(); qa.order = ascending ? nullptr : d_order.as<int64_t>();
-    qa.mu = d_mu.as<double>(); qa.var = var ? d_var.as<double>() : nullptr;
+    PredictAtRoom room;
+    room.reserve(c, qa, Bs, J, M, ts, ascending ? nullptr : order.data(), var != nullptr);
     if (c.ok()) c.e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
         qa.row0 = row0; qa.B = rows;
         c.then([&] { return mtg_launch_predict_at(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
         // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
-        c.gather(mu + row0 * M, d_mu.p, (size_t)rows * ts_bytes);
-        if (var) c.gather(var + row0 * M, d_var.p, (size_t)rows * ts_bytes);
+        c.gather(mu + row0 * M, room.mu.p, (size_t)rows * ts_bytes);
+        if (var) c.gather(var + row0 * M, room.var.p, (size_t)rows * ts_bytes);
         return c.e;
     });
     return c.finish(status);
@@ -2451,6 +2466,66 @@ MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int3
         if (normals) c.upload(d_q.p, normals + row0 * N, (size_t)rows * row_bytes);
         c.then([&] { return mtg_launch_gp_draw(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
         c.gather(y + row0 * N, d_y.p, (size_t)rows * row_bytes);
+        return c.e;
+    });
+    return c.finish(status);
+}
+
+MTG_API int mtg_gp_cond_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int64_t M,
+                             const double *ts, uint64_t seed, const double *normals, double *y, int32_t *status)
+{
+    RowCall c{ctx, "mtg_gp_cond_draw", B, theta, lc_index, 1};
+    int rc = c.ready();
+    if (rc) return rc;
+    if (B <= 0 || M < 0 || (M > 0 && (!ts || !y)) || !status || (!theta && ctx->model.P > 0)) return c.bad_arguments();
+    if ((rc = c.begin(true))) return rc;
+    for (int64_t m = 0; m < M; ++m)
+        if (!std::isfinite(ts[m])) return fail(ctx, MTG_E_ARG, "mtg_gp_cond_draw: ts[%lld] is not finite", (long long)m);
+    if (M == 0) return MTG_OK;
+    // the unique times in ascending order, for each the first entry of ts that holds it (the sort is stable), and for
+    // each entry of ts its unique time
+    std::vector<int64_t> order((size_t)M), first, inv((size_t)M);
+    for (int64_t m = 0; m < M; ++m) order[(size_t)m] = m;
+    std::stable_sort(order.begin(), order.end(), [ts](int64_t i, int64_t j) { return ts[i] < ts[j]; });
+    std::vector<double> tu;
+    for (int64_t m : order) {
+        if (tu.empty() || ts[m] != tu.back()) { tu.push_back(ts[m]); first.push_back(m); }
+        inv[(size_t)m] = (int64_t)tu.size() - 1;
+    }
+    const int64_t Mu = (int64_t)tu.size();
+    const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
+    const int64_t N = ctx->N;
+    if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_gp_cond_draw: rank %d > %d", J, MTG_MAX_J);
+    const size_t q_bytes = (size_t)(N + M) * 8;
+    // (M >= Mu: the scatter's grid as well as the evaluation's; a row's normals, y - y~, f*, mu and draws within the budget)
+    const int64_t Bs = mtg_plan_predict_at_slab(N, J, M, B, (normals ? q_bytes : 0) + (size_t)(N + 2 * Mu + M) * 8);
+    if (Bs == 0) return fail(ctx, MTG_E_ARG, "mtg_gp_cond_draw: M = %lld is too large", (long long)M);
+    MtgPredictAtArgs qa;
+    MtgGpCondDrawArgs da;
+    c.stage_inputs();
+    c.expand(qa);
+    static_cast<MtgRowArgs &>(da) = qa;
+    PredictAtRoom room;
+    room.reserve(c, qa, Bs, J, Mu, tu.data(), nullptr, false);
+    DevBuf d_first, d_inv, d_q, d_data, d_fs, d_y;
+    c.reserve({{d_first, normals ? (size_t)Mu * 8 : 0}, {d_inv, (size_t)M * 8}, {d_q, normals ? (size_t)Bs * q_bytes : 0},
+               {d_data, (size_t)Bs * N * 8}, {d_fs, (size_t)Bs * Mu * 8}, {d_y, (size_t)Bs * M * 8}});
+    if (normals) c.upload(d_first.p, first.data(), (size_t)Mu * 8);
+    c.upload(d_inv.p, inv.data(), (size_t)M * 8);
+    da.Mu = Mu; da.tu = qa.ts; da.first = normals ? d_first.as<int64_t>() : nullptr; da.M = M; da.inv = d_inv.as<int64_t>();
+    da.normals = normals ? d_q.as<double>() : nullptr;
+    da.seed_lo = (uint32_t)seed; da.seed_hi = (uint32_t)(seed >> 32); da.draw0 = ctx->stream_base;
+    da.data = d_data.as<double>(); da.fs = d_fs.as<double>(); da.mu = qa.mu; da.y = d_y.as<double>();
+    qa.data = da.data;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_gp_cond_draw_kernel<%d>", J);
+    if (c.ok()) c.e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
+        qa.row0 = da.row0 = row0; qa.B = da.B = rows;
+        // (the copies are ordered on the stream: the next slab's upload and kernels touch the buffers only after them)
+        if (normals) c.upload(d_q.p, normals + row0 * (N + M), (size_t)rows * q_bytes);
+        c.then([&] { return mtg_launch_gp_cond_draw(da, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        c.then([&] { return mtg_launch_predict_at(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        c.then([&] { mtg_launch_gp_cond_scatter(da, c.s); return hipGetLastError(); });
+        c.gather(y + row0 * M, d_y.p, (size_t)rows * M * 8);
         return c.e;
     });
     return c.finish(status);

@@ -171,9 +171,31 @@ struct MtgPredictAtArgs : MtgRowArgs {
     const double *ts;       // [M] new times
     const int64_t *order;   // [M] ts in ascending order (indices into ts), or NULL: ts is ascending as given
     double *mu, *var;       // [B][M]
+    const double *data;     // [B][N] of this slab: read in place of the resident data y (mtg_gp_cond_draw), or NULL
 };
 // both stages of the new-time prediction for one slab; 0 = rank outside 0 .. MTG_MAX_J
 int mtg_launch_predict_at(const MtgPredictAtArgs &, hipStream_t);
+
+// The joint prior draw of the conditional draw (mtg_gp_cond_draw.hip) on the light curve's epochs merged with the
+// unique new times tu, and the last step of Matheron's rule.  The sweep leaves y - y~ in `data` for mtg_launch_predict_at
+// and the latent f* in `fs`; the scatter adds the two at every entry of the caller's ts.
+struct MtgGpCondDrawArgs : MtgRowArgs {
+    int64_t Mu;             // unique new times
+    const double *tu;       // [Mu] ascending
+    const int64_t *first;   // [Mu] index in the caller's ts of the first entry with this time (the caller's normals only)
+    int64_t M;              // entries of the caller's ts
+    const int64_t *inv;     // [M] index into tu of each of them
+    const double *normals;  // [B][N + M] of this slab, or NULL: Philox on the device
+    uint32_t seed_lo, seed_hi;
+    int64_t draw0;          // global index of row 0 of the batch (mtg_set_stream_base): random counters only
+    double *data;           // [B][N]  y_n - y~_n
+    double *fs;             // [B][Mu] f*_u
+    const double *mu;       // [B][Mu] of mtg_launch_predict_at with `data`
+    double *y;              // [B][M]
+};
+// one slab: the sweep (0 = rank outside 0 .. MTG_MAX_J), and after mtg_launch_predict_at the scatter
+int mtg_launch_gp_cond_draw(const MtgGpCondDrawArgs &, hipStream_t);
+void mtg_launch_gp_cond_scatter(const MtgGpCondDrawArgs &, hipStream_t);
 
 // samples per LDS tile of the GP draw (mtg_gp_draw.hip): 64 rows x MTG_DRAW_T samples, row stride MTG_DRAW_T + 1 doubles
 #ifndef MTG_DRAW_T
@@ -208,7 +230,8 @@ struct MtgGradArgs : MtgRowArgs {       // the whole batch in one launch: row0 =
 // coefficient tangents, then the tangent sweep; 0 = rank outside 0 .. MTG_GRAD_MAX_J
 int mtg_launch_loglike_grad(const MtgGradArgs &, hipStream_t);
 static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivially_copyable<MtgPredictAtArgs>::value &&
-              std::is_trivially_copyable<MtgGpDrawArgs>::value && std::is_trivially_copyable<MtgGradArgs>::value,
+              std::is_trivially_copyable<MtgGpDrawArgs>::value && std::is_trivially_copyable<MtgGradArgs>::value &&
+              std::is_trivially_copyable<MtgGpCondDrawArgs>::value,
               "passed by value as kernel arguments");
 
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);

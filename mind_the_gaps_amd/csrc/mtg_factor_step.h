@@ -1,6 +1,6 @@
 // mtg_factor_step.h -- the forward step of the semiseparable factorisation with the state in registers (template on
 // the rank J, runtime split NR real slots | complex pairs): coefficient load, generators, decay, the (S, f)
-// recurrence and the pivot; and the switch from a runtime rank to the template.  Shared by mtg_predict_at.hip (factorisation + replay) and mtg_gp_draw.hip (the draw y = L sqrt(D) q).
+// recurrence and the pivot; and the switch from a runtime rank to the template.  Shared by mtg_predict_at.hip (factorisation + replay), mtg_gp_draw.hip (the draw y = L sqrt(D) q) and mtg_gp_cond_draw.hip (the same draw on the merged series).
 #pragma once
 #include "mtg_math.h"
 #include "mtg_device.h"

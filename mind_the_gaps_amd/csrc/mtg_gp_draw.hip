@@ -105,15 +105,8 @@ __global__ void __launch_bounds__(64) mtg_gp_draw_kernel(MtgGpDrawArgs a)
                 if constexpr (GIVEN) {
                     qn = s_q[lane * TS + j];
                 } else {
-                    if ((j & 1) == 0) {               // T is even: pairs do not straddle tiles
-                        const Philox rnd = philox4x32_10((uint32_t)(n >> 1), PURPOSE_GP_DRAW, (uint32_t)g, (uint32_t)(g >> 32),
-                                                         a.seed_lo, a.seed_hi);
-                        const double u1 = 1.0 - u01(rnd.c[0], rnd.c[1]), u2 = u01(rnd.c[2], rnd.c[3]);
-                        const double rad = sqrt(-2.0 * log(u1));
-                        double sn, cn;
-                        sincospi(2.0 * u2, &sn, &cn);
-                        qa = rad * cn; qb = rad * sn;
-                    }
+                    // T is even: pairs do not straddle tiles
+                    if ((j & 1) == 0) philox_normal_pair((uint32_t)(n >> 1), PURPOSE_GP_DRAW, g, a.seed_lo, a.seed_hi, qa, qb);
                     qn = (j & 1) ? qb : qa;
                 }
                 const double dx = dxt[n].x, t = dxt[n].y;

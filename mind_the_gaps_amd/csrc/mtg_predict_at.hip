@@ -74,7 +74,8 @@ __device__ __forceinline__ void pat_bwd_G(double *G, const double *phn, const do
             G[pat_sy(i, j)] = G[pat_sy(i, j)] - U[i] * XW[j] - XW[i] * U[j] + U[i] * U[j] * h;
 }
 
-template <int J>
+// DATA: row r of a.data stands in for the light curve's y (the conditional draw conditions on y - y~, mtg_gp_cond_draw.hip)
+template <int J, bool DATA>
 __global__ void __launch_bounds__(64) mtg_predict_at_factor_kernel(MtgPredictAtArgs a)
 {
 #pragma clang fp contract(off)
@@ -111,7 +112,9 @@ __global__ void __launch_bounds__(64) mtg_predict_at_factor_kernel(MtgPredictAtA
 #pragma unroll
             for (int i = 0; i < J; ++i) c[SY + i] = f[i];
         }
-        double D = yv[n].y + k.asum, z = yv[n].x - (k.slope * t + k.icpt);
+        double yn;
+        if constexpr (DATA) yn = a.data[r * N + n]; else yn = yv[n].x;
+        double D = yv[n].y + k.asum, z = yn - (k.slope * t + k.icpt);
         double Wn[J];
 #pragma unroll
         for (int i = 0; i < J; ++i) z -= U[i] * f[i];
@@ -382,7 +385,9 @@ template <int J>
 struct PatLaunch {
     static void launch(const MtgPredictAtArgs &a, hipStream_t s)
     {
-        hipLaunchKernelGGL(mtg_predict_at_factor_kernel<J>, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
+        const dim3 rows((unsigned)((a.B + 63) / 64));
+        if (a.data) hipLaunchKernelGGL((mtg_predict_at_factor_kernel<J, true>), rows, dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((mtg_predict_at_factor_kernel<J, false>), rows, dim3(64), 0, s, a);
         hipLaunchKernelGGL(mtg_predict_at_eval_kernel<J>, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
     }
 };

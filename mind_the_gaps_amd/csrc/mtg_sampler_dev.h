@@ -39,6 +39,21 @@ __host__ __device__ inline double u01(uint32_t hi, uint32_t lo)
 
 enum { PURPOSE_SPLIT = 1, PURPOSE_PROPOSE = 2, PURPOSE_ACCEPT = 3 };
 
+// The Box-Muller pair of the Philox block (c0, purpose, low word, high word of g), key = the seed: u1 = 1 - u01(r0, r1)
+// in (0, 1], u2 = u01(r2, r3), rad = sqrt(-2 ln u1), qa = rad cos(2 pi u2), qb = rad sin(2 pi u2) (mtg_gp_draw.hip,
+// mtg_gp_cond_draw.hip)
+__device__ __forceinline__ void philox_normal_pair(uint32_t c0, uint32_t purpose, uint64_t g, uint32_t seed_lo, uint32_t seed_hi,
+                                                   double &qa, double &qb)
+{
+#pragma clang fp contract(off)
+    const Philox rnd = philox4x32_10(c0, purpose, (uint32_t)g, (uint32_t)(g >> 32), seed_lo, seed_hi);
+    const double u1 = 1.0 - u01(rnd.c[0], rnd.c[1]), u2 = u01(rnd.c[2], rnd.c[3]);
+    const double rad = sqrt(-2.0 * log(u1));
+    double sn, cn;
+    sincospi(2.0 * u2, &sn, &cn);
+    qa = rad * cn; qb = rad * sn;
+}
+
 }  // namespace
 
 // Red/blue split + stretch proposal + theta -> coefficients for the `half`-th half of every

@@ -301,9 +301,11 @@ static inline bool mtg_plan_speculate(int tp_mode, int Jmodel, int64_t N, int64_
 
 // mtg_predict_at: the stored generators within MTG_PAT_SLAB_BYTES, and the grid of the second stage -- rows x
 // ceil(M / 64) blocks -- within 2^30 blocks; at least one row, at most B.  0: M alone has more than 2^30 blocks
-static inline int64_t mtg_plan_predict_at_slab(int64_t N, int J, int64_t M, int64_t B)
+// more_row_bytes: what a caller keeps per row of the slab beside the generators (mtg_gp_cond_draw: its normals, y - y~,
+// f*, mu and the draws, which grow with M), counted within the same budget
+static inline int64_t mtg_plan_predict_at_slab(int64_t N, int J, int64_t M, int64_t B, size_t more_row_bytes = 0)
 {
-    const size_t row_bytes = (size_t)N * (3 * J + 3) * 8;
+    const size_t row_bytes = (size_t)N * (3 * J + 3) * 8 + more_row_bytes;
     int64_t Bs = (int64_t)(MTG_PAT_SLAB_BYTES / row_bytes);
     const int64_t mblocks = (M + 63) / 64;
     if (mblocks > ((int64_t)1 << 30)) return 0;

@@ -39,7 +39,7 @@ EXPORTS = (
     "mtg_chain_autocorr", "mtg_fft_warmup", "mtg_simulate_plan", "mtg_ensemble_restore", "mtg_set_sort", "mtg_set_pipeline", "mtg_set_stream_base", "mtg_set_speculation", "mtg_last_solver", "mtg_pair_contexts", "mtg_unpair_contexts", "mtg_pair_stats", "mtg_set_simulate_pairs", "mtg_set_simulate_transform", "mtg_set_simulate_pdf", "mtg_set_simulate_kraft", "mtg_set_simulate_pdf_draws", "mtg_simulate_pdf_report", "mtg_set_pair_patience", "mtg_chain_autocorr_plans_built",
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
-    "mtg_predict_at", "mtg_gp_draw", "mtg_loglike_grad", "mtg_mean_nparams",
+    "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
 )
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
@@ -320,6 +320,8 @@ def load_library():
     lib.mtg_predict_at.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, _dp, _dp, _ip]
     lib.mtg_gp_draw.restype = c_int
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
+    lib.mtg_gp_cond_draw.restype = c_int
+    lib.mtg_gp_cond_draw.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_loglike_grad.restype = c_int
     lib.mtg_loglike_grad.argtypes = [c_vp, c_i64, _dp, _ip, c_int, _dp, _dp, _ip]
     lib.mtg_math_probe.restype = c_int
@@ -786,6 +788,28 @@ class Engine:
                                           _ptr(y), _iptr(status)))
         return y, status
 
+    def gp_cond_draw(self, theta, ts, lc_index=None, seed=0, normals=None):
+        """Draws of the process given the data of light curve ``lc_index[b]``, at new times ``ts`` [M] (any order,
+        duplicates allowed) -> (y[B][M], status[B]); y excludes the per-light-curve y_offset.  Matheron's rule on the
+        device, linear in N and M: a joint prior draw on the epochs merged with the new times, then the conditional
+        mean of ``predict_at`` for the data minus that draw (mtg_gp_cond_draw).  ``normals`` [B][N + M]: the caller's
+        standard normals, the N epochs' and then one per entry of ``ts`` (a repeated time uses its first entry's);
+        None: drawn on the device from ``seed`` and the draw's global index (``set_stream_base``), so that a draw
+        depends neither on the batch it travels in nor on the order of ``ts``."""
+        theta = np.atleast_2d(_f64(theta))
+        ts = _f64(np.atleast_1d(ts)).ravel()
+        B, M = theta.shape[0], len(ts)
+        lc = None if lc_index is None else np.ascontiguousarray(lc_index, dtype=np.int32)
+        if normals is not None:
+            normals = _f64(normals).reshape(-1, self.N + M)
+            if normals.shape[0] != B:
+                raise ValueError("normals must have shape (%d, %d)" % (B, self.N + M))
+        y = np.full((B, M), np.nan)
+        status = np.zeros(B, dtype=np.int32)            # (M = 0: the library writes nothing, statuses included)
+        self._check(self._lib.mtg_gp_cond_draw(self._ctx, B, _ptr(theta), _iptr(lc), M, _ptr(ts),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(normals), _ptr(y), _iptr(status)))
+        return y, status
+
     def loglike_grad(self, theta, lc_index=None, add_prior=False):
         """theta [B][P] -> (lnL[B], grad[B][P], status[B]): the log-likelihood and its analytic gradient by the free
         parameters from one launch (mtg_loglike_grad).  The box prior is flat: ``add_prior`` only decides which rows are
@@ -948,6 +972,6 @@ class Engine:
 
 for _name in ("set_lightcurves", "set_lightcurves_device", "set_model", "loglike", "loglike_device", "loglike_coeffs",
               "ensemble_init", "ensemble_run", "ensemble_restore", "ensemble_state", "chain_autocorr", "simulate_tk95",
-              "tk95_observe_series", "predict", "predict_at", "gp_draw", "loglike_grad", "apply_inverse", "math_probe"):
+              "tk95_observe_series", "predict", "predict_at", "gp_draw", "gp_cond_draw", "loglike_grad", "apply_inverse", "math_probe"):
     setattr(Engine, _name, _one_thread_at_a_time(getattr(Engine, _name)))
 del _name

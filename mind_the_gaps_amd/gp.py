@@ -435,6 +435,26 @@ class GP(ModelSet):
         y += mean_at(self._t)
         return y[0] if size is None else y
 
+    def sample_conditional(self, y, t=None, size=None, seed=None):
+        """Realisations of the process given the data ``y``, at times ``t`` (celerite.GP.sample_conditional; ``t=None``:
+        the computed times, where the draw is of the latent process, without measurement noise, as celerite's is):
+        ``[M]`` for ``size=None``, else ``[size][M]``.  celerite draws from the dense conditional covariance of
+        ``predict``; here each draw is Matheron's rule on the device, linear in N and M (``Engine.gp_cond_draw``).
+        ``seed`` as in ``sample``: None takes the normals from numpy's global generator, an integer lets the device
+        draw them.  Under a profile mean the device sees ``y - mean(t)`` with a zero mean and ``mean.get_value`` is
+        added back, as in ``predict``."""
+        eng, model, mean_at = self._mean_engine(y)
+        xs = self._t if t is None else np.atleast_1d(np.asarray(t, dtype=np.float64))
+        n = 1 if size is None else int(size)
+        if n == 0:
+            return np.empty((0, len(xs)))
+        theta = np.tile(model.full[model.free_index][None, :], (n, 1))
+        normals = np.random.randn(n, len(self._t) + len(xs)) if seed is None else None
+        out, status = eng.gp_cond_draw(theta, xs, seed=0 if seed is None else int(seed), normals=normals)
+        self._raise_for(status[0])                      # every row has the same theta, hence the same status
+        out += mean_at(xs)
+        return out[0] if size is None else out
+
     def predict(self, y, t=None, return_cov=True, return_var=False):
         """Conditional mean and (co)variance, celerite.GP.predict.
 

@@ -399,6 +399,39 @@ class GPModelling:
                 self.gp.set_parameter_vector(saved)
         return (mu[0], var[0]) if parameters.ndim == 1 else (mu, var)
 
+    def sample_conditional(self, times=None, nsims: int = 1, parameters=None, seed=None):
+        """``nsims`` light curves drawn from the process given the data, at ``times`` [M] (None: the observed epochs) ->
+        [nsims][M]: what fills a gap with realisations consistent with both the data and the fitted kernel
+        (``GP.sample_conditional``, linear in N and M).  ``parameters``: None -- ``nsims`` vectors drawn from the stored
+        posterior samples as ``generate_from_posteriors`` draws them, one light curve each -- or one vector [P], used
+        for every draw.  ``seed``: None takes the choice of samples and the device's seed from numpy's global
+        generator; an integer makes the call reproducible by itself."""
+        rng = np.random if seed is None else np.random.RandomState(int(seed))
+        if parameters is None:
+            if self._mcmc_samples is None:
+                raise RuntimeError(self._NOT_DERIVED)
+            theta = self._mcmc_samples[rng.randint(len(self._mcmc_samples), size=nsims)]
+        else:
+            theta = np.tile(np.asarray(parameters, dtype=np.float64)[None, :], (nsims, 1))
+        dev_seed = int(rng.randint(0, 2 ** 31 - 1))
+        times = self._lightcurve.times if times is None else np.atleast_1d(np.asarray(times, dtype=np.float64))
+        if self.gp._has_profile_mean():
+            # one vector at a time, as predict_at: the residual y - mean(t) at that vector bound with a zero mean
+            saved = self.gp.get_parameter_vector()
+            try:
+                rows = []
+                for b in range(nsims):
+                    self.gp.set_parameter_vector(theta[b])
+                    rows.append(self.gp.sample_conditional(self._lightcurve.y, t=times, seed=dev_seed + b))
+            finally:
+                self.gp.set_parameter_vector(saved)
+            return np.array(rows)
+        eng, model = self.gp._bound_engine(self._lightcurve.y)
+        y, status = eng.gp_cond_draw(theta, times, seed=dev_seed)
+        for st in status:
+            self.gp._raise_for(st)
+        return y + (model.y_offset or 0.0)
+
     def get_rstat(self, burnin: int = None):
         """Gelman-Rubin-like statistic as the reference computes it
         (gpmodelling.py:373-403): within-chain over total variance."""
