@@ -147,7 +147,7 @@ MTG_API int mtg_set_lightcurves_device(mtg_ctx *ctx, int64_t N, int64_t L, const
  * The profile means (MTG_MEAN_SINE, _TWOSINE, _GAUSSIAN) are evaluated by the
  * one-lane sweep alone (mtg_kernels_mean.hip): mtg_loglike_batch[_device],
  * mtg_loglike_coeffs, mtg_ensemble_* (sharded or not) and mtg_apply_inverse
- * (which does not read the mean) work with them; mtg_predict, mtg_predict_at,
+ * (which does not read the mean) work with them; mtg_predict, mtg_predict_at, mtg_predict_terms,
  * mtg_gp_draw, mtg_gp_cond_draw and mtg_loglike_grad return MTG_E_UNSUPPORTED (the host layer
  * binds y - mean(t) with a zero mean for those, one theta at a time), and a
  * context paired with mtg_pair_contexts launches alone.  A row whose mean is
@@ -535,6 +535,34 @@ MTG_API int mtg_apply_inverse(mtg_ctx *ctx, const double *theta, int32_t lc_inde
  */
 MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index,
                            int64_t M, const double *ts, double *mu, double *var, int32_t *status);
+
+/*
+ * celerite.GP.predict(y, t=ts, return_var=True, kernel=k_c): the conditional mean and variance of ONE COMPONENT of the
+ * sum kernel given the data, for T components in one call ("the QPO and the red noise separately").  Component c is
+ * the sum k_c of the terms whose bit is set in term_mask[c] -- bit k = term k of the model in the `+` order of
+ * mtg_set_model; 1 <= T <= 32; a bit at or beyond nterms other than MTG_TERMS_MEAN is MTG_E_ARG; a mask of 0 is
+ * allowed.  With r = y - mean and K the covariance of the WHOLE model (never of the component),
+ *   mu[b][c][m]  = k_c(t*_m, t) K^-1 r          (+ the constant or linear mean at t*_m with MTG_TERMS_MEAN in the mask;
+ *                                                the per-light-curve y_offset is excluded, as in mtg_predict_at)
+ *   var[b][c][m] = k_c(0) - k_c,*^T K^-1 k_c,*  (var == NULL: means only)
+ * both noise-free, like mtg_predict_at: a MTG_TERM_JITTER term contributes nothing to either, and a mask of 0 or of
+ * jitter terms alone gives mu = 0 (or the mean) and var = 0.  The means of single-term masks add up to the all-terms
+ * mean; the variances do not (the components are correlated given the data).
+ * celerite forms the dense M x N cross-covariance of the sub-kernel.  Here the factorisation, its checkpoints and the
+ * replay to t* are mtg_predict_at's and are done once per (row, time); only the generators at t* and k(0) are
+ * restricted to the slots of the selected terms, J^2 operations per mask: T components cost little more than one
+ * mtg_predict_at plus the T times larger copy back.  Which slots a term owns is decided per row where the slots are
+ * handed out (an SHO term owns two real slots when over-damped, a complex pair otherwise).  With every term selected
+ * and MTG_TERMS_MEAN, mu and var are bit for bit mtg_predict_at's; every (row, time, mask) result is independent of B,
+ * M, T, the order of ts and the order of the masks.
+ * Everything else as mtg_predict_at: ts in any order, duplicates allowed, a non-finite one is MTG_E_ARG; rows in
+ * slabs; rows outside the prior or not positive definite keep their status and read back NaN; ranks above MTG_MAX_J
+ * and profile means return MTG_E_UNSUPPORTED.  mtg_last_solver names "mtg_predict_terms_eval_kernel<J>".
+ */
+#define MTG_TERMS_MEAN (1u << 31)
+MTG_API int mtg_predict_terms(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int T,
+                              const uint32_t *term_mask /* [T] */, int64_t M, const double *ts,
+                              double *mu /* [B][T][M] */, double *var /* [B][T][M] or NULL */, int32_t *status);
 
 /*
  * celerite.GP.sample(size) -> solver.dot_L: B realisations of the process itself, y[b] ~ N(mean, K(theta[b])) on the

@@ -888,7 +888,7 @@ int check_ready(mtg_ctx *ctx, bool need_model)
 }
 
 // One host-pointer call over rows of theta in flight (`who`: mtg_loglike_batch, mtg_loglike_coeffs, mtg_predict,
-// mtg_predict_at, mtg_gp_draw, mtg_gp_cond_draw, mtg_loglike_grad, mtg_apply_inverse).  The entry runs ready, its own argument checks and
+// mtg_predict_at, mtg_predict_terms, mtg_gp_draw, mtg_gp_cond_draw, mtg_loglike_grad, mtg_apply_inverse).  The entry runs ready, its own argument checks and
 // begin -- in that order; each returns at once, nothing is queued yet -- then the stages below and its own reservations
 // and launches.  From stage_inputs on nothing returns early: a step runs only while the call is ok(), the first failure
 // is kept -- a HIP error in `e`, or in `rc` the code of a helper that has written its own report -- and finish() is the
@@ -912,7 +912,7 @@ struct RowCall {
     int bad_arguments() { return fail(ctx, MTG_E_ARG, "%s: bad arguments", who); }
     int begin(bool refuse_profile);
     void stage_inputs(bool with_theta = true);
-    void expand(MtgRowArgs &head);
+    void expand(MtgRowArgs &head, DevBuf *owner = nullptr);
     template <class F> void then(F step) { if (ok()) e = step(); }   // step() -> hipError_t
     void reserve(std::initializer_list<Room> rooms) { for (const Room &r : rooms) then([&] { return r.buf.reserve(r.bytes); }); }
     void upload(void *dev, const void *host, size_t bytes) { then([&] { return hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s); }); }
@@ -945,14 +945,16 @@ void RowCall::stage_inputs(bool with_theta)
 
 // The staged theta expanded into the coefficient workspace -- the prior's verdict in ctx->status, the structure of every
 // row in ctx->sig -- and the head of the per-row kernels' arguments filled for the whole batch.  (ctx->sig, like
-// ctx->coef, is rewritten by every expansion and read by nothing before the next one.)
-void RowCall::expand(MtgRowArgs &head)
+// ctx->coef, is rewritten by every expansion and read by nothing before the next one.)  owner (mtg_predict_terms): room
+// for, and from this expansion, the term of every slot of every accepted row, [nr_max + nc_max][cstride] int32.
+void RowCall::expand(MtgRowArgs &head, DevBuf *owner)
 {
     const MtgModel &m = ctx->model;
     if (ok()) rc = reserve_workspace(ctx, B, model_nslots(m), 1);
+    if (owner) reserve({{*owner, (size_t)(m.nr_max + m.nc_max) * (size_t)ctx->cstride * 4}});
     then([&] {
         mtg_launch_prepare(make_prep_args(ctx, B, ctx->theta.as<double>(), add_prior, ctx->out.as<double>(),
-                                          ctx->status.as<int32_t>(), 1), s);
+                                          ctx->status.as<int32_t>(), 1), s, owner ? owner->as<int32_t>() : nullptr);
         return hipGetLastError();
     });
     head.coef = ctx->coef.as<double>(); head.cstride = ctx->cstride; head.lay = MtgCoefLayout{m.nr_max, m.nc_max};
@@ -2434,6 +2436,62 @@ MTG_API int mtg_predict_at(mtg_ctx *ctx, int64_t B, const double *theta, const i
         // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
         c.gather(mu + row0 * M, room.mu.p, (size_t)rows * ts_bytes);
         if (var) c.gather(var + row0 * M, room.var.p, (size_t)rows * ts_bytes);
+        return c.e;
+    });
+    return c.finish(status);
+}
+
+MTG_API int mtg_predict_terms(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int T,
+                              const uint32_t *term_mask, int64_t M, const double *ts, double *mu, double *var, int32_t *status)
+{
+    RowCall c{ctx, "mtg_predict_terms", B, theta, lc_index, 1};
+    int rc = c.ready();
+    if (rc) return rc;
+    if (B <= 0 || T < 1 || T > 32 || !term_mask || M <= 0 || !ts || !mu || !status || (!theta && ctx->model.P > 0))
+        return c.bad_arguments();
+    if ((rc = c.begin(true))) return rc;
+    const uint32_t known = ((uint32_t)1 << ctx->model.nterms) - 1u;    // (nterms <= MTG_MAX_TERMS < 31)
+    for (int k = 0; k < T; ++k)
+        if (term_mask[k] & ~(known | MTG_TERMS_MEAN))
+            return fail(ctx, MTG_E_ARG, "mtg_predict_terms: term_mask[%d] = 0x%x selects a term beyond the model's %d", k,
+                        term_mask[k], ctx->model.nterms);
+    bool ascending = true;
+    for (int64_t m = 0; m < M; ++m) {
+        if (!std::isfinite(ts[m])) return fail(ctx, MTG_E_ARG, "mtg_predict_terms: ts[%lld] is not finite", (long long)m);
+        if (m > 0 && ts[m] < ts[m - 1]) ascending = false;
+    }
+    // the times in ascending order along a wave, each result stored where its time was given (as mtg_predict_at)
+    std::vector<int64_t> order;
+    if (!ascending) {
+        order.resize((size_t)M);
+        for (int64_t m = 0; m < M; ++m) order[(size_t)m] = m;
+        std::sort(order.begin(), order.end(), [ts](int64_t i, int64_t j) { return ts[i] < ts[j] || (ts[i] == ts[j] && i < j); });
+    }
+    const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
+    const int64_t N = ctx->N;
+    if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_predict_terms: rank %d > %d", J, MTG_MAX_J);
+    // (a row's T M means and variances within the slab's budget)
+    const int64_t Bs = mtg_plan_predict_at_slab(N, J, M, B, (size_t)T * (size_t)M * 16);
+    if (Bs == 0) return fail(ctx, MTG_E_ARG, "mtg_predict_terms: M = %lld is too large", (long long)M);
+    const size_t out_bytes = (size_t)T * (size_t)M * 8;
+    MtgPredictTermsArgs qa;
+    DevBuf owner, masks, d_mu, d_var;
+    c.stage_inputs();
+    c.expand(qa, &owner);
+    PredictAtRoom room;
+    room.reserve(c, qa, Bs, J, M, ts, ascending ? nullptr : order.data(), var != nullptr);
+    c.reserve({{masks, (size_t)T * 4}, {d_mu, (size_t)Bs * out_bytes}, {d_var, var ? (size_t)Bs * out_bytes : 0}});
+    c.upload(masks.p, term_mask, (size_t)T * 4);
+    qa.T = T; qa.masks = masks.as<uint32_t>(); qa.owner = owner.as<int32_t>();
+    qa.mu = d_mu.as<double>(); qa.var = var ? d_var.as<double>() : nullptr;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_predict_terms_eval_kernel<%d>", J);
+    if (c.ok()) c.e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
+        qa.row0 = row0; qa.B = rows;
+        c.then([&] { return mtg_launch_predict_at_factor(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        c.then([&] { return mtg_launch_predict_terms_eval(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
+        c.gather(mu + row0 * T * M, d_mu.p, (size_t)rows * out_bytes);
+        if (var) c.gather(var + row0 * T * M, d_var.p, (size_t)rows * out_bytes);
         return c.e;
     });
     return c.finish(status);

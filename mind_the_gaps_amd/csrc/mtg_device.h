@@ -175,6 +175,18 @@ struct MtgPredictAtArgs : MtgRowArgs {
 };
 // both stages of the new-time prediction for one slab; 0 = rank outside 0 .. MTG_MAX_J
 int mtg_launch_predict_at(const MtgPredictAtArgs &, hipStream_t);
+// the first stage alone (factorisation, checkpoints, reversed sweep), for an evaluation stage of the caller's own
+int mtg_launch_predict_at_factor(const MtgPredictAtArgs &, hipStream_t);
+
+// Per-term conditional mean / variance at new times (mtg_predict_terms.hip): mtg_predict_at's workspace and first stage,
+// then an evaluation stage that restricts the generators at t* to the slots of each mask's terms
+struct MtgPredictTermsArgs : MtgPredictAtArgs {   // mu, var: [B][T][M] of this slab
+    int T;                      // masks, 1 .. 32
+    const uint32_t *masks;      // [T]: bit k = term k of the model, MTG_TERMS_MEAN = add the mean
+    const int32_t *owner;       // [nr_max + nc_max][cstride]: the term of every slot of every row (mtg_launch_prepare)
+};
+// the evaluation stage for one slab, after mtg_launch_predict_at_factor; 0 = rank outside 0 .. MTG_MAX_J
+int mtg_launch_predict_terms_eval(const MtgPredictTermsArgs &, hipStream_t);
 
 // The joint prior draw of the conditional draw (mtg_gp_cond_draw.hip) on the light curve's epochs merged with the
 // unique new times tu, and the last step of Matheron's rule.  The sweep leaves y - y~ in `data` for mtg_launch_predict_at
@@ -231,7 +243,7 @@ struct MtgGradArgs : MtgRowArgs {       // the whole batch in one launch: row0 =
 int mtg_launch_loglike_grad(const MtgGradArgs &, hipStream_t);
 static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivially_copyable<MtgPredictAtArgs>::value &&
               std::is_trivially_copyable<MtgGpDrawArgs>::value && std::is_trivially_copyable<MtgGradArgs>::value &&
-              std::is_trivially_copyable<MtgGpCondDrawArgs>::value,
+              std::is_trivially_copyable<MtgGpCondDrawArgs>::value && std::is_trivially_copyable<MtgPredictTermsArgs>::value,
               "passed by value as kernel arguments");
 
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
@@ -247,7 +259,8 @@ mtg_solve_launcher mtg_find_tp_wide_solver(int nr, int nc);
 // All nsig = (SHO terms + 1) structures (nr0 + 2k, nc0 - k) of a model in one launch: the launcher
 // takes list = base of the per-structure lists, count_ptr = base of the counts; lanes 64 or 256.
 mtg_solve_launcher mtg_find_tp_fused_solver(int nr0, int nc0, int nsig, int lanes);
-void mtg_launch_prepare(const MtgPrepArgs &, hipStream_t);
+// owner: NULL, or [nr_max + nc_max][cstride] int32 receiving the term of every slot of every accepted row (mtg_prepare.h)
+void mtg_launch_prepare(const MtgPrepArgs &, hipStream_t, int32_t *owner = nullptr);
 // mtg_sort.hip: evaluation indices sorted (stable) by key = structure * L + light curve, rejected rows last
 int mtg_sort_key_bits(int64_t L, int nsig);
 size_t mtg_sort_temp_bytes(int64_t B, int bits);

@@ -97,6 +97,45 @@ __device__ __forceinline__ void pat_pivot(const double *S, const double *U, cons
     }
 }
 
+// ---- the backward recurrences of the new-time prediction (mtg_predict_at.hip, mtg_predict_terms.hip) ----
+// g <- phn o (g + Un xn): g_n from g_{n+1} and sample n + 1
+template <int J>
+__device__ __forceinline__ void pat_bwd_g(double *g, const double *phn, const double *Un, double xn)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < J; ++i) g[i] = phn[i] * (g[i] + Un[i] * xn);
+}
+
+// G <- U U^T / D + (I - U W^T) X (I - W U^T),  X = phn phn^T o G: G_n from G_{n+1} and sample n
+// (forming A = I - U W^T explicitly and the product A X with it was tried: J^3 instead of J^2, and no more accurate --
+// 0.78 of the bound on `signatures` against 0.013)
+template <int J>
+__device__ __forceinline__ void pat_bwd_G(double *G, const double *phn, const double *U, const double *W, double D)
+{
+#pragma clang fp contract(off)
+    double XW[J], wxw = 0.0;
+#pragma unroll
+    for (int i = 0; i < J; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) G[pat_sy(i, j)] = phn[i] * phn[j] * G[pat_sy(i, j)];
+#pragma unroll
+    for (int i = 0; i < J; ++i) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < J; ++j) s += G[pat_sy(i, j)] * W[j];
+        XW[i] = s;
+    }
+#pragma unroll
+    for (int i = 0; i < J; ++i) wxw += W[i] * XW[i];
+    const double h = wxw + 1.0 / D;
+#pragma unroll
+    for (int i = 0; i < J; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j)
+            G[pat_sy(i, j)] = G[pat_sy(i, j)] - U[i] * XW[j] - XW[i] * U[j] + U[i] * U[j] * h;
+}
+
 // F<J>::launch(args...) for the rank J in 1 .. MTG_MAX_J; 0 = no such rank (rank 0, the white model, is the caller's)
 template <template <int> class F, class... A>
 int pat_dispatch_rank(int J, const A &...args)

@@ -73,10 +73,18 @@ __global__ void __launch_bounds__(256) mtg_prepare_kernel(MtgPrepArgs a)
     mtg_prepare_one(a, e, e < a.B);
 }
 
-void mtg_launch_prepare(const MtgPrepArgs &a, hipStream_t stream)
+// the same expansion, which also names the term every slot belongs to (mtg_prepare.h; mtg_predict_terms)
+__global__ void __launch_bounds__(256) mtg_prepare_owner_kernel(MtgPrepArgs a, int32_t *owner)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    mtg_prepare_one<true>(a, e, e < a.B, nullptr, owner);
+}
+
+void mtg_launch_prepare(const MtgPrepArgs &a, hipStream_t stream, int32_t *owner)
 {
     const int64_t blocks = (a.B + 255) / 256;
-    hipLaunchKernelGGL(mtg_prepare_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+    if (owner) hipLaunchKernelGGL(mtg_prepare_owner_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, owner);
+    else hipLaunchKernelGGL(mtg_prepare_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
 }
 
 

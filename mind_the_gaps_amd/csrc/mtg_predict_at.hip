@@ -36,44 +36,6 @@
 #include "mtg_math.h"
 #include "mtg_device.h"
 #include "mtg_factor_step.h"
-// g <- phn o (g + Un xn): g_n from g_{n+1} and sample n + 1
-template <int J>
-__device__ __forceinline__ void pat_bwd_g(double *g, const double *phn, const double *Un, double xn)
-{
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < J; ++i) g[i] = phn[i] * (g[i] + Un[i] * xn);
-}
-
-// G <- U U^T / D + (I - U W^T) X (I - W U^T),  X = phn phn^T o G: G_n from G_{n+1} and sample n
-// (forming A = I - U W^T explicitly and the product A X with it was tried: J^3 instead of J^2, and no more accurate --
-// 0.78 of the bound on `signatures` against 0.013)
-template <int J>
-__device__ __forceinline__ void pat_bwd_G(double *G, const double *phn, const double *U, const double *W, double D)
-{
-#pragma clang fp contract(off)
-    double XW[J], wxw = 0.0;
-#pragma unroll
-    for (int i = 0; i < J; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) G[pat_sy(i, j)] = phn[i] * phn[j] * G[pat_sy(i, j)];
-#pragma unroll
-    for (int i = 0; i < J; ++i) {
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) s += G[pat_sy(i, j)] * W[j];
-        XW[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < J; ++i) wxw += W[i] * XW[i];
-    const double h = wxw + 1.0 / D;
-#pragma unroll
-    for (int i = 0; i < J; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j)
-            G[pat_sy(i, j)] = G[pat_sy(i, j)] - U[i] * XW[j] - XW[i] * U[j] + U[i] * U[j] * h;
-}
-
 // DATA: row r of a.data stands in for the light curve's y (the conditional draw conditions on y - y~, mtg_gp_cond_draw.hip)
 template <int J, bool DATA>
 __global__ void __launch_bounds__(64) mtg_predict_at_factor_kernel(MtgPredictAtArgs a)
@@ -382,15 +344,32 @@ __global__ void __launch_bounds__(64) mtg_predict_at_white_eval_kernel(MtgPredic
 }
 
 template <int J>
-struct PatLaunch {
+struct PatFactorLaunch {
     static void launch(const MtgPredictAtArgs &a, hipStream_t s)
     {
         const dim3 rows((unsigned)((a.B + 63) / 64));
         if (a.data) hipLaunchKernelGGL((mtg_predict_at_factor_kernel<J, true>), rows, dim3(64), 0, s, a);
         else hipLaunchKernelGGL((mtg_predict_at_factor_kernel<J, false>), rows, dim3(64), 0, s, a);
+    }
+};
+
+template <int J>
+struct PatLaunch {
+    static void launch(const MtgPredictAtArgs &a, hipStream_t s)
+    {
+        PatFactorLaunch<J>::launch(a, s);
         hipLaunchKernelGGL(mtg_predict_at_eval_kernel<J>, dim3((unsigned)(a.B * ((a.M + 63) / 64))), dim3(64), 0, s, a);
     }
 };
+
+// the first stage alone, for mtg_predict_terms.hip's evaluation: the same kernels as below
+int mtg_launch_predict_at_factor(const MtgPredictAtArgs &a, hipStream_t s)
+{
+    const int J = a.nr0 + 2 * a.nc0;
+    if (J != 0) return pat_dispatch_rank<PatFactorLaunch>(J, a, s);
+    hipLaunchKernelGGL(mtg_predict_at_white_factor_kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, s, a);
+    return 1;
+}
 
 // both stages for rows [row0, row0 + B) of the batch; J = nr0 + 2 nc0 in 0 .. MTG_MAX_J (returns 0 otherwise)
 int mtg_launch_predict_at(const MtgPredictAtArgs &a, hipStream_t s)

@@ -10,6 +10,13 @@
 
 #include <math.h>
 
+// the term a slot belongs to, where the caller asked for the map (mtg_prepare_from's OWNER)
+template <bool OWNER>
+__device__ __forceinline__ void mtg_own(int32_t *owner, int64_t at, int term)
+{
+    if constexpr (OWNER) owner[at] = term;
+}
+
 // th_row: where this evaluation's theta row is to be READ from when it is not a.theta + e * P -- the sampler's
 // speculative kernel keeps the proposals it has just made in LDS as well (a global round trip per parameter, one after
 // the other through the term loop: 1.0-1.2 us of the 6-9 us the expansion takes in that kernel; the rest is the
@@ -17,7 +24,12 @@
 // (Not kept: the model's description read from a copy in LDS instead of the kernel arguments -- the expansion took as
 // long, and copying the description out of the argument segment with per-thread indices cost 27 us.)
 // th: the row's free parameters (valid for a dead thread too)
-__device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e, bool live, const double *th)
+// OWNER (mtg_predict_terms alone): the term every slot handed out below belongs to is written to `owner`, one int32 per
+// (slot, row) -- real slot j in row j, complex pair k in row nr_max + k, each of stride a.cstride -- by the very
+// statements that hand the slots out; everybody else compiles without it
+template <bool OWNER = false>
+__device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e, bool live, const double *th,
+                                                 int32_t *owner = nullptr)
 {
     const MtgModel &m = a.model;
     auto par = [th, &m](int k) -> double {   // (th by value: a reference would take the address of a local, which the back end mishandles when it survives inlining)
@@ -59,20 +71,20 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
             switch (m.kinds[i]) {
             case MTG_TERM_REAL: {
                 const double av = exp(par(o));
-                c[lay.ar(ir) * cs] = av; c[lay.cr(ir) * cs] = exp(par(o + 1)); ++ir; asum += av;
+                c[lay.ar(ir) * cs] = av; c[lay.cr(ir) * cs] = exp(par(o + 1)); mtg_own<OWNER>(owner, (int64_t)ir * cs + e, i); ++ir; asum += av;
                 break;
             }
             case MTG_TERM_COMPLEX3: {
                 const double av = exp(par(o));
                 c[lay.ac(ic) * cs] = av; c[lay.bc(ic) * cs] = 0.0;
-                c[lay.cc(ic) * cs] = exp(par(o + 1)); c[lay.dc(ic) * cs] = exp(par(o + 2)); ++ic;
+                c[lay.cc(ic) * cs] = exp(par(o + 1)); c[lay.dc(ic) * cs] = exp(par(o + 2)); mtg_own<OWNER>(owner, (int64_t)(m.nr_max + ic) * cs + e, i); ++ic;
                 asum += av;
                 break;
             }
             case MTG_TERM_COMPLEX4: {
                 const double av = exp(par(o));
                 c[lay.ac(ic) * cs] = av; c[lay.bc(ic) * cs] = exp(par(o + 1));
-                c[lay.cc(ic) * cs] = exp(par(o + 2)); c[lay.dc(ic) * cs] = exp(par(o + 3)); ++ic;
+                c[lay.cc(ic) * cs] = exp(par(o + 2)); c[lay.dc(ic) * cs] = exp(par(o + 3)); mtg_own<OWNER>(owner, (int64_t)(m.nr_max + ic) * cs + e, i); ++ic;
                 asum += av;
                 break;
             }
@@ -82,15 +94,15 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
                     const double f = sqrt(1.0 - 4.0 * Q * Q);
                     const double a1 = 0.5 * S0 * w0 * Q * (1.0 + 1.0 / f);
                     const double a2 = 0.5 * S0 * w0 * Q * (1.0 - 1.0 / f);
-                    c[lay.ar(ir) * cs] = a1; c[lay.cr(ir) * cs] = 0.5 * w0 / Q * (1.0 - f); ++ir;
-                    c[lay.ar(ir) * cs] = a2; c[lay.cr(ir) * cs] = 0.5 * w0 / Q * (1.0 + f); ++ir;
+                    c[lay.ar(ir) * cs] = a1; c[lay.cr(ir) * cs] = 0.5 * w0 / Q * (1.0 - f); mtg_own<OWNER>(owner, (int64_t)ir * cs + e, i); ++ir;
+                    c[lay.ar(ir) * cs] = a2; c[lay.cr(ir) * cs] = 0.5 * w0 / Q * (1.0 + f); mtg_own<OWNER>(owner, (int64_t)ir * cs + e, i); ++ir;
                     asum += a1; asum += a2;
                     ++nover;
                 } else {
                     const double f = sqrt(4.0 * Q * Q - 1.0);
                     const double av = S0 * w0 * Q;
                     c[lay.ac(ic) * cs] = av; c[lay.bc(ic) * cs] = av / f;
-                    c[lay.cc(ic) * cs] = 0.5 * w0 / Q; c[lay.dc(ic) * cs] = 0.5 * w0 / Q * f; ++ic;
+                    c[lay.cc(ic) * cs] = 0.5 * w0 / Q; c[lay.dc(ic) * cs] = 0.5 * w0 / Q * f; mtg_own<OWNER>(owner, (int64_t)(m.nr_max + ic) * cs + e, i); ++ic;
                     asum += av;
                 }
                 break;
@@ -101,7 +113,7 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
                 const double S0 = exp(2.0 * par(o)) / w0;
                 const double av = w0 * S0;
                 c[lay.ac(ic) * cs] = av; c[lay.bc(ic) * cs] = w0 * w0 * S0 / eps;
-                c[lay.cc(ic) * cs] = w0; c[lay.dc(ic) * cs] = eps; ++ic;
+                c[lay.cc(ic) * cs] = w0; c[lay.dc(ic) * cs] = eps; mtg_own<OWNER>(owner, (int64_t)(m.nr_max + ic) * cs + e, i); ++ic;
                 asum += av;
                 break;
             }
@@ -112,7 +124,7 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
             }
             case MTG_TERM_DRW: {  // celerite_models.py:58-66, Q = 1/2
                 const double av = exp(par(o));
-                c[lay.ar(ir) * cs] = av; c[lay.cr(ir) * cs] = 0.5 * exp(par(o + 1)) / 0.5; ++ir;
+                c[lay.ar(ir) * cs] = av; c[lay.cr(ir) * cs] = 0.5 * exp(par(o + 1)) / 0.5; mtg_own<OWNER>(owner, (int64_t)ir * cs + e, i); ++ir;
                 asum += av;
                 break;
             }
@@ -123,14 +135,14 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
                 const double av = exp(par(o));
                 const double w0 = exp(par(o + 2));
                 c[lay.ac(ic) * cs] = av; c[lay.bc(ic) * cs] = 0.0;
-                c[lay.cc(ic) * cs] = 0.5 * w0 / exp(par(o + 1)); c[lay.dc(ic) * cs] = w0; ++ic;
+                c[lay.cc(ic) * cs] = 0.5 * w0 / exp(par(o + 1)); c[lay.dc(ic) * cs] = w0; mtg_own<OWNER>(owner, (int64_t)(m.nr_max + ic) * cs + e, i); ++ic;
                 asum += av;
                 break;
             }
             case MTG_TERM_COSINUS: {  // celerite_models.py:39-52
                 const double av = exp(par(o));
                 c[lay.ac(ic) * cs] = av; c[lay.bc(ic) * cs] = 0.0;
-                c[lay.cc(ic) * cs] = 0.0; c[lay.dc(ic) * cs] = exp(par(o + 1)); ++ic;
+                c[lay.cc(ic) * cs] = 0.0; c[lay.dc(ic) * cs] = exp(par(o + 1)); mtg_own<OWNER>(owner, (int64_t)(m.nr_max + ic) * cs + e, i); ++ic;
                 asum += av;
                 break;
             }
@@ -138,7 +150,7 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
                 const double av = exp(par(o));
                 const double w0 = exp(par(o + 2));
                 c[lay.ac(ic) * cs] = av; c[lay.bc(ic) * cs] = exp(par(o + 1));
-                c[lay.cc(ic) * cs] = w0; c[lay.dc(ic) * cs] = w0; ++ic;
+                c[lay.cc(ic) * cs] = w0; c[lay.dc(ic) * cs] = w0; mtg_own<OWNER>(owner, (int64_t)(m.nr_max + ic) * cs + e, i); ++ic;
                 asum += av;
                 break;
             }
@@ -184,7 +196,9 @@ __device__ __forceinline__ void mtg_prepare_from(const MtgPrepArgs &a, int64_t e
 }
 
 // row e of the batch a.theta, or the copy of it the caller holds (th_row)
-__device__ __forceinline__ void mtg_prepare_one(const MtgPrepArgs &a, int64_t e, bool live, const double *th_row = nullptr)
+template <bool OWNER = false>
+__device__ __forceinline__ void mtg_prepare_one(const MtgPrepArgs &a, int64_t e, bool live, const double *th_row = nullptr,
+                                                int32_t *owner = nullptr)
 {
-    mtg_prepare_from(a, e, live, th_row ? th_row : a.theta + (live ? e : 0) * a.model.P);
+    mtg_prepare_from<OWNER>(a, e, live, th_row ? th_row : a.theta + (live ? e : 0) * a.model.P, owner);
 }

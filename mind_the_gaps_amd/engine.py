@@ -40,7 +40,10 @@ EXPORTS = (
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
+    "mtg_predict_terms",
 )
+
+TERMS_MEAN = 1 << 31   # include/mtg.h, MTG_TERMS_MEAN: a mask of predict_terms with this bit adds the mean
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -318,6 +321,8 @@ def load_library():
     lib.mtg_predict.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, _ip]
     lib.mtg_predict_at.restype = c_int
     lib.mtg_predict_at.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, _dp, _dp, _ip]
+    lib.mtg_predict_terms.restype = c_int
+    lib.mtg_predict_terms.argtypes = [c_vp, c_i64, _dp, _ip, c_int, ctypes.POINTER(ctypes.c_uint32), c_i64, _dp, _dp, _dp, _ip]
     lib.mtg_gp_draw.restype = c_int
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_gp_cond_draw.restype = c_int
@@ -770,6 +775,25 @@ class Engine:
                                              _iptr(status)))
         return mu, var, status
 
+    def predict_terms(self, theta, masks, ts, lc_index=None, return_var=True):
+        """Conditional mean / variance of COMPONENTS of the sum kernel given the data, at times ``ts`` [M] (any order)
+        -> (mu[B][T][M], var[B][T][M] or None, status[B]).  ``masks`` [T], 1 <= T <= 32: bit k of a mask selects term k
+        of the model (``set_model``'s order), ``TERMS_MEAN`` adds the constant or linear mean (never the y_offset).
+        K stays the covariance of the whole model; the factorisation and the replay are ``predict_at``'s, done once for
+        all T components (mtg_predict_terms)."""
+        theta = np.atleast_2d(_f64(theta))
+        ts = _f64(np.atleast_1d(ts)).ravel()
+        masks = np.ascontiguousarray(np.atleast_1d(masks), dtype=np.uint32).ravel()
+        B, M, T = theta.shape[0], len(ts), len(masks)
+        lc = None if lc_index is None else np.ascontiguousarray(lc_index, dtype=np.int32)
+        mu = np.full((B, T, M), np.nan)
+        var = np.full((B, T, M), np.nan) if return_var else None
+        status = np.empty(B, dtype=np.int32)
+        self._check(self._lib.mtg_predict_terms(self._ctx, B, _ptr(theta), _iptr(lc), T,
+                                                masks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), M, _ptr(ts),
+                                                _ptr(mu), _ptr(var), _iptr(status)))
+        return mu, var, status
+
     def gp_draw(self, theta, lc_index=None, seed=0, normals=None):
         """Realisations of the GP itself, y[b] ~ N(mean, K(theta[b])) on the sampling and error bars of light curve
         ``lc_index[b]`` -> (y[B][N], status[B]); y excludes the per-light-curve y_offset.  ``normals`` [B][N]: the
@@ -972,6 +996,6 @@ class Engine:
 
 for _name in ("set_lightcurves", "set_lightcurves_device", "set_model", "loglike", "loglike_device", "loglike_coeffs",
               "ensemble_init", "ensemble_run", "ensemble_restore", "ensemble_state", "chain_autocorr", "simulate_tk95",
-              "tk95_observe_series", "predict", "predict_at", "gp_draw", "gp_cond_draw", "loglike_grad", "apply_inverse", "math_probe"):
+              "tk95_observe_series", "predict", "predict_at", "predict_terms", "gp_draw", "gp_cond_draw", "loglike_grad", "apply_inverse", "math_probe"):
     setattr(Engine, _name, _one_thread_at_a_time(getattr(Engine, _name)))
 del _name

@@ -455,8 +455,32 @@ class GP(ModelSet):
         out += mean_at(xs)
         return out[0] if size is None else out
 
-    def predict(self, y, t=None, return_cov=True, return_var=False):
+    def _term_mask(self, kernel):
+        """``kernel`` -- one top-level term of this GP's sum, or a sum of several -- as the bit mask of
+        ``Engine.predict_terms``; the terms are matched by identity"""
+        mine = self.kernel.terms
+        parts = kernel.terms if isinstance(kernel, Term) else None
+        mask = 0
+        for part in parts or ():
+            where = [k for k, term in enumerate(mine) if term is part]
+            if not where:
+                parts = None
+                break
+            mask |= 1 << where[0]
+        if not parts:
+            raise ValueError("kernel= must be one of the terms of this GP's kernel (gp.kernel.terms[k]) or a sum of them")
+        return mask
+
+    def predict(self, y, t=None, return_cov=True, return_var=False, kernel=None):
         """Conditional mean and (co)variance, celerite.GP.predict.
+
+        ``kernel``: None, or a component of this GP's kernel -- ``gp.kernel.terms[k]`` or a sum of such terms, matched
+        by identity; anything else (a term inside a product, a foreign object) raises ``ValueError``.  Then the mean and
+        the variance are those of that component given the data, ``mean + k_c,* K^-1 r`` and
+        ``k_c(0) - k_c,*^T K^-1 k_c,*`` with K the covariance of the whole kernel (celerite adds the mean here too), at
+        ``t`` or at the computed times, from one device call that shares the factorisation and the replay of
+        ``Engine.predict_at`` (``Engine.predict_terms``).  With ``return_cov=True`` the dense covariance of the
+        component is assembled on the host over ``apply_inverse``, as the new-time covariance below is.
 
         At the training times (``t=None``) with ``return_var=True`` -- the reference's call,
         gpmodelling.py:366 -- mean and variance both come from the O(N J^2) factorisation on the
@@ -469,7 +493,15 @@ class GP(ModelSet):
         right-hand sides).  Like celerite's, the variances are those of the noise-free process (no
         jitter, no measurement errors).  Under a profile mean (sine, two sines, Gaussian) the device sees the residual
         ``y - mean(t)`` with a zero mean and ``mean.get_value`` is added back here."""
+        mask = None if kernel is None else self._term_mask(kernel)
         eng, model, mean_at = self._mean_engine(y)
+        if mask is not None and (return_var or not return_cov):
+            xs = self._t if t is None else np.atleast_1d(np.asarray(t, dtype=np.float64))
+            mu, var, status = eng.predict_terms(model.full[model.free_index][None, :], [mask | _engine.TERMS_MEAN], xs,
+                                                return_var=return_var)
+            self._raise_for(status[0])
+            mu = mu[0, 0] + mean_at(xs)
+            return (mu, var[0, 0]) if return_var else mu
         if t is None and (return_var or not return_cov):
             mu, var, status = eng.predict(model.full[model.free_index][None, :])
             self._raise_for(status[0])
@@ -484,8 +516,9 @@ class GP(ModelSet):
         y = np.asarray(y, dtype=np.float64)
         xs = self._t if t is None else np.atleast_1d(np.asarray(t, dtype=np.float64))
         resid = y - self.mean.get_value(self._t)
-        kxs = self.kernel.get_value(xs[:, None] - self._t[None, :])                # [N_*][N]
+        part = self.kernel if kernel is None else kernel
+        kxs = part.get_value(xs[:, None] - self._t[None, :])                       # [N_*][N]
         sol, status = eng.apply_inverse(model.full[model.free_index], np.column_stack([resid, kxs.T]))
         self._raise_for(status)
         mu = self.mean.get_value(xs) + kxs @ sol[:, 0]
-        return mu, self.kernel.get_value(xs[:, None] - xs[None, :]) - kxs @ sol[:, 1:]
+        return mu, part.get_value(xs[:, None] - xs[None, :]) - kxs @ sol[:, 1:]

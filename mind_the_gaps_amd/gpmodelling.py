@@ -399,6 +399,33 @@ class GPModelling:
                 self.gp.set_parameter_vector(saved)
         return (mu[0], var[0]) if parameters.ndim == 1 else (mu, var)
 
+    def predict_components(self, t=None, parameters=None):
+        """The fitted curve taken apart: ``{term name: (mu, var)}`` with one entry per term of the kernel, the
+        conditional mean and variance of that term alone given the light curve (``GP.predict(kernel=term)``; the mean
+        model is added to every ``mu``), at times ``t`` (None: the observed epochs).  The names are the parameter
+        prefixes of the sum, ``terms[k]``, or ``kernel`` for a kernel of one term.  ``parameters``: None -- the
+        maximum-posterior sample if posteriors were derived, else the GP's current vector -- or one vector [P].  All
+        terms come from one device call sharing one factorisation (``Engine.predict_terms``), except under a profile
+        mean, where ``GP.predict`` is called per term."""
+        if parameters is None:
+            parameters = self.max_parameters if self._mcmc_samples is not None else self.gp.get_parameter_vector()
+        times = self._lightcurve.times if t is None else np.atleast_1d(np.asarray(t, dtype=np.float64))
+        parts = self.gp.kernel.terms
+        names = ["terms[%d]" % k for k in range(len(parts))] if len(parts) > 1 else ["kernel"]
+        saved = self.gp.get_parameter_vector()
+        try:
+            self.gp.set_parameter_vector(np.asarray(parameters, dtype=np.float64))
+            if self.gp._has_profile_mean():
+                return {name: self.gp.predict(self._lightcurve.y, t=times, return_var=True, return_cov=False, kernel=part)
+                        for name, part in zip(names, parts)}
+            eng, model = self.gp._bound_engine(self._lightcurve.y)
+            masks = [(1 << k) | _engine.TERMS_MEAN for k in range(len(parts))]
+            mu, var, status = eng.predict_terms(model.full[model.free_index][None, :], masks, times)
+            self.gp._raise_for(status[0])
+            return {name: (mu[0, k] + (model.y_offset or 0.0), var[0, k]) for k, name in enumerate(names)}
+        finally:
+            self.gp.set_parameter_vector(saved)
+
     def sample_conditional(self, times=None, nsims: int = 1, parameters=None, seed=None):
         """``nsims`` light curves drawn from the process given the data, at ``times`` [M] (None: the observed epochs) ->
         [nsims][M]: what fills a gap with realisations consistent with both the data and the fitted kernel
