@@ -2,7 +2,7 @@
  *
  *   gcc -std=c99 -O2 -I include examples/c_api_demo.c -o examples/c_api_demo \
  *       -L mind_the_gaps_amd -lmtg_hip -Wl,-rpath,$PWD/mind_the_gaps_amd -lm
- *   ./examples/c_api_demo            -> one line per evaluation: "lnL status"
+ *   ./examples/c_api_demo            -> one line per evaluation: "lnL status" (and the Lomb-Scargle peak on stderr)
  *
  * A damped random walk + SHO (the tutorials' null model) on a small irregular light curve with a
  * deterministic pattern, so that tests/test_capi_example_gpu.py can rebuild the same inputs and
@@ -48,6 +48,16 @@ int main(void)
     if (mtg_set_model(ctx, 2, kinds, NULL, MTG_MEAN_CONSTANT, 6, full, 5, free_index, bounds) != MTG_OK) goto fail;
     if (mtg_loglike_batch(ctx, B, &theta[0][0], NULL, 1, out, status) != MTG_OK) goto fail;
     for (b = 0; b < B; ++b) printf("%.17g %d\n", out[b], (int)status[b]);
+    /* the highest Lomb-Scargle peak of the same light curve (the 0.9 rad sinusoid: 0.143 cycles per unit of time), reduced
+     * on the device; on stderr, so that stdout stays one line per evaluation */
+    {
+        double freqs[64], peak;
+        int64_t at;
+        int k;
+        for (k = 0; k < 64; ++k) freqs[k] = 0.01 + 0.005 * k;
+        if (mtg_lomb_scargle(ctx, 64, freqs, MTG_LS_STANDARD, 1, NULL, &peak, &at) != MTG_OK) goto fail;
+        fprintf(stderr, "Lomb-Scargle peak %.4f at %.3f cycles per unit of time\n", peak, at >= 0 ? freqs[at] : 0.0);
+    }
     rc = 0;
 fail:
     if (rc) fprintf(stderr, "mtg: %s\n", mtg_last_error(ctx));

@@ -631,6 +631,52 @@ MTG_API int mtg_loglike_grad(mtg_ctx *ctx, int64_t B, const double *theta, const
                              double *out /* [B] */, double *grad /* [B][P] */, int32_t *status);
 
 /*
+ * astropy's LombScargle(t, y, dy, fit_mean=True, center_data=True, nterms=1, normalization=...).power(freqs): the
+ * generalised (floating-mean) Lomb-Scargle periodogram of EVERY resident light curve l at every freqs[k] (host, cycles
+ * per unit of time) -- the set of mtg_set_lightcurves or the simulated one mtg_simulate_tk95(make_resident) left.  A
+ * model need not be set.
+ *   weighted != 0: w_n = sigma_n^-2 / sum sigma^-2 from the resident error bars; weighted == 0: w_n = 1 / N (dy = None).
+ *   ybar = sum w y, r = y - ybar, YY = sum w r^2, and with c_n, s_n = cos, sin(2 pi f (t_n - t_0))
+ *     C = sum w c,  S = sum w s,  YC = sum w r c,  YS = sum w r s,
+ *     CC = sum w c^2 - C^2,  SS = sum w s^2 - S^2,  CS = sum w c s - C S,
+ *     p = (SS YC^2 + CC YS^2 - 2 CS YC YS) / (CC SS - CS^2)
+ * the tau-free form of Zechmeister & Kuerster (2009), algebraically astropy's YC_tau^2 / CC_tau + YS_tau^2 / SS_tau and
+ * invariant under a shift of the times and of y: the elapsed time t - t_0 is used, and the y_offset of the resident set
+ * does not matter.  normalization:
+ */
+#define MTG_LS_STANDARD 0   /* p / YY, in [0, 1]                                  */
+#define MTG_LS_MODEL    1   /* p / (YY - p)                                       */
+#define MTG_LS_LOG      2   /* -log(1 - p / YY)                                   */
+#define MTG_LS_PSD      3   /* p * 0.5 * sum(1 / sigma_n^2)  (unweighted: 0.5 N)  */
+/*
+ * The phase is formed in cycles: f (t_n - t_0) is taken exactly (product and fma remainder), its integer part is
+ * dropped before anything is rounded, and the fraction goes through the (cos, sin) table of the sweep; what is left is
+ * the rounding of t_n - t_0 itself (exact for times within a factor of two of each other).  Against a 50-digit
+ * evaluation of astropy's form the standard power is within max(10 rho, 64 sqrt(N) u), u = 2^-53, rho the error of the
+ * same formula in plain float64 (tests/test_lomb_scargle_gpu.py), also with f T ~ 1e6 cycles.
+ * One lane owns a frequency; the samples are walked in ascending order, in chunks of 256 whose partial sums are added
+ * to a running total; on shared sampling a lane carries a tile of light curves, so that one (cos, sin) pair serves the
+ * whole tile.  power[l][k] depends on (light curve l, freqs[k], normalization, weighted) alone, bit for bit: not on L,
+ * on which light curves share the tile, on F, on the order of freqs, or on whether the sampling is stored shared or per
+ * light curve.
+ *   power       [L][F] (host) or NULL
+ *   peak_power  [L] or NULL: the maximum of row l;  peak_index [L] or NULL: the first k that attains it.  Both are
+ *               reduced on the device: with power == NULL nothing of size L F comes back, and the device workspace is
+ *               bounded -- the light curves are processed in slabs.
+ * A frequency at which CC SS - CS^2 is not positive gives NaN in that entry; the peak passes NaN entries over (a row of
+ * nothing else: NaN and -1).
+ * MTG_E_STATE without light curves; MTG_E_ARG for F < 1, a frequency that is not finite or <= 0, an unknown
+ * normalization, N < 4 (three points are fitted exactly: the denominator is 0), and all three outputs NULL.  Runs on
+ * the context's stream, ordered with its other calls; the resident set is only read.  mtg_last_solver names
+ * "mtg_lomb_scargle_kernel<R>" (R light curves per lane), mtg_last_kernel_ms runs from the pre-pass to the last slab's
+ * powers and peaks (with one slab: kernels only; the copies of earlier slabs lie inside it).
+ */
+MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host, cycles per unit time */,
+                             int normalization, int weighted,
+                             double *power /* [L][F] host, or NULL */,
+                             double *peak_power /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
+
+/*
  * Accuracy probe of the device elementary functions the recurrence uses
  * (tests only): exp_neg[i] = exp(-x[i]), sin/cos(x[i]), rcp_x[i] = 1 / x[i] for
  * n host values x >= 0.

@@ -2497,6 +2497,58 @@ MTG_API int mtg_predict_terms(mtg_ctx *ctx, int64_t B, const double *theta, cons
     return c.finish(status);
 }
 
+MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, double *power,
+                             double *peak_power, int64_t *peak_index)
+{
+    RowCall c{ctx, "mtg_lomb_scargle", 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    int rc = c.ready(false);
+    if (rc) return rc;
+    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: need F >= 1 frequencies");
+    if (!power && !peak_power && !peak_index) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: power, peak_power and peak_index are all NULL");
+    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
+        return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: unknown normalization %d", normalization);
+    const int64_t N = ctx->N, L = ctx->L;
+    if (N < 4) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: N = %lld < 4 samples (a sinusoid with a floating mean fits three exactly)", (long long)N);
+    for (int64_t k = 0; k < F; ++k)
+        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
+            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: freqs[%lld] = %g is not a finite positive frequency", (long long)k, freqs[k]);
+    if ((rc = c.begin(false))) return rc;
+    // the powers of a slab of light curves at a time: <= 256 MiB of workspace whatever L F is
+    int64_t Ls = ((int64_t)1 << 25) / F;
+    const int R = mtg_lomb_scargle_tile(L, !ctx->t_per_lc, weighted);
+    Ls = Ls / R * R;   // whole tiles (a light curve's power does not depend on its tile: this only fills the lanes)
+    if (Ls < R) Ls = R;
+    if (Ls > L) Ls = L;
+    MtgLombScargleArgs qa;
+    DevBuf d_freqs, d_stats, d_power, d_peak, d_index;
+    const bool want_peak = peak_power || peak_index;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_power, (size_t)Ls * (size_t)F * 8},
+               {d_peak, want_peak ? (size_t)L * 8 : 0}, {d_index, want_peak ? (size_t)L * 8 : 0}});
+    c.upload(d_freqs.p, freqs, (size_t)F * 8);
+    qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
+    qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.L = L;
+    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization;
+    qa.stats = d_stats.as<double>(); qa.F = F; qa.freqs = d_freqs.as<double>(); qa.power = d_power.as<double>();
+    qa.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_lomb_scargle_kernel<%d>", R);
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        mtg_launch_lomb_scargle_stats(qa, c.s);
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
+        c.then([&] { return mtg_launch_lomb_scargle(qa, l0, rows, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        if (l0 + rows == L) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });   // mtg_last_kernel_ms: up to the last slab's kernels
+        // (the copy is ordered on the stream: the next slab's kernel overwrites the buffer only after it)
+        if (power) c.gather(power + l0 * F, d_power.p, (size_t)rows * (size_t)F * 8);
+        return c.e;
+    });
+    if (c.ok()) ctx->timed = true;
+    if (peak_power) c.gather(peak_power, d_peak.p, (size_t)L * 8);
+    if (peak_index) c.gather(peak_index, d_index.p, (size_t)L * 8);
+    return c.finish(nullptr);
+}
+
 MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, uint64_t seed,
                         const double *normals, double *y, int32_t *status)
 {

@@ -246,6 +246,32 @@ static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivi
               std::is_trivially_copyable<MtgGpCondDrawArgs>::value && std::is_trivially_copyable<MtgPredictTermsArgs>::value,
               "passed by value as kernel arguments");
 
+// light curves whose sums one lane of the Lomb-Scargle kernel carries on shared sampling (mtg_lomb_scargle.hip): with the
+// chunk's partial sums 2 x 6 R doubles per lane when every light curve has weights of its own, 2 x (2 R + 4) otherwise
+#ifndef MTG_LS_R_WEIGHTED
+#define MTG_LS_R_WEIGHTED 8
+#endif
+#ifndef MTG_LS_R_UNWEIGHTED
+#define MTG_LS_R_UNWEIGHTED 16
+#endif
+struct MtgLombScargleArgs {
+    const double2 *dxt, *yv;
+    int64_t N, t_stride, L;   // the resident set: t_stride 0 (shared sampling) or N
+    int weighted, normalization;
+    double *stats;            // [L][4]: ybar, YY, sum sigma^-2 (or N), 0
+    int64_t F;
+    const double *freqs;      // [F] on the device
+    double *power;            // [slab][F]: the slab being worked on
+    double *peak_power;       // [L] or NULL
+    int64_t *peak_index;      // [L] or NULL
+};
+// the pre-pass over all L light curves; then one slab [l0, l0 + Ls) of powers and, where asked for, its peaks
+// (0 = more workgroups than a grid holds)
+void mtg_launch_lomb_scargle_stats(const MtgLombScargleArgs &, hipStream_t);
+int mtg_launch_lomb_scargle(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, hipStream_t);
+// light curves per lane for a set of L (1, 4, or the full tile of the weighting)
+int mtg_lomb_scargle_tile(int64_t L, int shared_sampling, int weighted);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

@@ -40,10 +40,13 @@ EXPORTS = (
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
-    "mtg_predict_terms",
+    "mtg_predict_terms", "mtg_lomb_scargle",
 )
 
 TERMS_MEAN = 1 << 31   # include/mtg.h, MTG_TERMS_MEAN: a mask of predict_terms with this bit adds the mean
+# include/mtg.h, MTG_LS_*: the normalisations of lomb_scargle, by astropy's names
+LS_STANDARD, LS_MODEL, LS_LOG, LS_PSD = range(4)
+LS_NORMALIZATIONS = {"standard": LS_STANDARD, "model": LS_MODEL, "log": LS_LOG, "psd": LS_PSD}
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -324,6 +327,8 @@ def load_library():
     lib.mtg_predict_terms.restype = c_int
     lib.mtg_predict_terms.argtypes = [c_vp, c_i64, _dp, _ip, c_int, ctypes.POINTER(ctypes.c_uint32), c_i64, _dp, _dp, _dp, _ip]
     lib.mtg_gp_draw.restype = c_int
+    lib.mtg_lomb_scargle.restype = c_int
+    lib.mtg_lomb_scargle.argtypes = [c_vp, c_i64, _dp, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_gp_cond_draw.restype = c_int
     lib.mtg_gp_cond_draw.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, ctypes.c_uint64, _dp, _dp, _ip]
@@ -793,6 +798,28 @@ class Engine:
                                                 masks.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), M, _ptr(ts),
                                                 _ptr(mu), _ptr(var), _iptr(status)))
         return mu, var, status
+
+    def lomb_scargle(self, freqs, normalization="standard", weighted=True, power=True, peak=False):
+        """Generalised (floating-mean) Lomb-Scargle periodogram of every resident light curve at ``freqs`` [F] (cycles per
+        unit of time): astropy's ``LombScargle(t, y, dy, normalization=...).power(freqs)`` with its defaults
+        ``fit_mean=True, center_data=True, nterms=1``; ``weighted=False`` is ``dy=None``.  -> ``power`` [L][F], and / or
+        with ``peak`` ``(peak_power[L], peak_index[L])``: the maximum of every row and the first index attaining it,
+        reduced on the device -- with ``power=False`` nothing of size L F comes back.  Both asked for: a tuple
+        ``(power, peak_power, peak_index)``.  A model need not be set (mtg_lomb_scargle)."""
+        freqs = _f64(np.atleast_1d(freqs)).ravel()
+        if isinstance(normalization, str):
+            if normalization not in LS_NORMALIZATIONS:
+                raise ValueError("normalization must be one of %s" % sorted(LS_NORMALIZATIONS))
+            normalization = LS_NORMALIZATIONS[normalization]
+        F, L = len(freqs), int(self.L)
+        out = np.full((L, F), np.nan) if power else None
+        pk = np.full(L, np.nan) if peak else None
+        ix = np.full(L, -1, dtype=np.int64) if peak else None
+        self._check(self._lib.mtg_lomb_scargle(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), _ptr(out),
+                                               _ptr(pk), None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        if power and peak:
+            return out, pk, ix
+        return out if power else (pk, ix)
 
     def gp_draw(self, theta, lc_index=None, seed=0, normals=None):
         """Realisations of the GP itself, y[b] ~ N(mean, K(theta[b])) on the sampling and error bars of light curve

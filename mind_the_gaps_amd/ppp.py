@@ -29,7 +29,7 @@ from .modeling import ConstantModel
 from .sampler import integrated_time
 
 __all__ = ["EnsembleBatchSampler", "BatchPosteriors", "derive_posteriors_batch", "batched_minimize",
-           "protassov_test", "derive_posteriors_sharded"]
+           "protassov_test", "periodogram_peak_test", "derive_posteriors_sharded"]
 
 
 class PhaseTimer:
@@ -564,6 +564,62 @@ def protassov_test(lightcurve, null_kernel, alt_kernel, nsims=100, walkers=12, m
     return dict(T_obs=t_obs, T_sim=t_sim, p_value=lrt_pvalue(t_obs, t_sim), p_value_percentile=lrt_pvalue_percentile(t_obs, t_sim), null=null, alt=alt,
                 sim_null=fits[0], sim_alt=fits[1], lightcurves=out, seconds=timer.seconds, reproducible=plan.reproducible,
                 paired_launches=pair_stats, split=plan.split)
+
+
+def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walkers=12, max_steps=500, sigma_noise=None,
+                          extension_factor=2, normalization="standard", weighted=True, seed=None, device=0, progress=False,
+                          pdf="Gaussian", max_iter=400):
+    """The classic companion of the LRT p-value of ``protassov_test``: is the highest Lomb-Scargle peak of the observed
+    light curve unusual among light curves of the null model?
+
+    1. posterior of ``null_kernel`` on the observed light curve (the chain ``protassov_test`` runs for its null model);
+    2. ``nsims`` posterior samples, one light curve simulated from each on the observed sampling (device TK95, the path
+       ``protassov_test`` takes) and left resident on the device;
+    3. the generalised Lomb-Scargle periodogram of every simulated light curve at ``frequencies``, reduced to its peak on
+       the device (``Engine.lomb_scargle(power=False, peak=True)``), and the same of the observed light curve.
+
+    Returns dict(observed_peak, observed_frequency, sim_peaks[nsims], p_value = (1 + #{sim >= obs}) / (1 + nsims), null,
+    samples[nsims][P], sim_seed, lightcurves) -- the last three are what step 2 drew and made.  One GPU.  Every random number
+    comes from ``default_rng(seed)`` in a fixed order (the chain's seed, the picks, the simulator's seed): the same seed gives
+    the same result bit for bit.  ``weighted``: by the error bars, the simulated light curves' own included -- Poisson noise
+    at a few counts per epoch leaves epochs with ``dy = 0`` that take all the weight; pass ``weighted=False`` there."""
+    from .gp import get_engine
+    from .gpmodelling import GPModelling
+    from .simulator import Simulator
+    frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
+    sim = Simulator(null_kernel, lightcurve.times, lightcurve.exposures, lightcurve.mean, pdf,
+                    lightcurve.bkg_rate, lightcurve.bkg_rate_err, sigma_noise=sigma_noise,
+                    extension_factor=extension_factor, max_iter=max_iter, random_state=0, device=device)
+    sim.warm_up()
+    rng = np.random.default_rng(seed)
+    chain_seed = int(rng.integers(0, 2 ** 31 - 1))
+    on_device = walkers % 2 == 0
+    null = GPModelling(lightcurve, null_kernel, device=device, random_state=np.random.RandomState(chain_seed) if on_device else None)
+    state = np.random.get_state()
+    if not on_device:
+        np.random.seed(chain_seed)
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            null.derive_posteriors(fit=True, max_steps=max_steps, walkers=walkers, progress=progress, device_sampler=on_device)
+    finally:
+        if not on_device:
+            np.random.set_state(state)
+    samples = null.mcmc_samples[rng.integers(len(null.mcmc_samples), size=nsims)][:, :null_kernel.vector_size]
+    sim_seed = int(rng.integers(0, 2 ** 31 - 1))
+    eng = get_engine(device)
+    out = sim.simulate(samples, make_resident=True, seed=sim_seed)      # (the process-wide engine of the device holds them now)
+    sim_peaks, _ = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted, power=False, peak=True)
+    y = np.asarray(lightcurve.y, dtype=np.float64)
+    dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
+    eng.set_lightcurves(np.asarray(lightcurve.times, dtype=np.float64), y, dy)
+    eng.bound_to = None
+    obs, at = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None,
+                               power=False, peak=True)
+    observed_peak = float(obs[0])
+    p_value = (1.0 + float(np.sum(sim_peaks >= observed_peak))) / (1.0 + nsims)
+    return dict(observed_peak=observed_peak, observed_frequency=float(frequencies[at[0]]) if at[0] >= 0 else float("nan"),
+                sim_peaks=sim_peaks, p_value=p_value, null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
 
 
 def _seed_schedule(seed, nsims):
