@@ -677,6 +677,39 @@ MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs /* [F]
                              double *peak_power /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
 
 /*
+ * What the periodograms of the resident set say about every frequency: reductions of power[l][k] ACROSS the light
+ * curves, without the [L][F] array ever leaving the device.  power[l][k] is, by definition and bit for bit, what
+ * mtg_lomb_scargle returns for the same resident set, frequency, normalization and weighting (its launcher computes it).
+ *   order_stat[q][k]    the element of rank ranks[q] of column k sorted ascending with NaN last (numpy's sort order);
+ *                       ranks at or beyond valid[k] read NaN.  Equal values are one value: -0 and +0 may come in either sign.
+ *   valid[k]            #{l : power[l][k] is not NaN}
+ *   exceed[k]           #{l : power[l][k] >= reference[k]} (a NaN never counts)
+ *   peak_ratio[l]       max_k power[l][k] / scale[k] (the IEEE quotient), NaN entries passed over;
+ *   peak_ratio_index[l] the first k attaining it; a row of nothing but NaN: NaN and -1.
+ * The frequencies are walked in slabs (at most 64 MiB of device workspace whatever L F is; a column of up to 16384
+ * light curves is sorted in LDS, a longer one by a segmented radix sort).  Invariance: every output for column k depends
+ * on the resident set as a SET, freqs[k], normalization, weighted and reference[k] / scale[k] alone, bit for bit -- not on
+ * F, the order of freqs, the slabs, or (order_stat, valid, exceed) the order of the light curves; peak_ratio[l] depends
+ * on light curve l, the frequencies and scale alone.
+ * MTG_E_STATE without light curves; MTG_E_ARG for what mtg_lomb_scargle refuses (F < 1, a bad frequency, an unknown
+ * normalization, N < 4) and for Q < 0, a rank outside [0, L), Q > 0 with order_stat NULL, exceed without reference, a
+ * ratio output without scale, a reference entry that is not finite, a scale entry that is not finite and positive, and
+ * a call that asks for no output; the message names the offending index.  The resident set is only read; after an
+ * error the context works as before.  mtg_last_solver names "mtg_ls_envelope_column_kernel<C>" (C columns per
+ * workgroup) or "mtg_ls_envelope_select_kernel" (segmented sort), or the ratio-peak kernel where nothing else was asked
+ * for; mtg_last_kernel_ms runs from the pre-pass to the last slab's kernels.
+ */
+MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host */, int normalization, int weighted,
+                                      int Q, const int64_t *ranks /* [Q] host, each in [0, L), any order, duplicates allowed */,
+                                      double *order_stat /* [Q][F] host */,
+                                      int64_t *valid /* [F] or NULL */,
+                                      const double *reference /* [F] host, finite, or NULL */,
+                                      int64_t *exceed /* [F] or NULL, needs reference */,
+                                      const double *scale /* [F] host, finite and > 0, or NULL */,
+                                      double *peak_ratio /* [L] or NULL, needs scale */,
+                                      int64_t *peak_ratio_index /* [L] or NULL, needs scale */);
+
+/*
  * Accuracy probe of the device elementary functions the recurrence uses
  * (tests only): exp_neg[i] = exp(-x[i]), sin/cos(x[i]), rcp_x[i] = 1 / x[i] for
  * n host values x >= 0.

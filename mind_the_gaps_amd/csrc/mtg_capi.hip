@@ -1,6 +1,7 @@
 // mtg_capi.hip -- host side of the C-ABI declared in include/mtg.h.
 // One context = one MI355X + resident light curves + model + workspaces.
 #include "mtg_device.h"
+#include "mtg_ls_envelope_plan.h"
 #include "mtg_mean.h"
 #include "mtg_sim_plan.h"
 #include "mtg_solve_plan.h"
@@ -2546,6 +2547,95 @@ MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs, int n
     if (c.ok()) ctx->timed = true;
     if (peak_power) c.gather(peak_power, d_peak.p, (size_t)L * 8);
     if (peak_index) c.gather(peak_index, d_index.p, (size_t)L * 8);
+    return c.finish(nullptr);
+}
+
+MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, int Q,
+                                      const int64_t *ranks, double *order_stat, int64_t *valid, const double *reference,
+                                      int64_t *exceed, const double *scale, double *peak_ratio, int64_t *peak_ratio_index)
+{
+    RowCall c{ctx, "mtg_lomb_scargle_envelope", 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    int rc = c.ready(false);
+    if (rc) return rc;
+    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: need F >= 1 frequencies");
+    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
+        return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: unknown normalization %d", normalization);
+    const int64_t N = ctx->N, L = ctx->L;
+    if (N < 4) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: N = %lld < 4 samples (a sinusoid with a floating mean fits three exactly)", (long long)N);
+    for (int64_t k = 0; k < F; ++k)
+        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
+            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: freqs[%lld] = %g is not a finite positive frequency", (long long)k, freqs[k]);
+    if (Q < 0 || (Q > 0 && !ranks)) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: Q = %d ranks%s", Q, Q < 0 ? "" : ", ranks is NULL");
+    if (Q > 0 && !order_stat) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: Q = %d ranks, order_stat is NULL", Q);
+    for (int q = 0; q < Q; ++q)
+        if (ranks[q] < 0 || ranks[q] >= L)
+            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: ranks[%d] = %lld is outside [0, L = %lld)", q, (long long)ranks[q], (long long)L);
+    if (exceed && !reference) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: exceed needs reference");
+    const bool want_ratio = peak_ratio || peak_ratio_index, want_columns = Q > 0 || valid || exceed;
+    if (want_ratio && !scale) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: peak_ratio and peak_ratio_index need scale");
+    if (!want_columns && !want_ratio)
+        return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: order_stat, valid, exceed, peak_ratio and peak_ratio_index are all NULL");
+    for (int64_t k = 0; reference && k < F; ++k)
+        if (!std::isfinite(reference[k]))
+            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: reference[%lld] = %g is not finite", (long long)k, reference[k]);
+    for (int64_t k = 0; scale && k < F; ++k)
+        if (!std::isfinite(scale[k]) || !(scale[k] > 0.0))
+            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: scale[%lld] = %g is not finite and positive", (long long)k, scale[k]);
+    if ((rc = c.begin(false))) return rc;
+    // a slab of frequencies at a time, every light curve's power at them: mtg_ls_envelope_plan.h
+    const int64_t Fs = mtg_lse_slab_width(L, F, Q, MTG_LSE_BUDGET);
+    const bool in_lds = mtg_lse_in_lds(L) != 0;
+    const size_t slab_bytes = (size_t)L * (size_t)Fs * 8, temp_bytes = want_columns ? mtg_ls_envelope_temp_bytes(L, Fs) : 0;
+    MtgLombScargleArgs qa;
+    MtgLsEnvelopeArgs ea;
+    DevBuf d_freqs, d_stats, d_power, d_ranks, d_os, d_valid, d_ref, d_exceed, d_scale, d_peak, d_index, d_ka, d_kb, d_temp;
+    const bool sort_global = want_columns && !in_lds;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_power, slab_bytes}, {d_ranks, (size_t)Q * 8},
+               {d_os, (size_t)Q * (size_t)Fs * 8}, {d_valid, valid ? (size_t)F * 8 : 0}, {d_ref, reference ? (size_t)F * 8 : 0},
+               {d_exceed, exceed ? (size_t)F * 8 : 0}, {d_scale, want_ratio ? (size_t)F * 8 : 0},
+               {d_peak, want_ratio ? (size_t)L * 8 : 0}, {d_index, want_ratio ? (size_t)L * 8 : 0},
+               {d_ka, sort_global ? slab_bytes : 0}, {d_kb, sort_global ? slab_bytes : 0}, {d_temp, sort_global ? temp_bytes + 256 : 0}});
+    c.upload(d_freqs.p, freqs, (size_t)F * 8);
+    if (Q > 0) c.upload(d_ranks.p, ranks, (size_t)Q * 8);
+    if (reference) c.upload(d_ref.p, reference, (size_t)F * 8);
+    if (want_ratio) c.upload(d_scale.p, scale, (size_t)F * 8);
+    qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
+    qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.L = L;
+    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization;
+    qa.stats = d_stats.as<double>(); qa.power = d_power.as<double>();
+    qa.peak_power = nullptr; qa.peak_index = nullptr;
+    ea.slab = d_power.as<double>(); ea.L = L; ea.Q = Q; ea.ranks = d_ranks.as<int64_t>(); ea.order_stat = d_os.as<double>();
+    ea.valid = valid ? d_valid.as<int64_t>() : nullptr; ea.reference = reference ? d_ref.as<double>() : nullptr;
+    ea.exceed = exceed ? d_exceed.as<int64_t>() : nullptr; ea.scale = d_scale.as<double>();
+    ea.peak_ratio = d_peak.as<double>(); ea.peak_ratio_index = d_index.as<int64_t>();
+    ea.keys_a = d_ka.p; ea.keys_b = d_kb.p; ea.temp = d_temp.p; ea.temp_bytes = temp_bytes + 256;
+    if (!want_columns) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_ls_envelope_ratio_peak_kernel");
+    else if (in_lds) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_ls_envelope_column_kernel<%d>", mtg_lse_columns(L));
+    else snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_ls_envelope_select_kernel");
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        mtg_launch_lomb_scargle_stats(qa, c.s);
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(F, Fs, [&](int64_t k0, int64_t cols) {
+        qa.F = cols; qa.freqs = d_freqs.as<double>() + k0;
+        ea.Fs = cols; ea.k0 = k0;
+        c.then([&] { return mtg_launch_lomb_scargle(qa, 0, L, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        if (want_columns) c.then([&] { return mtg_launch_ls_envelope_columns(ea, c.s); });
+        if (want_ratio) c.then([&] { return mtg_launch_ls_envelope_ratio_peaks(ea, c.s); });
+        if (k0 + cols == F) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+        // (the copy is ordered on the stream: the next slab's kernels overwrite the buffer only after it)
+        if (Q > 0) c.then([&] {
+            return hipMemcpy2DAsync(order_stat + k0, (size_t)F * 8, d_os.p, (size_t)cols * 8, (size_t)cols * 8, (size_t)Q,
+                                    hipMemcpyDeviceToHost, c.s);
+        });
+        return c.e;
+    });
+    if (c.ok()) ctx->timed = true;
+    if (valid) c.gather(valid, d_valid.p, (size_t)F * 8);
+    if (exceed) c.gather(exceed, d_exceed.p, (size_t)F * 8);
+    if (peak_ratio) c.gather(peak_ratio, d_peak.p, (size_t)L * 8);
+    if (peak_ratio_index) c.gather(peak_ratio_index, d_index.p, (size_t)L * 8);
     return c.finish(nullptr);
 }
 

@@ -272,6 +272,32 @@ int mtg_launch_lomb_scargle(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, 
 // light curves per lane for a set of L (1, 4, or the full tile of the weighting)
 int mtg_lomb_scargle_tile(int64_t L, int shared_sampling, int weighted);
 
+// One slab of mtg_lomb_scargle_envelope (mtg_lomb_scargle_envelope.hip; the cutting rules: mtg_ls_envelope_plan.h): the
+// powers of all L light curves at the Fs frequencies from k0 on, as mtg_launch_lomb_scargle left them
+struct MtgLsEnvelopeArgs {
+    const double *slab;            // [L][Fs]
+    int64_t L, Fs, k0;
+    int Q;
+    const int64_t *ranks;          // [Q] on the device, each in [0, L)
+    double *order_stat;            // [Q][Fs]: the slab's
+    int64_t *valid;                // [F] or NULL: the call's, written at k0 + k
+    const double *reference;       // [F] or NULL
+    int64_t *exceed;               // [F] or NULL (needs reference)
+    const double *scale;           // [F]: ratio peaks only
+    double *peak_ratio;            // [L]: the running maximum of power / scale over the slabs so far, ascending k0
+    int64_t *peak_ratio_index;     // [L]
+    void *keys_a, *keys_b;         // [Fs][L] 64-bit keys each, and rocPRIM's temporary storage: L > MTG_LSE_LDS_KEYS only
+    void *temp;
+    size_t temp_bytes;
+};
+static_assert(std::is_trivially_copyable<MtgLsEnvelopeArgs>::value, "plain data");
+// order statistics, valid and exceed of every column of the slab (in LDS, or by segmented sort: mtg_lse_in_lds)
+hipError_t mtg_launch_ls_envelope_columns(const MtgLsEnvelopeArgs &, hipStream_t);
+// the slab folded into the running ratio peaks
+hipError_t mtg_launch_ls_envelope_ratio_peaks(const MtgLsEnvelopeArgs &, hipStream_t);
+// rocPRIM's temporary storage for a slab of Fs columns (0 on the LDS path)
+size_t mtg_ls_envelope_temp_bytes(int64_t L, int64_t Fs);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

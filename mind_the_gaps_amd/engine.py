@@ -5,6 +5,7 @@ There is no CPU fallback: if the shared library or a GPU is missing, every
 entry point raises (``EngineUnavailable``) -- a likelihood is never computed
 on the host.
 """
+import collections
 import ctypes
 import importlib.util
 import os
@@ -40,7 +41,7 @@ EXPORTS = (
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
-    "mtg_predict_terms", "mtg_lomb_scargle",
+    "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope",
 )
 
 TERMS_MEAN = 1 << 31   # include/mtg.h, MTG_TERMS_MEAN: a mask of predict_terms with this bit adds the mean
@@ -51,6 +52,9 @@ LS_NORMALIZATIONS = {"standard": LS_STANDARD, "model": LS_MODEL, "log": LS_LOG, 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_int64, ctypes.c_int64)
+
+
+LombScargleEnvelope = collections.namedtuple("LombScargleEnvelope", "order_stat valid exceed peak_ratio peak_ratio_index")
 
 
 class EngineUnavailable(RuntimeError):
@@ -329,6 +333,9 @@ def load_library():
     lib.mtg_gp_draw.restype = c_int
     lib.mtg_lomb_scargle.restype = c_int
     lib.mtg_lomb_scargle.argtypes = [c_vp, c_i64, _dp, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lomb_scargle_envelope.restype = c_int
+    lib.mtg_lomb_scargle_envelope.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, ctypes.POINTER(c_i64), _dp, ctypes.POINTER(c_i64),
+                                              _dp, ctypes.POINTER(c_i64), _dp, _dp, ctypes.POINTER(c_i64)]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_gp_cond_draw.restype = c_int
     lib.mtg_gp_cond_draw.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, ctypes.c_uint64, _dp, _dp, _ip]
@@ -820,6 +827,48 @@ class Engine:
         if power and peak:
             return out, pk, ix
         return out if power else (pk, ix)
+
+    def lomb_scargle_envelope(self, freqs, ranks=(), reference=None, scale=None, normalization="standard", weighted=True):
+        """What the periodograms of the resident set say about every frequency, reduced ACROSS the light curves on the
+        device; ``power[l][k]`` below is ``lomb_scargle(freqs, normalization, weighted)`` bit for bit and never comes back.
+        -> ``LombScargleEnvelope(order_stat, valid, exceed, peak_ratio, peak_ratio_index)``, ``None`` where not asked for:
+
+        * ``ranks`` [Q] (each in [0, L), any order, duplicates allowed): ``order_stat[q][k]``, the element of rank
+          ``ranks[q]`` of ``np.sort(power, axis=0)[:, k]`` (NaN last; ``periodogram.envelope_levels`` turns them into
+          quantiles);
+        * with ``ranks`` or ``reference``: ``valid[k]``, the number of entries of column k that are not NaN;
+        * ``reference`` [F], finite: ``exceed[k] = #{l : power[l][k] >= reference[k]}``;
+        * ``scale`` [F], finite and positive: ``peak_ratio[l] = max_k power[l][k] / scale[k]`` and the first index
+          attaining it (NaN passed over; a row of nothing else: NaN and -1).
+
+        A model need not be set (mtg_lomb_scargle_envelope)."""
+        freqs = _f64(np.atleast_1d(freqs)).ravel()
+        if isinstance(normalization, str):
+            if normalization not in LS_NORMALIZATIONS:
+                raise ValueError("normalization must be one of %s" % sorted(LS_NORMALIZATIONS))
+            normalization = LS_NORMALIZATIONS[normalization]
+        F, L = len(freqs), int(self.L)
+        ranks = np.ascontiguousarray(np.atleast_1d(ranks), dtype=np.int64).ravel()
+        Q = len(ranks)
+        ip = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        order_stat = np.full((Q, F), np.nan) if Q else None
+        nvalid = np.zeros(F, dtype=np.int64) if (Q or reference is not None) else None
+        exceed = None
+        if reference is not None:
+            reference = _f64(np.atleast_1d(reference)).ravel()
+            if len(reference) != F:
+                raise ValueError("reference must have one entry per frequency")
+            exceed = np.zeros(F, dtype=np.int64)
+        pk = ix = None
+        if scale is not None:
+            scale = _f64(np.atleast_1d(scale)).ravel()
+            if len(scale) != F:
+                raise ValueError("scale must have one entry per frequency")
+            pk, ix = np.full(L, np.nan), np.full(L, -1, dtype=np.int64)
+        self._check(self._lib.mtg_lomb_scargle_envelope(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), Q,
+                                                        ip(ranks) if Q else None, _ptr(order_stat), ip(nvalid), _ptr(reference),
+                                                        ip(exceed), _ptr(scale), _ptr(pk), ip(ix)))
+        return LombScargleEnvelope(order_stat, nvalid, exceed, pk, ix)
 
     def gp_draw(self, theta, lc_index=None, seed=0, normals=None):
         """Realisations of the GP itself, y[b] ~ N(mean, K(theta[b])) on the sampling and error bars of light curve

@@ -2,6 +2,9 @@
 (``lomb_scargle_biases.ipynb``: ``LombScargle(t, y, fit_mean=True, nterms=1, center_data=True, normalization=...)`` and
 ``.power(frequencies)``), for one light curve or for a whole set on shared sampling in one call.
 
+``envelope_ranks`` / ``envelope_levels`` turn the order statistics of ``Engine.lomb_scargle_envelope`` into the quantiles
+``np.quantile(power, levels, axis=0)`` would give, without the [L][F] power array.
+
 The periodogram is the generalised (floating-mean) one of Zechmeister & Kuerster (2009), evaluated by ``mtg_lomb_scargle``
 (include/mtg.h) on the GPU.  There is no CPU fallback, as elsewhere in the package.
 """
@@ -9,7 +12,7 @@ import numpy as np
 
 from .engine import LS_NORMALIZATIONS
 
-__all__ = ["LombScargle"]
+__all__ = ["LombScargle", "envelope_ranks", "envelope_levels"]
 
 
 class LombScargle:
@@ -64,3 +67,52 @@ class LombScargle:
     def autopower(self, **kwargs):
         frequency = self.autofrequency(**kwargs)
         return frequency, self.power(frequency)
+
+
+def _virtual_index(L, levels):
+    """numpy's position of a quantile in a sorted sample of L (method "linear": (L - 1) q, as numpy 2 forms it), with the
+    two neighbouring ranks: beyond the last rank the last one."""
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or not np.all((levels >= 0) & (levels <= 1)):
+        raise ValueError("levels must lie in [0, 1]")
+    virtual = (L - 1) * levels
+    lower = np.floor(virtual).astype(np.int64)
+    upper = lower + 1
+    upper[upper > L - 1] = L - 1
+    lower[lower > L - 1] = L - 1
+    lower[lower < 0] = 0
+    return virtual, lower, upper
+
+
+def envelope_ranks(L, levels):
+    """The ranks ``Engine.lomb_scargle_envelope`` has to return for ``envelope_levels(..., L, levels)``: the two
+    neighbours of every level's position in a sorted sample of L, and the last rank L - 1, which tells whether a column
+    holds a NaN -> ascending int64, without duplicates."""
+    L = int(L)
+    if L < 1:
+        raise ValueError("L must be at least 1")
+    _, lower, upper = _virtual_index(L, levels)
+    return np.unique(np.concatenate([lower, upper, [L - 1]])).astype(np.int64)
+
+
+def envelope_levels(order_stat, ranks, L, levels):
+    """``np.quantile(power, levels, axis=0)`` (numpy's default "linear" rule) from order statistics alone:
+    ``order_stat[q]`` is the row of rank ``ranks[q]`` of ``np.sort(power, axis=0)``, ``L = len(power)``.  -> [len(levels)][F];
+    a column with a NaN gives NaN, as numpy's does.  ``ranks`` must hold ``envelope_ranks(L, levels)``.  The interpolation is
+    written as numpy writes it (``a + (b - a) t``, and ``b - (b - a) (1 - t)`` from t = 1/2 on), so the result is numpy's
+    bit for bit."""
+    order_stat = np.atleast_2d(np.asarray(order_stat, dtype=np.float64))
+    where = {int(r): q for q, r in enumerate(np.atleast_1d(ranks))}
+    L = int(L)
+    virtual, lower, upper = _virtual_index(L, levels)
+    missing = sorted(set(map(int, np.concatenate([lower, upper, [L - 1]]))) - set(where))
+    if missing:
+        raise ValueError("ranks lack %s (envelope_ranks gives what is needed)" % missing)
+    a = order_stat[[where[int(r)] for r in lower]]
+    b = order_stat[[where[int(r)] for r in upper]]
+    t = (virtual - lower).reshape(-1, 1)
+    diff = b - a
+    out = a + diff * t
+    np.subtract(b, diff * (1 - t), out=out, where=t >= 0.5)
+    out[:, np.isnan(order_stat[where[L - 1]])] = np.nan
+    return out

@@ -29,7 +29,7 @@ from .modeling import ConstantModel
 from .sampler import integrated_time
 
 __all__ = ["EnsembleBatchSampler", "BatchPosteriors", "derive_posteriors_batch", "batched_minimize",
-           "protassov_test", "periodogram_peak_test", "derive_posteriors_sharded"]
+           "protassov_test", "periodogram_peak_test", "periodogram_significance", "derive_posteriors_sharded"]
 
 
 class PhaseTimer:
@@ -583,10 +583,31 @@ def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walke
     comes from ``default_rng(seed)`` in a fixed order (the chain's seed, the picks, the simulator's seed): the same seed gives
     the same result bit for bit.  ``weighted``: by the error bars, the simulated light curves' own included -- Poisson noise
     at a few counts per epoch leaves epochs with ``dy = 0`` that take all the weight; pass ``weighted=False`` there."""
+    frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
+    eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
+                                                           extension_factor, seed, device, progress, pdf, max_iter)
+    sim_peaks, _ = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted, power=False, peak=True)
+    y = np.asarray(lightcurve.y, dtype=np.float64)
+    dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
+    eng.set_lightcurves(np.asarray(lightcurve.times, dtype=np.float64), y, dy)
+    eng.bound_to = None
+    obs, at = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None,
+                               power=False, peak=True)
+    observed_peak = float(obs[0])
+    p_value = (1.0 + float(np.sum(sim_peaks >= observed_peak))) / (1.0 + nsims)
+    return dict(observed_peak=observed_peak, observed_frequency=float(frequencies[at[0]]) if at[0] >= 0 else float("nan"),
+                sim_peaks=sim_peaks, p_value=p_value, null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+
+
+def _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise, extension_factor, seed, device,
+                       progress, pdf, max_iter):
+    """Steps 1 and 2 of ``periodogram_peak_test`` and ``periodogram_significance``: the null model's chain on the observed
+    light curve, ``nsims`` posterior samples, one light curve simulated from each and left resident on the device's
+    engine -> (engine, null, samples, sim_seed, lightcurves).  Every random number comes from ``default_rng(seed)`` in a
+    fixed order (the chain's seed, the picks, the simulator's seed)."""
     from .gp import get_engine
     from .gpmodelling import GPModelling
     from .simulator import Simulator
-    frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
     sim = Simulator(null_kernel, lightcurve.times, lightcurve.exposures, lightcurve.mean, pdf,
                     lightcurve.bkg_rate, lightcurve.bkg_rate_err, sigma_noise=sigma_noise,
                     extension_factor=extension_factor, max_iter=max_iter, random_state=0, device=device)
@@ -609,17 +630,77 @@ def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walke
     sim_seed = int(rng.integers(0, 2 ** 31 - 1))
     eng = get_engine(device)
     out = sim.simulate(samples, make_resident=True, seed=sim_seed)      # (the process-wide engine of the device holds them now)
-    sim_peaks, _ = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted, power=False, peak=True)
+    return eng, null, samples, sim_seed, out
+
+
+def _observed_power(eng, lightcurve, frequencies, normalization, weighted):
+    """The observed light curve made resident (nobody's evaluator's afterwards), and its periodogram [F]."""
     y = np.asarray(lightcurve.y, dtype=np.float64)
     dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
     eng.set_lightcurves(np.asarray(lightcurve.times, dtype=np.float64), y, dy)
     eng.bound_to = None
-    obs, at = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None,
-                               power=False, peak=True)
-    observed_peak = float(obs[0])
-    p_value = (1.0 + float(np.sum(sim_peaks >= observed_peak))) / (1.0 + nsims)
-    return dict(observed_peak=observed_peak, observed_frequency=float(frequencies[at[0]]) if at[0] >= 0 else float("nan"),
-                sim_peaks=sim_peaks, p_value=p_value, null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+    return eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None)[0]
+
+
+def _significance_of_resident_set(eng, observed_power, frequencies, nsims, levels, normalization, weighted):
+    """Steps 4 to 6 of ``periodogram_significance`` on an engine that holds the ``nsims`` simulated light curves: the two
+    envelope calls and the arithmetic on what comes back (tests drive it with a stand-in engine on the CPU)."""
+    from .periodogram import envelope_levels, envelope_ranks
+    levels = tuple(float(v) for v in np.atleast_1d(levels))
+    if not np.all(np.isfinite(observed_power)):
+        k = int(np.flatnonzero(~np.isfinite(observed_power))[0])
+        raise ValueError("periodogram_significance: the observed power at frequencies[%d] = %g is not finite" % (k, frequencies[k]))
+    ranks = envelope_ranks(nsims, (0.5,) + levels)
+    env = eng.lomb_scargle_envelope(frequencies, ranks=ranks, reference=observed_power, normalization=normalization, weighted=weighted)
+    quantiles = envelope_levels(env.order_stat, ranks, nsims, (0.5,) + levels)
+    median = quantiles[0]
+    bad = ~(np.isfinite(median) & (median > 0))
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError("periodogram_significance: the median power of the simulated light curves at frequencies[%d] = %g is %g, "
+                         "not finite and positive" % (k, frequencies[k], median[k]))
+    peaks = eng.lomb_scargle_envelope(frequencies, scale=median, normalization=normalization, weighted=weighted)
+    ratio = observed_power / median
+    at = int(np.argmax(ratio))                     # (finite over finite and positive: no NaN; the first maximum)
+    observed_ratio_peak = float(ratio[at])
+    return dict(observed_power=observed_power, median=median, levels=quantiles[1:],
+                local_p=(1.0 + env.exceed) / (1.0 + nsims),
+                observed_ratio_peak=observed_ratio_peak, observed_frequency=float(frequencies[at]),
+                sim_ratio_peaks=peaks.peak_ratio,
+                global_p=(1.0 + float(np.sum(peaks.peak_ratio >= observed_ratio_peak))) / (1.0 + nsims))
+
+
+def periodogram_significance(lightcurve, null_kernel, frequencies, nsims=100, levels=(0.95, 0.997), walkers=12, max_steps=500,
+                             sigma_noise=None, extension_factor=2, normalization="standard", weighted=True, seed=None, device=0,
+                             progress=False, pdf="Gaussian", max_iter=400):
+    """What a red-noise periodicity search reports (Vaughan 2005): the significance of the observed Lomb-Scargle power
+    frequency by frequency, against light curves of the null model.  ``periodogram_peak_test`` compares highest RAW peaks,
+    which for red-noise nulls sit at the lowest frequencies whatever the data hold; this compares every frequency with the
+    null's own distribution there, and corrects for the trials with the highest RATIO of power to the null's median.
+
+    1. the observed light curve's periodogram at ``frequencies``;
+    2. and 3. the null chain, the ``nsims`` posterior picks and the simulated set of ``periodogram_peak_test``: the same
+       ones for the same seed, left resident on the device;
+    4. one ``Engine.lomb_scargle_envelope`` call on that set: the order statistics for the median and ``levels`` (numpy's
+       "linear" quantiles, ``periodogram.envelope_levels``) and, per frequency, the simulations at or above the observed power;
+    5. a second call with ``scale=median``: every simulation's highest power / median;
+    6. the same ratio peak of the observed light curve, on the host.
+    The [nsims][F] powers never leave the device.
+
+    Returns dict(observed_power[F], median[F], levels[len(levels)][F], local_p[F] = (1 + exceed) / (1 + nsims),
+    observed_ratio_peak, observed_frequency, sim_ratio_peaks[nsims], global_p = (1 + #{sim >= obs}) / (1 + nsims), null,
+    samples[nsims][P], sim_seed, lightcurves).  A median that is not finite and positive at some frequency raises a
+    ValueError naming it.  One GPU; the same seed gives the same result bit for bit.  ``weighted``: by the error bars, the
+    simulated light curves' own included -- Poisson noise at a few counts per epoch leaves epochs with ``dy = 0`` that
+    take all the weight; pass ``weighted=False`` there."""
+    from .gp import get_engine
+    frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
+    observed_power = _observed_power(get_engine(device), lightcurve, frequencies, normalization, weighted)
+    eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
+                                                           extension_factor, seed, device, progress, pdf, max_iter)
+    res = _significance_of_resident_set(eng, observed_power, frequencies, nsims, levels, normalization, weighted)
+    res.update(null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+    return res
 
 
 def _seed_schedule(seed, nsims):
