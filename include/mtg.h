@@ -584,6 +584,41 @@ MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int3
                         const double *normals /* [B][N] or NULL: Philox */, double *y /* [B][N] */, int32_t *status);
 
 /*
+ * The whitened (one-step-ahead) residuals of B rows and their goodness-of-fit diagnostics: the inverse of mtg_gp_draw.
+ * With K = L diag(D) L^T and r = y - mean(t) (the fitted constant or linear mean),
+ *     q = D^-1/2 L^-1 r,    q[b][n] = (y_n - E[y_n | y_1 .. y_n-1]) / sqrt(Var[y_n | y_1 .. y_n-1]):
+ * under the model the q_n are i.i.d. N(0, 1) -- what a KS test against the normal and an autocorrelation band of
+ * +-1.96 / sqrt(N) assume (the smoothing residual of mtg_predict is neither independent nor of unit variance) -- and
+ * lnL = -1/2 (stats[1] + stats[2] + N ln 2 pi).  O(N J^2) per row: the forward sweep of mtg_gp_draw with the
+ * innovation taken from the data.
+ *   y      [B][N] data (host) WITHOUT the per-light-curve y_offset, as mtg_gp_draw returns them; NULL: the resident
+ *          data of light curve lc_index[b].  The same data give the same bits either way.
+ *   q      [B][N] or NULL.
+ *   acf    [B][K] or NULL (then K must be 0): acf[b][k - 1] = sum_{n < N - k} q_n q_{n+k} / sum_n q_n^2, k = 1 .. K,
+ *          1 <= K <= N - 1 (matplotlib's acorr: no mean subtracted, normalised by lag 0).  O(N K) per row.
+ *   stats  [B][MTG_WHITEN_NSTATS] or NULL:
+ *          0 sum q   1 sum q^2   2 sum ln D   3 sum q^3   4 sum q^4   7 max |q|      (summed in sample order)
+ *          5 D+ = max_i (i / N - Phi(q_(i)))   6 D- = max_i (Phi(q_(i)) - (i - 1) / N)   (the one-sample KS distances
+ *          of the sorted row against the standard normal, Phi(x) = erfc(-x / sqrt 2) / 2).  D+ and D- are formed
+ *          where the residuals are on the device anyway, that is when q or acf is asked for; a call for stats alone
+ *          stores nothing of size N, costs one sweep and returns NaN in slots 5 and 6.
+ * K outside its range, K != 0 without acf, and q, acf and stats all NULL are MTG_E_ARG; B == 0 is MTG_OK.  Rows outside
+ * the prior or with a non-positive pivot keep their status and read back NaN in every output.  A row's outputs do not
+ * depend on the batch it travels in.  Large batches go in slabs of rows (device memory O(slab N): up to 256 MiB each
+ * for the given y, q, its sorted copy and the lags; what exceeds 64 MiB is freed when the call returns); where D+ and
+ * D- are formed a slab holds fewer than 2^31 samples (the sort's item count), down to one row, and N >= 2^31 is
+ * MTG_E_ARG.  Ranks above MTG_MAX_J and profile means return MTG_E_UNSUPPORTED.  mtg_last_solver names
+ * "mtg_whiten_kernel<J>".
+ */
+#define MTG_WHITEN_NSTATS 8
+MTG_API int mtg_whiten(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index,
+                       const double *y      /* [B][N] host, or NULL: the resident data of lc_index[b] */,
+                       double *q            /* [B][N] or NULL */,
+                       int K, double *acf   /* [B][K] or NULL (then K must be 0) */,
+                       double *stats        /* [B][MTG_WHITEN_NSTATS] or NULL */,
+                       int32_t *status);
+
+/*
  * celerite.GP.sample_conditional(y, t): B draws of the process GIVEN the resident data, at M new times ts[M] (any
  * order, duplicates allowed, shared by all rows; a non-finite one is MTG_E_ARG; M == 0 is MTG_OK and writes nothing).
  * celerite forms the dense M x N cross-covariance and factors the dense M x M conditional covariance; here Matheron's

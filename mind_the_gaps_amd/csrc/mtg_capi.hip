@@ -157,6 +157,8 @@ struct mtg_ctx {
     // staging for the host-pointer entry points
     DevBuf theta, lc, out, status;
     DevBuf grad_dcoef, grad, grad_verdict;  // mtg_loglike_grad: coefficient tangents [nslots][B P], the gradient [B][P], the expansion's status [B]; grown on demand
+    // mtg_whiten: one slab of given data, residuals, their sorted copy and lag sums, the sort's scratch; [B][8] sums; grown on demand
+    DevBuf whiten_y, whiten_q, whiten_sorted, whiten_acf, whiten_temp, whiten_stats;
 
     // small batches: one wave per evaluation, parallel in time (0 never, 1 whenever compiled, 2 auto)
     int tp_mode = 2;   // (3: as 1, but the one-wave-per-evaluation kernel only -- results independent of the batch size)
@@ -2669,6 +2671,60 @@ MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int3
         return c.e;
     });
     return c.finish(status);
+}
+
+MTG_API int mtg_whiten(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, const double *y, double *q,
+                       int K, double *acf, double *stats, int32_t *status)
+{
+    RowCall c{ctx, "mtg_whiten", B, theta, lc_index, 1};
+    int rc = c.ready();
+    if (rc) return rc;
+    if (B < 0 || !status || (!theta && ctx->model.P > 0 && B > 0) || (!q && !acf && !stats)) return c.bad_arguments();
+    const int64_t N = ctx->N;
+    if (acf ? (K < 1 || K > N - 1) : K != 0)
+        return fail(ctx, MTG_E_ARG, "mtg_whiten: K = %d lags%s (1 <= K <= N - 1 = %lld with acf, 0 without)", K, acf ? "" : ", acf is NULL",
+                    (long long)(N - 1));
+    if ((rc = c.begin(true))) return rc;
+    const int J = ctx->model.nr0 + 2 * ctx->model.nc0;
+    if (J > MTG_MAX_J) return fail(ctx, MTG_E_UNSUPPORTED, "mtg_whiten: rank %d > %d", J, MTG_MAX_J);
+    if (B == 0) return MTG_OK;
+    const size_t row_bytes = (size_t)N * 8, stat_bytes = (size_t)MTG_WHITEN_NSTATS * 8;
+    // D+ and D- need the rows' residuals on the device: with stats alone the sweep stores nothing of size N, writes its
+    // sums and leaves NaN in the two slots; with acf but no q the residuals go to the context's slab
+    const bool need_q = q || acf, want_ks = stats && need_q;
+    const int64_t Bs = mtg_plan_whiten_slab(N, B, ctx->window_bytes, want_ks);
+    const size_t temp_bytes = want_ks ? mtg_whiten_sort_temp_bytes(Bs, N) : 0;
+    if (want_ks && temp_bytes == 0) return fail(ctx, MTG_E_ARG, "mtg_whiten: N = %lld is too large for the KS sort", (long long)N);
+    MtgWhitenArgs qa;
+    c.stage_inputs();
+    c.expand(qa);
+    c.reserve({{ctx->whiten_y, y ? (size_t)Bs * row_bytes : 0}, {ctx->whiten_q, need_q ? (size_t)Bs * row_bytes : 0},
+               {ctx->whiten_sorted, want_ks ? (size_t)Bs * row_bytes : 0}, {ctx->whiten_acf, acf ? (size_t)Bs * (size_t)K * 8 : 0},
+               {ctx->whiten_temp, temp_bytes}, {ctx->whiten_stats, (size_t)B * stat_bytes}});
+    qa.y = y ? ctx->whiten_y.as<double>() : nullptr;
+    qa.q = need_q ? ctx->whiten_q.as<double>() : nullptr;
+    qa.stats = ctx->whiten_stats.as<double>();
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_whiten_kernel<%d>", J);
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    if (c.ok()) c.e = for_each_slab(B, Bs, [&](int64_t row0, int64_t rows) {
+        qa.row0 = row0; qa.B = rows;
+        // (the copies are ordered on the stream: the next slab's upload and kernels touch the buffers only after them)
+        if (y) c.upload(ctx->whiten_y.p, y + row0 * N, (size_t)rows * row_bytes);
+        c.then([&] { return mtg_launch_whiten(qa, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
+        if (want_ks) c.then([&] { return mtg_launch_whiten_ks(qa, ctx->whiten_sorted.as<double>(), ctx->whiten_temp.p, temp_bytes, c.s); });
+        if (acf) c.then([&] { return mtg_launch_whiten_acf(qa, K, ctx->whiten_acf.as<double>(), c.s); });
+        if (row0 + rows == B) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+        if (q) c.gather(q + row0 * N, ctx->whiten_q.p, (size_t)rows * row_bytes);
+        if (acf) c.gather(acf + row0 * K, ctx->whiten_acf.p, (size_t)rows * (size_t)K * 8);
+        return c.e;
+    });
+    if (c.ok()) ctx->timed = true;
+    if (stats) c.gather(stats, ctx->whiten_stats.p, (size_t)B * stat_bytes);
+    rc = c.finish(status);
+    // (the stream is idle) a large call does not leave its slabs with the context: up to four of 256 MiB
+    for (DevBuf *buf : {&ctx->whiten_y, &ctx->whiten_q, &ctx->whiten_sorted, &ctx->whiten_acf, &ctx->whiten_temp})
+        if (buf->cap > MTG_WHITEN_KEEP_BYTES) buf->release();
+    return rc;
 }
 
 MTG_API int mtg_gp_cond_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, int64_t M,

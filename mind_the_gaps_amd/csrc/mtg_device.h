@@ -223,6 +223,23 @@ struct MtgGpDrawArgs : MtgRowArgs {     // of yv only the sigma^2 half is read
 // one slab of draws; 0 = rank outside 0 .. MTG_MAX_J
 int mtg_launch_gp_draw(const MtgGpDrawArgs &, hipStream_t);
 
+// samples per chunk of the autocorrelation's lag sums (mtg_whiten.hip): wave w of four takes the chunks w, w + 4, ...
+#ifndef MTG_WHITEN_ACF_CHUNK
+#define MTG_WHITEN_ACF_CHUNK 256
+#endif
+
+struct MtgWhitenArgs : MtgRowArgs {     // the inverse of the draw (mtg_whiten.hip)
+    const double *y;        // [B][N] data of this slab without the y_offset, or NULL: the resident data
+    double *q;              // [B][N] of this slab, or NULL: the sums alone
+    double *stats;          // [batch][MTG_WHITEN_NSTATS], indexed by the row of the batch
+};
+// one slab of the sweep; 0 = rank outside 0 .. MTG_MAX_J
+int mtg_launch_whiten(const MtgWhitenArgs &, hipStream_t);
+// the diagnostics of one slab from its q: KS distances into stats (q sorted into `sorted`, [B][N]), lag sums into acf [B][K]
+size_t mtg_whiten_sort_temp_bytes(int64_t rows, int64_t N);
+hipError_t mtg_launch_whiten_ks(const MtgWhitenArgs &, double *sorted, void *temp, size_t temp_bytes, hipStream_t);
+hipError_t mtg_launch_whiten_acf(const MtgWhitenArgs &, int K, double *acf, hipStream_t);
+
 // highest rank the gradient's tangent sweep is compiled for (mtg_loglike_grad.hip): primal and tangent state of a
 // lane live in registers, and beyond this rank they no longer fit without scratch
 #ifndef MTG_GRAD_MAX_J
@@ -243,7 +260,8 @@ struct MtgGradArgs : MtgRowArgs {       // the whole batch in one launch: row0 =
 int mtg_launch_loglike_grad(const MtgGradArgs &, hipStream_t);
 static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivially_copyable<MtgPredictAtArgs>::value &&
               std::is_trivially_copyable<MtgGpDrawArgs>::value && std::is_trivially_copyable<MtgGradArgs>::value &&
-              std::is_trivially_copyable<MtgGpCondDrawArgs>::value && std::is_trivially_copyable<MtgPredictTermsArgs>::value,
+              std::is_trivially_copyable<MtgGpCondDrawArgs>::value && std::is_trivially_copyable<MtgPredictTermsArgs>::value &&
+              std::is_trivially_copyable<MtgWhitenArgs>::value,
               "passed by value as kernel arguments");
 
 // light curves whose sums one lane of the Lomb-Scargle kernel carries on shared sampling (mtg_lomb_scargle.hip): with the

@@ -324,6 +324,27 @@ static inline int64_t mtg_plan_draw_slab(int64_t N, int64_t B)
     return Bs;
 }
 
+// mtg_whiten: as mtg_plan_draw_slab -- whole workgroups of 64 rows whose residuals [rows][N] stay within `budget` bytes,
+// at least 64, or all B rows -- and at most 65472 rows, the y extent of the autocorrelation's grid in whole workgroups.
+// The budget is MTG_DRAW_SLAB_BYTES or the context's window (mtg_set_window_bytes), whichever is smaller: one slab of
+// residuals stays within the reach of one buffer descriptor, as a resident light curve does.  sorted: the rows are sorted
+// for the KS distances, and the segmented sort counts a slab's items in 32 bits: then rows N < 2^31 comes first, down to
+// one row (a slab need not be whole workgroups: a row does not depend on its neighbours).
+#define MTG_WHITEN_SLAB_MAX_ROWS 65472
+// slab buffers above this are given back at the end of a call (mtg_capi.hip)
+#define MTG_WHITEN_KEEP_BYTES ((size_t)64 << 20)
+static inline int64_t mtg_plan_whiten_slab(int64_t N, int64_t B, uint64_t window_bytes, bool sorted = false)
+{
+    const uint64_t budget = window_bytes < (uint64_t)MTG_DRAW_SLAB_BYTES ? window_bytes : (uint64_t)MTG_DRAW_SLAB_BYTES;
+    int64_t Bs = (int64_t)(budget / ((uint64_t)N * 8)) / 64 * 64;
+    if (Bs < 64) Bs = 64;
+    if (Bs > MTG_WHITEN_SLAB_MAX_ROWS) Bs = MTG_WHITEN_SLAB_MAX_ROWS;
+    if (sorted && Bs > (int64_t)0x7fffffff / N) Bs = (int64_t)0x7fffffff / N;
+    if (Bs < 1) Bs = 1;
+    if (Bs > B) Bs = B;
+    return Bs;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // The run plan of the device-resident sampler (mtg_capi.hip: mtg_ensemble_run)
 

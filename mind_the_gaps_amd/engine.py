@@ -41,9 +41,12 @@ EXPORTS = (
     "mtg_set_simulate_draws",
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
-    "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope",
+    "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope", "mtg_whiten",
 )
 
+# include/mtg.h, MTG_WHITEN_NSTATS and the slots of a row of whiten's stats
+WHITEN_NSTATS = 8
+WHITEN_SUM, WHITEN_SUM2, WHITEN_LOGDET, WHITEN_SUM3, WHITEN_SUM4, WHITEN_KS_PLUS, WHITEN_KS_MINUS, WHITEN_MAXABS = range(8)
 TERMS_MEAN = 1 << 31   # include/mtg.h, MTG_TERMS_MEAN: a mask of predict_terms with this bit adds the mean
 # include/mtg.h, MTG_LS_*: the normalisations of lomb_scargle, by astropy's names
 LS_STANDARD, LS_MODEL, LS_LOG, LS_PSD = range(4)
@@ -337,6 +340,8 @@ def load_library():
     lib.mtg_lomb_scargle_envelope.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, ctypes.POINTER(c_i64), _dp, ctypes.POINTER(c_i64),
                                               _dp, ctypes.POINTER(c_i64), _dp, _dp, ctypes.POINTER(c_i64)]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
+    lib.mtg_whiten.restype = c_int
+    lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
     lib.mtg_gp_cond_draw.restype = c_int
     lib.mtg_gp_cond_draw.argtypes = [c_vp, c_i64, _dp, _ip, c_i64, _dp, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_loglike_grad.restype = c_int
@@ -888,6 +893,34 @@ class Engine:
                                           _ptr(y), _iptr(status)))
         return y, status
 
+    def whiten(self, theta, lc_index=None, y=None, residuals=True, lags=0, stats=True, ks=True):
+        """Whitened (one-step-ahead) residuals q = D^-1/2 L^-1 (y - mean) of B rows, the inverse of ``gp_draw``, and
+        their diagnostics -> (q[B][N] or None, acf[B][lags] or None, stats[B][WHITEN_NSTATS] or None, status[B]).
+        ``y`` [B][N]: data without the per-light-curve y_offset (what ``gp_draw`` returns); None: the resident data of
+        light curve ``lc_index[b]``.  ``lags`` = K >= 1: acf[b][k - 1] = sum_n q_n q_(n+k) / sum_n q_n^2, k = 1 .. K
+        (matplotlib's acorr).  stats: sum q, sum q^2, sum ln D, sum q^3, sum q^4, KS D+, KS D- against the standard
+        normal, max |q| (WHITEN_* index them).  The library forms D+ and D- where the residuals are on the device, that
+        is with ``residuals`` or ``lags``; for the sums alone -- one sweep, nothing of size N stored, NaN in the two
+        slots -- say so with ``ks=False``: without it such a call is refused rather than answered without its KS
+        distances (mtg_whiten).  Rows outside the prior or not positive definite keep their status and read back NaN."""
+        theta = np.atleast_2d(_f64(theta))
+        B = theta.shape[0]
+        lc = None if lc_index is None else np.ascontiguousarray(lc_index, dtype=np.int32)
+        if y is not None:
+            y = _f64(y).reshape(-1, self.N)
+            if y.shape[0] != B:
+                raise ValueError("y must have shape (%d, %d)" % (B, self.N))
+        K = int(lags)
+        if stats and ks and not residuals and K == 0:
+            raise ValueError("the KS distances need residuals=True or lags >= 1; pass ks=False for the sums alone")
+        q = np.full((B, self.N), np.nan) if residuals else None
+        acf = np.full((B, max(K, 1)), np.nan) if K != 0 else None      # (a K out of range is the library's to refuse)
+        st = np.full((B, WHITEN_NSTATS), np.nan) if stats else None
+        status = np.empty(B, dtype=np.int32)
+        self._check(self._lib.mtg_whiten(self._ctx, B, _ptr(theta), _iptr(lc), _ptr(y), _ptr(q), K, _ptr(acf), _ptr(st),
+                                         _iptr(status)))
+        return q, acf, st, status
+
     def gp_cond_draw(self, theta, ts, lc_index=None, seed=0, normals=None):
         """Draws of the process given the data of light curve ``lc_index[b]``, at new times ``ts`` [M] (any order,
         duplicates allowed) -> (y[B][M], status[B]); y excludes the per-light-curve y_offset.  Matheron's rule on the
@@ -1072,6 +1105,6 @@ class Engine:
 
 for _name in ("set_lightcurves", "set_lightcurves_device", "set_model", "loglike", "loglike_device", "loglike_coeffs",
               "ensemble_init", "ensemble_run", "ensemble_restore", "ensemble_state", "chain_autocorr", "simulate_tk95",
-              "tk95_observe_series", "predict", "predict_at", "predict_terms", "gp_draw", "gp_cond_draw", "loglike_grad", "apply_inverse", "math_probe"):
+              "tk95_observe_series", "predict", "predict_at", "predict_terms", "gp_draw", "whiten", "gp_cond_draw", "loglike_grad", "apply_inverse", "math_probe"):
     setattr(Engine, _name, _one_thread_at_a_time(getattr(Engine, _name)))
 del _name

@@ -411,6 +411,18 @@ class GP(ModelSet):
         self._raise_for(status)
         return x
 
+    def whiten(self, y):
+        """Whitened (one-step-ahead) residuals of ``y`` at the current parameters, ``q = D^-1/2 L^-1 (y - mean)`` with
+        ``K = L diag(D) L^T`` -> ``[N]``: ``q_n`` is ``y_n`` minus its prediction from the samples before it, over the
+        standard deviation of that prediction.  Under the model the ``q_n`` are independent standard normals -- what a
+        KS test or an autocorrelation band assumes -- and ``sample`` with the normals ``q`` gives ``y`` back
+        (``Engine.whiten``, O(N J^2) on the device).  Under a profile mean the device sees ``y - mean(t)`` with a zero
+        mean, as in ``predict``."""
+        eng, model, _ = self._mean_engine(y)
+        q, _, _, status = eng.whiten(model.full[model.free_index][None, :], stats=False)
+        self._raise_for(status[0])
+        return q[0]
+
     def sample(self, size=None, seed=None):
         """Realisations of the process at the computed times, ``y ~ N(mean, K)`` with the measurement errors and the
         jitter on the diagonal (celerite.GP.sample -> solver.dot_L): ``[N]`` for ``size=None``, else ``[size][N]``.

@@ -33,6 +33,29 @@ from .sampler import EnsembleSampler
 __all__ = ["GPModelling"]
 
 
+def whiten_diagnostics(stats, acf, N):
+    """The host arithmetic of ``GPModelling.residual_diagnostics``: ``Engine.whiten``'s stats [B][8] and acf [B][K] of
+    series of N samples -> the dict it returns, arrays over the B rows."""
+    from scipy.stats import chi2 as _chi2, kstwo
+    stats, acf = np.atleast_2d(np.asarray(stats, dtype=np.float64)), np.atleast_2d(np.asarray(acf, dtype=np.float64))
+    K = acf.shape[1]
+    s1, s2, s3, s4 = (stats[:, k] for k in (_engine.WHITEN_SUM, _engine.WHITEN_SUM2, _engine.WHITEN_SUM3, _engine.WHITEN_SUM4))
+    ks = np.maximum(stats[:, _engine.WHITEN_KS_PLUS], stats[:, _engine.WHITEN_KS_MINUS])
+    # ks_1samp(method="auto") always takes the exact distribution of the two-sided statistic, and clips
+    pvalue = np.clip(kstwo.sf(ks, N), 0.0, 1.0)
+    # central moments (biased, scipy.stats.skew / kurtosis defaults) from the power sums
+    m = s1 / N
+    m2 = s2 / N - m * m
+    m3 = s3 / N - 3.0 * m * s2 / N + 2.0 * m ** 3
+    m4 = s4 / N - 4.0 * m * s3 / N + 6.0 * m * m * s2 / N - 3.0 * m ** 4
+    lb = N * (N + 2.0) * np.sum(acf * acf / (N - np.arange(1, K + 1, dtype=np.float64))[None, :], axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):      # a constant series has no shape: NaN
+        skewness, kurtosis = m3 / m2 ** 1.5, m4 / (m2 * m2) - 3.0
+    return dict(ks_statistic=ks, ks_pvalue=pvalue, chi2=s2.copy(), skewness=skewness, excess_kurtosis=kurtosis,
+                acf=acf, ljung_box=lb, ljung_box_pvalue=_chi2.sf(lb, K), max_abs=stats[:, _engine.WHITEN_MAXABS].copy(),
+                acf_band=1.96 / np.sqrt(N))
+
+
 class GPModelling:
     """The interface for Gaussian Process (GP) modelling on MI355X."""
 
@@ -353,11 +376,67 @@ class GPModelling:
 
     def standarized_residuals(self, include_noise: bool = True):
         """Standardised residuals (gpmodelling.py:353-370) need ``GP.predict`` -- outside
-        the log-likelihood hot path."""
+        the log-likelihood hot path.  These are smoothing residuals, each sample
+        against its prediction from ALL the data: correlated, and not of unit variance even under the true model; to
+        test for whiteness (KS against the normal, autocorrelation) use ``whitened_residuals``, whose entries are
+        independent standard normals under the model."""
         pred_mean, pred_var = self.gp.predict(self._lightcurve.y, return_var=True, return_cov=False)
         if include_noise:
             pred_var += self.gp.kernel.jitter
         return (self._lightcurve.y - pred_mean) / np.sqrt(pred_var)
+
+    def _whiten_rows(self, parameters, residuals, lags, stats):
+        """``Engine.whiten`` of the light curve at ``parameters`` (as in ``predict_at``) -> (q, acf, stats, one vector?)"""
+        if parameters is None:
+            parameters = self.max_parameters if self._mcmc_samples is not None else self.gp.get_parameter_vector()
+        parameters = np.asarray(parameters, dtype=np.float64)
+        theta = np.atleast_2d(parameters)
+        if self.gp._has_profile_mean():
+            # one vector at a time, as predict_at: the residual y - mean(t) at that vector bound with a zero mean
+            saved = self.gp.get_parameter_vector()
+            try:
+                rows = []
+                for b in range(len(theta)):
+                    self.gp.set_parameter_vector(theta[b])
+                    eng, model, _ = self.gp._mean_engine(self._lightcurve.y)
+                    out = eng.whiten(model.full[model.free_index][None, :], residuals=residuals, lags=lags, stats=stats)
+                    self.gp._raise_for(out[3][0])
+                    rows.append(out[:3])
+            finally:
+                self.gp.set_parameter_vector(saved)
+            q, acf, st = (None if rows[0][k] is None else np.vstack([r[k] for r in rows]) for k in range(3))
+        else:
+            eng, model = self.gp._bound_engine(self._lightcurve.y)
+            q, acf, st, status = eng.whiten(theta, residuals=residuals, lags=lags, stats=stats)
+            for s in status:
+                self.gp._raise_for(s)
+        return q, acf, st, parameters.ndim == 1
+
+    def whitened_residuals(self, parameters=None):
+        """Whitened (one-step-ahead) residuals of the light curve, ``q_n = (y_n - E[y_n | y_1 .. y_n-1]) /
+        sqrt(Var[y_n | y_1 .. y_n-1])`` (Kelly et al. 2014; ``GP.whiten``): independent standard normals under the model,
+        so that ``ks_1samp(q, norm.cdf)`` and ``plt.acorr(q)`` test what they claim to.  ``parameters`` as in
+        ``predict_at``: None -- the maximum-posterior sample if posteriors were derived, else the GP's current vector
+        -- or one vector [P], or [B][P] posterior samples, evaluated in one launch.  Returns [N] or [B][N]."""
+        q, _, _, one = self._whiten_rows(parameters, True, 0, False)
+        return q[0] if one else q
+
+    def residual_diagnostics(self, parameters=None, lags=None):
+        """Goodness of fit of the whitened residuals at ``parameters`` (as in ``whitened_residuals``), computed on the
+        device next to the light curve -- only [B] and [B][lags] numbers come back -> a dict of arrays over the B rows
+        (scalars and [lags] for one vector): ``ks_statistic`` and ``ks_pvalue`` (scipy's ``ks_1samp(q, norm.cdf)``),
+        ``chi2`` = sum q^2, ``skewness``, ``excess_kurtosis``, ``acf`` at lags 1 .. ``lags`` (``plt.acorr``'s
+        definition; None: N // 4, the tutorial's), ``ljung_box`` = N (N + 2) sum_k acf_k^2 / (N - k) with its chi^2
+        p-value ``ljung_box_pvalue``, ``max_abs``, and the 95 per cent band of a white series ``acf_band`` =
+        1.96 / sqrt(N).  The KS p-value is the textbook one: it is biased towards large values once parameters were
+        fitted to the same data, so compare it over posterior samples or simulated light curves, not to 0.05."""
+        N = len(self._lightcurve.times)
+        K = N // 4 if lags is None else int(lags)
+        if K < 1:
+            raise ValueError("lags must be at least 1")
+        _, acf, st, one = self._whiten_rows(parameters, False, K, True)
+        out = whiten_diagnostics(st, acf, N)
+        return {k: (v[0] if one and np.ndim(v) > 0 else v) for k, v in out.items()}
 
     def predict_at(self, times, parameters=None, include_noise: bool = False):
         """Model curve and its variance at ``times`` [M] (new; celerite users loop ``gp.predict(y, t, return_var=True)``
