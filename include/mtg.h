@@ -712,6 +712,31 @@ MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs /* [F]
                              double *peak_power /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
 
 /*
+ * mtg_lomb_scargle with nterms = K phase-tied harmonics per frequency: astropy's LombScargle(fit_mean=True,
+ * center_data=True, nterms=K).power(freqs, method="chi2"), the batched form of fitting a profile that is not a sinusoid
+ * (eclipses, pulses, QPO harmonics).  Weights, ybar, r and YY as above; with phi_n = 2 pi f (t_n - t_0) and the design row
+ *   x_n = (1, sin phi_n, cos phi_n, ..., sin K phi_n, cos K phi_n),   A = sum w x x^T,   b = sum w r x,   p = b^T A^-1 b
+ * and the four normalizations applied to p as above.  b_0 = sum w r is zero, so the bias column is eliminated first (the
+ * Schur complement A_hh - h h^T, the step CC = sum w c^2 - C^2 above) and the 2K x 2K rest is factored by Cholesky;
+ * for K = 1 this is algebraically the formula above.  Every entry of A is half a sum or difference of
+ * C_m = sum w cos m phi and S_m = sum w sin m phi, m <= 2 K: a lane accumulates those 4 K sums and 2 K data sums per light
+ * curve.  The base pair (cos phi, sin phi) is mtg_lomb_scargle's bit for bit; harmonic m follows from harmonic m - 1 by
+ * one complex multiplication by it.  Against a 50-digit evaluation the standard power is within
+ * max(10 rho, 64 sqrt(N) u kappa), kappa the 2-norm condition number of A (tests/test_lomb_scargle_multi_gpu.py).
+ *   nterms == 1 runs mtg_lomb_scargle's kernel: the result is mtg_lomb_scargle's bit for bit.
+ * Outputs, slabs, peak reduction and invariance as for mtg_lomb_scargle: power[l][k] depends on (light curve l, freqs[k],
+ * nterms, normalization, weighted) alone, bit for bit.  A frequency at which a pivot of the factorisation is not positive
+ * gives NaN in that entry.  Errors as for mtg_lomb_scargle, and MTG_E_ARG for nterms outside 1 .. MTG_LS_MAX_TERMS and for
+ * N < 2 nterms + 2 (2 nterms + 1 samples are fitted exactly).  mtg_last_solver names "mtg_lomb_scargle_multi_kernel<K,R>"
+ * (R light curves per lane: csrc/mtg_ls_multi_plan.h), or mtg_lomb_scargle's kernel for nterms == 1.
+ */
+enum { MTG_LS_MAX_TERMS = 5 };   /* (not one of the MTG_LS_* normalization macros) */
+MTG_API int mtg_lomb_scargle_multi(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host, cycles per unit time */,
+                                   int nterms /* 1 .. MTG_LS_MAX_TERMS */, int normalization, int weighted,
+                                   double *power /* [L][F] host, or NULL */,
+                                   double *peak_power /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
+
+/*
  * What the periodograms of the resident set say about every frequency: reductions of power[l][k] ACROSS the light
  * curves, without the [L][F] array ever leaving the device.  power[l][k] is, by definition and bit for bit, what
  * mtg_lomb_scargle returns for the same resident set, frequency, normalization and weighting (its launcher computes it).
@@ -743,6 +768,19 @@ MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *fre
                                       const double *scale /* [F] host, finite and > 0, or NULL */,
                                       double *peak_ratio /* [L] or NULL, needs scale */,
                                       int64_t *peak_ratio_index /* [L] or NULL, needs scale */);
+/*
+ * mtg_lomb_scargle_envelope of the periodogram with nterms harmonics: power[l][k] is mtg_lomb_scargle_multi's bit for bit,
+ * everything after the powers (slabs, column sort, exceedance, ratio peaks) is mtg_lomb_scargle_envelope's; nterms and N
+ * are checked as mtg_lomb_scargle_multi checks them.
+ */
+MTG_API int mtg_lomb_scargle_envelope_multi(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host */,
+                                            int nterms /* 1 .. MTG_LS_MAX_TERMS */, int normalization, int weighted,
+                                            int Q, const int64_t *ranks /* [Q] host */, double *order_stat /* [Q][F] host */,
+                                            int64_t *valid /* [F] or NULL */, const double *reference /* [F] host, or NULL */,
+                                            int64_t *exceed /* [F] or NULL, needs reference */,
+                                            const double *scale /* [F] host, or NULL */,
+                                            double *peak_ratio /* [L] or NULL, needs scale */,
+                                            int64_t *peak_ratio_index /* [L] or NULL, needs scale */);
 
 /*
  * Accuracy probe of the device elementary functions the recurrence uses

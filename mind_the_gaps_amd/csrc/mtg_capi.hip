@@ -2500,25 +2500,47 @@ MTG_API int mtg_predict_terms(mtg_ctx *ctx, int64_t B, const double *theta, cons
     return c.finish(status);
 }
 
-MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, double *power,
-                             double *peak_power, int64_t *peak_index)
+// what the periodogram entries refuse about the number of harmonics and of samples (MTG_OK: nothing): K harmonics with a
+// floating mean fit 2 K + 1 samples exactly
+static int ls_refuse_terms(mtg_ctx *ctx, const char *who, int nterms, int64_t N)
 {
-    RowCall c{ctx, "mtg_lomb_scargle", 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    if (nterms < 1 || nterms > MTG_LS_MAX_TERMS)
+        return fail(ctx, MTG_E_ARG, "%s: nterms = %d is outside 1 .. %d", who, nterms, MTG_LS_MAX_TERMS);
+    if (nterms == 1 && N < 4)
+        return fail(ctx, MTG_E_ARG, "%s: N = %lld < 4 samples (a sinusoid with a floating mean fits three exactly)", who, (long long)N);
+    if (N < 2 * nterms + 2)
+        return fail(ctx, MTG_E_ARG, "%s: N = %lld < %d samples (%d harmonics with a floating mean fit %d exactly)", who, (long long)N,
+                    2 * nterms + 2, nterms, 2 * nterms + 1);
+    return MTG_OK;
+}
+
+// the kernel that computes the powers, as mtg_last_solver names it
+static void ls_kernel_name(char *out, size_t n, int nterms, int R)
+{
+    if (nterms == 1) snprintf(out, n, "mtg_lomb_scargle_kernel<%d>", R);
+    else snprintf(out, n, "mtg_lomb_scargle_multi_kernel<%d,%d>", nterms, R);
+}
+
+// mtg_lomb_scargle (nterms = 1) and mtg_lomb_scargle_multi
+static int lomb_scargle_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization, int weighted,
+                              double *power, double *peak_power, int64_t *peak_index)
+{
+    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
     int rc = c.ready(false);
     if (rc) return rc;
-    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: need F >= 1 frequencies");
-    if (!power && !peak_power && !peak_index) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: power, peak_power and peak_index are all NULL");
+    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
+    if (!power && !peak_power && !peak_index) return fail(ctx, MTG_E_ARG, "%s: power, peak_power and peak_index are all NULL", who);
     if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
-        return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: unknown normalization %d", normalization);
+        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
     const int64_t N = ctx->N, L = ctx->L;
-    if (N < 4) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: N = %lld < 4 samples (a sinusoid with a floating mean fits three exactly)", (long long)N);
+    if ((rc = ls_refuse_terms(ctx, who, nterms, N))) return rc;
     for (int64_t k = 0; k < F; ++k)
         if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
-            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle: freqs[%lld] = %g is not a finite positive frequency", (long long)k, freqs[k]);
+            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
     if ((rc = c.begin(false))) return rc;
     // the powers of a slab of light curves at a time: <= 256 MiB of workspace whatever L F is
     int64_t Ls = ((int64_t)1 << 25) / F;
-    const int R = mtg_lomb_scargle_tile(L, !ctx->t_per_lc, weighted);
+    const int R = nterms == 1 ? mtg_lomb_scargle_tile(L, !ctx->t_per_lc, weighted) : mtg_ls_multi_tile(nterms, L, !ctx->t_per_lc, weighted);
     Ls = Ls / R * R;   // whole tiles (a light curve's power does not depend on its tile: this only fills the lanes)
     if (Ls < R) Ls = R;
     if (Ls > L) Ls = L;
@@ -2530,10 +2552,10 @@ MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs, int n
     c.upload(d_freqs.p, freqs, (size_t)F * 8);
     qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
     qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.L = L;
-    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization;
+    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization; qa.nterms = nterms;
     qa.stats = d_stats.as<double>(); qa.F = F; qa.freqs = d_freqs.as<double>(); qa.power = d_power.as<double>();
     qa.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
-    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_lomb_scargle_kernel<%d>", R);
+    ls_kernel_name(ctx->last_solver, sizeof ctx->last_solver, nterms, R);
     c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
     c.then([&] {
         mtg_launch_lomb_scargle_stats(qa, c.s);
@@ -2552,37 +2574,51 @@ MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs, int n
     return c.finish(nullptr);
 }
 
-MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, int Q,
-                                      const int64_t *ranks, double *order_stat, int64_t *valid, const double *reference,
-                                      int64_t *exceed, const double *scale, double *peak_ratio, int64_t *peak_ratio_index)
+MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, double *power,
+                             double *peak_power, int64_t *peak_index)
 {
-    RowCall c{ctx, "mtg_lomb_scargle_envelope", 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    return lomb_scargle_entry(ctx, "mtg_lomb_scargle", F, freqs, 1, normalization, weighted, power, peak_power, peak_index);
+}
+
+MTG_API int mtg_lomb_scargle_multi(mtg_ctx *ctx, int64_t F, const double *freqs, int nterms, int normalization, int weighted,
+                                   double *power, double *peak_power, int64_t *peak_index)
+{
+    return lomb_scargle_entry(ctx, "mtg_lomb_scargle_multi", F, freqs, nterms, normalization, weighted, power, peak_power, peak_index);
+}
+
+// mtg_lomb_scargle_envelope (nterms = 1) and mtg_lomb_scargle_envelope_multi
+static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization,
+                                       int weighted, int Q, const int64_t *ranks, double *order_stat, int64_t *valid,
+                                       const double *reference, int64_t *exceed, const double *scale, double *peak_ratio,
+                                       int64_t *peak_ratio_index)
+{
+    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
     int rc = c.ready(false);
     if (rc) return rc;
-    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: need F >= 1 frequencies");
+    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
     if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
-        return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: unknown normalization %d", normalization);
+        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
     const int64_t N = ctx->N, L = ctx->L;
-    if (N < 4) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: N = %lld < 4 samples (a sinusoid with a floating mean fits three exactly)", (long long)N);
+    if ((rc = ls_refuse_terms(ctx, who, nterms, N))) return rc;
     for (int64_t k = 0; k < F; ++k)
         if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
-            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: freqs[%lld] = %g is not a finite positive frequency", (long long)k, freqs[k]);
-    if (Q < 0 || (Q > 0 && !ranks)) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: Q = %d ranks%s", Q, Q < 0 ? "" : ", ranks is NULL");
-    if (Q > 0 && !order_stat) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: Q = %d ranks, order_stat is NULL", Q);
+            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    if (Q < 0 || (Q > 0 && !ranks)) return fail(ctx, MTG_E_ARG, "%s: Q = %d ranks%s", who, Q, Q < 0 ? "" : ", ranks is NULL");
+    if (Q > 0 && !order_stat) return fail(ctx, MTG_E_ARG, "%s: Q = %d ranks, order_stat is NULL", who, Q);
     for (int q = 0; q < Q; ++q)
         if (ranks[q] < 0 || ranks[q] >= L)
-            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: ranks[%d] = %lld is outside [0, L = %lld)", q, (long long)ranks[q], (long long)L);
-    if (exceed && !reference) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: exceed needs reference");
+            return fail(ctx, MTG_E_ARG, "%s: ranks[%d] = %lld is outside [0, L = %lld)", who, q, (long long)ranks[q], (long long)L);
+    if (exceed && !reference) return fail(ctx, MTG_E_ARG, "%s: exceed needs reference", who);
     const bool want_ratio = peak_ratio || peak_ratio_index, want_columns = Q > 0 || valid || exceed;
-    if (want_ratio && !scale) return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: peak_ratio and peak_ratio_index need scale");
+    if (want_ratio && !scale) return fail(ctx, MTG_E_ARG, "%s: peak_ratio and peak_ratio_index need scale", who);
     if (!want_columns && !want_ratio)
-        return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: order_stat, valid, exceed, peak_ratio and peak_ratio_index are all NULL");
+        return fail(ctx, MTG_E_ARG, "%s: order_stat, valid, exceed, peak_ratio and peak_ratio_index are all NULL", who);
     for (int64_t k = 0; reference && k < F; ++k)
         if (!std::isfinite(reference[k]))
-            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: reference[%lld] = %g is not finite", (long long)k, reference[k]);
+            return fail(ctx, MTG_E_ARG, "%s: reference[%lld] = %g is not finite", who, (long long)k, reference[k]);
     for (int64_t k = 0; scale && k < F; ++k)
         if (!std::isfinite(scale[k]) || !(scale[k] > 0.0))
-            return fail(ctx, MTG_E_ARG, "mtg_lomb_scargle_envelope: scale[%lld] = %g is not finite and positive", (long long)k, scale[k]);
+            return fail(ctx, MTG_E_ARG, "%s: scale[%lld] = %g is not finite and positive", who, (long long)k, scale[k]);
     if ((rc = c.begin(false))) return rc;
     // a slab of frequencies at a time, every light curve's power at them: mtg_ls_envelope_plan.h
     const int64_t Fs = mtg_lse_slab_width(L, F, Q, MTG_LSE_BUDGET);
@@ -2603,7 +2639,7 @@ MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *fre
     if (want_ratio) c.upload(d_scale.p, scale, (size_t)F * 8);
     qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
     qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.L = L;
-    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization;
+    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization; qa.nterms = nterms;
     qa.stats = d_stats.as<double>(); qa.power = d_power.as<double>();
     qa.peak_power = nullptr; qa.peak_index = nullptr;
     ea.slab = d_power.as<double>(); ea.L = L; ea.Q = Q; ea.ranks = d_ranks.as<int64_t>(); ea.order_stat = d_os.as<double>();
@@ -2639,6 +2675,22 @@ MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *fre
     if (peak_ratio) c.gather(peak_ratio, d_peak.p, (size_t)L * 8);
     if (peak_ratio_index) c.gather(peak_ratio_index, d_index.p, (size_t)L * 8);
     return c.finish(nullptr);
+}
+
+MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, int Q,
+                                      const int64_t *ranks, double *order_stat, int64_t *valid, const double *reference,
+                                      int64_t *exceed, const double *scale, double *peak_ratio, int64_t *peak_ratio_index)
+{
+    return lomb_scargle_envelope_entry(ctx, "mtg_lomb_scargle_envelope", F, freqs, 1, normalization, weighted, Q, ranks, order_stat,
+                                       valid, reference, exceed, scale, peak_ratio, peak_ratio_index);
+}
+
+MTG_API int mtg_lomb_scargle_envelope_multi(mtg_ctx *ctx, int64_t F, const double *freqs, int nterms, int normalization, int weighted,
+                                            int Q, const int64_t *ranks, double *order_stat, int64_t *valid, const double *reference,
+                                            int64_t *exceed, const double *scale, double *peak_ratio, int64_t *peak_ratio_index)
+{
+    return lomb_scargle_envelope_entry(ctx, "mtg_lomb_scargle_envelope_multi", F, freqs, nterms, normalization, weighted, Q, ranks,
+                                       order_stat, valid, reference, exceed, scale, peak_ratio, peak_ratio_index);
 }
 
 MTG_API int mtg_gp_draw(mtg_ctx *ctx, int64_t B, const double *theta, const int32_t *lc_index, uint64_t seed,

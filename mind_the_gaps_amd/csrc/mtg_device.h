@@ -276,6 +276,7 @@ struct MtgLombScargleArgs {
     const double2 *dxt, *yv;
     int64_t N, t_stride, L;   // the resident set: t_stride 0 (shared sampling) or N
     int weighted, normalization;
+    int nterms;               // harmonics K: 1 (mtg_lomb_scargle_kernel) or 2 .. MTG_LS_MAX_TERMS (mtg_lomb_scargle_multi_kernel)
     double *stats;            // [L][4]: ybar, YY, sum sigma^-2 (or N), 0
     int64_t F;
     const double *freqs;      // [F] on the device
@@ -289,6 +290,11 @@ void mtg_launch_lomb_scargle_stats(const MtgLombScargleArgs &, hipStream_t);
 int mtg_launch_lomb_scargle(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, hipStream_t);
 // light curves per lane for a set of L (1, 4, or the full tile of the weighting)
 int mtg_lomb_scargle_tile(int64_t L, int shared_sampling, int weighted);
+// ... and with K >= 2 harmonics: mtg_ls_multi_tile(K, L, shared_sampling, weighted)
+#include "mtg_ls_multi_plan.h"
+// the powers of one slab with nterms >= 2 (mtg_lomb_scargle_multi.hip; mtg_launch_lomb_scargle dispatches to it and adds
+// the peaks; 0 = more workgroups than a grid holds)
+int mtg_launch_lomb_scargle_multi_powers(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, hipStream_t);
 
 // One slab of mtg_lomb_scargle_envelope (mtg_lomb_scargle_envelope.hip; the cutting rules: mtg_ls_envelope_plan.h): the
 // powers of all L light curves at the Fs frequencies from k0 on, as mtg_launch_lomb_scargle left them

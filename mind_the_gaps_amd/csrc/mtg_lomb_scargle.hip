@@ -29,43 +29,9 @@
 // frequencies, or on how the sampling is stored.
 #include "mtg_device.h"
 #include "mtg_math.h"
-
-#ifndef MTG_LS_CHUNK
-#define MTG_LS_CHUNK 256
-#endif
-#define MTG_LS_THREADS 256
+#include "mtg_ls_phase.h"
 
 namespace {
-
-struct MtgLsTab {
-    double2 cis[MTG_TRIG_N];   // (cos, sin)(2 pi j / N): the table of mtg_math.h
-};
-
-// (sin, cos) of 2 pi f te with the phase formed in cycles.  The product is taken exactly, f te = p + pe (one fma); the
-// integer part of p is dropped before anything is rounded (p - rint(p) is exact), the fraction q in [-1/2, 1/2] is
-// split into m = rint(q N) table steps and a remainder (exact again: both are multiples of ulp(p) below 2^-1), the low
-// part of the product joins the remainder, and only then comes the factor 2 pi -- on |x| <= pi / N, where its rounding
-// is 1e-19 rad.  What is left is the rounding of te itself.  The table index is masked as in mtg_abs_sincos
-// (mtg_sweep_mean.h): whatever f te is, the load stays inside the table.
-template <class Tab>
-__device__ __forceinline__ void mtg_cycles_sincos(double f, double te, double *sn, double *cs, const Tab *tab)
-{
-#pragma clang fp contract(off)
-    const double magic = 0x1.8p+56;                                                 // 1.5 * 2^(52+4)
-    const double p = f * te;
-    const double pe = __builtin_fma(f, te, -p);
-    const double q = p - __builtin_rint(p);
-    const double wk = __builtin_fma(q, 16.0 * MTG_TRIG_N, magic);                   // q 16 N
-    const double md16 = wk - magic;                                                 // 16 m
-    const double rc = __builtin_fma(md16, -(1.0 / (16.0 * MTG_TRIG_N)), q) + pe;    // cycles, |rc| <= 1 / 2N
-    const double r = rc * 0x1.921fb54442d18p+2;                                     // 2 pi
-    const int m16 = __double2loint(wk) << 4;                                        // low mantissa dword of wk = m
-    const double2 cj = *(const double2 *)((const char *)tab->cis + (m16 & ((MTG_TRIG_N - 1) * 16)));
-    double s, c;
-    mtg_sincos_small(r, &s, &c);
-    *sn = __builtin_fma(cj.x, s, cj.y * c);
-    *cs = __builtin_fma(-cj.y, s, cj.x * c);
-}
 
 // sum of v over the workgroup in a fixed order (thread-strided partial sums, then a binary tree): `red` holds
 // MTG_LS_THREADS doubles
@@ -159,11 +125,7 @@ mtg_lomb_scargle_kernel(const MtgLsArgs a)
     __shared__ double2 col_s[NP * CH];
 
     const int tid = threadIdx.x, nth = blockDim.x;
-    for (int j = tid; j < MTG_TRIG_N; j += nth) {
-        double s, c;
-        sincospi((double)j * (2.0 / MTG_TRIG_N), &s, &c);
-        tab.cis[j] = make_double2(c, s);
-    }
+    mtg_ls_fill_tab(&tab);
     const int64_t tile = blockIdx.x / a.nfb;
     const int fb = (int)(blockIdx.x - tile * a.nfb);
     const int64_t lt = a.l0 + tile * R;                 // first light curve of the tile
@@ -316,6 +278,14 @@ void ls_launch(const MtgLsArgs &a, int64_t blocks, int threads, hipStream_t s)
     hipLaunchKernelGGL((mtg_lomb_scargle_kernel<R, WEIGHTED>), dim3((unsigned)blocks), dim3(threads), 0, s, a);
 }
 
+// the peaks of the slab's rows, where asked for
+void ls_launch_peaks(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls, hipStream_t s)
+{
+    if (q.peak_power || q.peak_index)
+        hipLaunchKernelGGL(mtg_lomb_scargle_peak_kernel, dim3((unsigned)Ls), dim3(MTG_LS_THREADS), 0, s, q.power, q.F,
+                           q.peak_power ? q.peak_power + l0 : nullptr, q.peak_index ? q.peak_index + l0 : nullptr);
+}
+
 }  // namespace
 
 int mtg_lomb_scargle_tile(int64_t L, int shared_sampling, int weighted)
@@ -333,6 +303,11 @@ void mtg_launch_lomb_scargle_stats(const MtgLombScargleArgs &q, hipStream_t s)
 
 int mtg_launch_lomb_scargle(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls, hipStream_t s)
 {
+    if (q.nterms > 1) {   // the powers with harmonics come from mtg_lomb_scargle_multi.hip; the peaks are reduced here
+        if (!mtg_launch_lomb_scargle_multi_powers(q, l0, Ls, s)) return 0;
+        ls_launch_peaks(q, l0, Ls, s);
+        return 1;
+    }
     const int R = mtg_lomb_scargle_tile(q.L, q.t_stride == 0, q.weighted);
     // narrow frequency lists leave most of a wide workgroup idle: one or two waves then (the arithmetic of a lane is the same)
     const int threads = q.F <= 64 ? 64 : q.F <= 128 ? 128 : MTG_LS_THREADS;
@@ -352,8 +327,6 @@ int mtg_launch_lomb_scargle(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls,
         else if (R == 4) ls_launch<4, false>(a, blocks, threads, s);
         else ls_launch<MTG_LS_R_UNWEIGHTED, false>(a, blocks, threads, s);
     }
-    if (q.peak_power || q.peak_index)
-        hipLaunchKernelGGL(mtg_lomb_scargle_peak_kernel, dim3((unsigned)Ls), dim3(MTG_LS_THREADS), 0, s, q.power, q.F,
-                           q.peak_power ? q.peak_power + l0 : nullptr, q.peak_index ? q.peak_index + l0 : nullptr);
+    ls_launch_peaks(q, l0, Ls, s);
     return 1;
 }

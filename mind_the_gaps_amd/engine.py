@@ -42,6 +42,7 @@ EXPORTS = (
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
     "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope", "mtg_whiten",
+    "mtg_lomb_scargle_multi", "mtg_lomb_scargle_envelope_multi",
 )
 
 # include/mtg.h, MTG_WHITEN_NSTATS and the slots of a row of whiten's stats
@@ -51,6 +52,7 @@ TERMS_MEAN = 1 << 31   # include/mtg.h, MTG_TERMS_MEAN: a mask of predict_terms 
 # include/mtg.h, MTG_LS_*: the normalisations of lomb_scargle, by astropy's names
 LS_STANDARD, LS_MODEL, LS_LOG, LS_PSD = range(4)
 LS_NORMALIZATIONS = {"standard": LS_STANDARD, "model": LS_MODEL, "log": LS_LOG, "psd": LS_PSD}
+LS_MAX_TERMS = 5   # include/mtg.h, MTG_LS_MAX_TERMS: the harmonics of lomb_scargle(nterms=...)
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -339,6 +341,11 @@ def load_library():
     lib.mtg_lomb_scargle_envelope.restype = c_int
     lib.mtg_lomb_scargle_envelope.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, ctypes.POINTER(c_i64), _dp, ctypes.POINTER(c_i64),
                                               _dp, ctypes.POINTER(c_i64), _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lomb_scargle_multi.restype = c_int
+    lib.mtg_lomb_scargle_multi.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lomb_scargle_envelope_multi.restype = c_int
+    lib.mtg_lomb_scargle_envelope_multi.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64), _dp,
+                                                    ctypes.POINTER(c_i64), _dp, ctypes.POINTER(c_i64), _dp, _dp, ctypes.POINTER(c_i64)]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_whiten.restype = c_int
     lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
@@ -811,13 +818,15 @@ class Engine:
                                                 _ptr(mu), _ptr(var), _iptr(status)))
         return mu, var, status
 
-    def lomb_scargle(self, freqs, normalization="standard", weighted=True, power=True, peak=False):
+    def lomb_scargle(self, freqs, normalization="standard", weighted=True, power=True, peak=False, nterms=1):
         """Generalised (floating-mean) Lomb-Scargle periodogram of every resident light curve at ``freqs`` [F] (cycles per
         unit of time): astropy's ``LombScargle(t, y, dy, normalization=...).power(freqs)`` with its defaults
         ``fit_mean=True, center_data=True, nterms=1``; ``weighted=False`` is ``dy=None``.  -> ``power`` [L][F], and / or
         with ``peak`` ``(peak_power[L], peak_index[L])``: the maximum of every row and the first index attaining it,
         reduced on the device -- with ``power=False`` nothing of size L F comes back.  Both asked for: a tuple
-        ``(power, peak_power, peak_index)``.  A model need not be set (mtg_lomb_scargle)."""
+        ``(power, peak_power, peak_index)``.  ``nterms`` = K in 1 .. 5: K phase-tied harmonics per frequency, astropy's
+        ``nterms=K`` (its ``chi2`` method; mtg_lomb_scargle_multi), for signals that are not sinusoidal; it needs
+        N >= 2 K + 2 samples.  A model need not be set (mtg_lomb_scargle)."""
         freqs = _f64(np.atleast_1d(freqs)).ravel()
         if isinstance(normalization, str):
             if normalization not in LS_NORMALIZATIONS:
@@ -827,15 +836,20 @@ class Engine:
         out = np.full((L, F), np.nan) if power else None
         pk = np.full(L, np.nan) if peak else None
         ix = np.full(L, -1, dtype=np.int64) if peak else None
-        self._check(self._lib.mtg_lomb_scargle(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), _ptr(out),
-                                               _ptr(pk), None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        outputs = (_ptr(out), _ptr(pk), None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        if nterms == 1:
+            self._check(self._lib.mtg_lomb_scargle(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), *outputs))
+        else:
+            self._check(self._lib.mtg_lomb_scargle_multi(self._ctx, F, _ptr(freqs), int(nterms), int(normalization),
+                                                         int(bool(weighted)), *outputs))
         if power and peak:
             return out, pk, ix
         return out if power else (pk, ix)
 
-    def lomb_scargle_envelope(self, freqs, ranks=(), reference=None, scale=None, normalization="standard", weighted=True):
+    def lomb_scargle_envelope(self, freqs, ranks=(), reference=None, scale=None, normalization="standard", weighted=True, nterms=1):
         """What the periodograms of the resident set say about every frequency, reduced ACROSS the light curves on the
-        device; ``power[l][k]`` below is ``lomb_scargle(freqs, normalization, weighted)`` bit for bit and never comes back.
+        device; ``power[l][k]`` below is ``lomb_scargle(freqs, normalization, weighted, nterms=nterms)`` bit for bit and
+        never comes back.
         -> ``LombScargleEnvelope(order_stat, valid, exceed, peak_ratio, peak_ratio_index)``, ``None`` where not asked for:
 
         * ``ranks`` [Q] (each in [0, L), any order, duplicates allowed): ``order_stat[q][k]``, the element of rank
@@ -870,9 +884,12 @@ class Engine:
             if len(scale) != F:
                 raise ValueError("scale must have one entry per frequency")
             pk, ix = np.full(L, np.nan), np.full(L, -1, dtype=np.int64)
-        self._check(self._lib.mtg_lomb_scargle_envelope(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), Q,
-                                                        ip(ranks) if Q else None, _ptr(order_stat), ip(nvalid), _ptr(reference),
-                                                        ip(exceed), _ptr(scale), _ptr(pk), ip(ix)))
+        rest = (Q, ip(ranks) if Q else None, _ptr(order_stat), ip(nvalid), _ptr(reference), ip(exceed), _ptr(scale), _ptr(pk), ip(ix))
+        if nterms == 1:
+            self._check(self._lib.mtg_lomb_scargle_envelope(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), *rest))
+        else:
+            self._check(self._lib.mtg_lomb_scargle_envelope_multi(self._ctx, F, _ptr(freqs), int(nterms), int(normalization),
+                                                                  int(bool(weighted)), *rest))
         return LombScargleEnvelope(order_stat, nvalid, exceed, pk, ix)
 
     def gp_draw(self, theta, lc_index=None, seed=0, normals=None):

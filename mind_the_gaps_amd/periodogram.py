@@ -1,6 +1,7 @@
 """Lomb-Scargle periodogram on the device: the part of ``astropy.timeseries.LombScargle`` the reference's workflow uses
 (``lomb_scargle_biases.ipynb``: ``LombScargle(t, y, fit_mean=True, nterms=1, center_data=True, normalization=...)`` and
-``.power(frequencies)``), for one light curve or for a whole set on shared sampling in one call.
+``.power(frequencies)``), for one light curve or for a whole set on shared sampling in one call -- and ``nterms`` up to 5 (not 2: see the class),
+the batched form of the reference's ``utils.fit_sines`` (phase-tied harmonics at one frequency) over a frequency grid.
 
 ``envelope_ranks`` / ``envelope_levels`` turn the order statistics of ``Engine.lomb_scargle_envelope`` into the quantiles
 ``np.quantile(power, levels, axis=0)`` would give, without the [L][F] power array.
@@ -10,7 +11,7 @@ The periodogram is the generalised (floating-mean) one of Zechmeister & Kuerster
 """
 import numpy as np
 
-from .engine import LS_NORMALIZATIONS
+from .engine import LS_MAX_TERMS, LS_NORMALIZATIONS
 
 __all__ = ["LombScargle", "envelope_ranks", "envelope_levels"]
 
@@ -19,13 +20,19 @@ class LombScargle:
     """``LombScargle(t, y, dy=None, fit_mean=True, center_data=True, nterms=1, normalization="standard")``.
 
     ``t`` [N] (ascending), ``y`` [N] or [L][N] (L light curves on the sampling ``t``), ``dy`` None (unweighted), a scalar,
-    [N] or [L][N].  Only astropy's defaults ``fit_mean=True, center_data=True, nterms=1`` exist on the device; anything
-    else raises ``NotImplementedError``."""
+    [N] or [L][N].  ``nterms`` = 1, 3, 4 or 5 harmonics (beyond one: astropy's ``chi2`` method, N >= 2 nterms + 2 samples);
+    ``nterms=2`` raises ``NotImplementedError`` here and runs through ``Engine.lomb_scargle(nterms=2)``.  Only astropy's
+    defaults ``fit_mean=True, center_data=True`` exist on the device; anything else raises ``NotImplementedError``."""
 
     def __init__(self, t, y, dy=None, fit_mean=True, center_data=True, nterms=1, normalization="standard", device=0):
-        for name, value, only in (("fit_mean", fit_mean, True), ("center_data", center_data, True), ("nterms", nterms, 1)):
+        for name, value, only in (("fit_mean", fit_mean, True), ("center_data", center_data, True)):
             if value != only:
                 raise NotImplementedError("LombScargle(%s=%r): only %s=%r runs on the device" % (name, value, name, only))
+        if nterms == 2:
+            raise NotImplementedError("LombScargle(nterms=2): this class takes nterms = 1, 3, 4, 5; two harmonics run through "
+                                      "Engine.lomb_scargle(nterms=2)")
+        if nterms not in range(1, LS_MAX_TERMS + 1):
+            raise NotImplementedError("LombScargle(nterms=%r): nterms = 1 .. %d run on the device" % (nterms, LS_MAX_TERMS))
         if normalization not in LS_NORMALIZATIONS:
             raise ValueError("normalization must be one of %s" % sorted(LS_NORMALIZATIONS))
         self.t = np.ascontiguousarray(t, dtype=np.float64)
@@ -34,6 +41,7 @@ class LombScargle:
             raise ValueError("t must be [N] and y [N] or [L][N]")
         self.dy = None if dy is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dy, dtype=np.float64), self.y.shape))
         self.normalization = normalization
+        self.nterms = int(nterms)
         self.device = device
 
     def autofrequency(self, samples_per_peak=5, nyquist_factor=5, minimum_frequency=None, maximum_frequency=None):
@@ -61,7 +69,7 @@ class LombScargle:
         """The periodogram at ``frequency`` (cycles per unit of ``t``) -> [F], or [L][F] for a set."""
         frequency = np.asarray(frequency, dtype=np.float64)
         out = self._bound_engine().lomb_scargle(frequency.ravel(), normalization=normalization or self.normalization,
-                                                weighted=self.dy is not None)
+                                                weighted=self.dy is not None, nterms=self.nterms)
         return out.reshape(self.y.shape[:-1] + frequency.shape)
 
     def autopower(self, **kwargs):

@@ -568,7 +568,7 @@ def protassov_test(lightcurve, null_kernel, alt_kernel, nsims=100, walkers=12, m
 
 def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walkers=12, max_steps=500, sigma_noise=None,
                           extension_factor=2, normalization="standard", weighted=True, seed=None, device=0, progress=False,
-                          pdf="Gaussian", max_iter=400):
+                          pdf="Gaussian", max_iter=400, nterms=1):
     """The classic companion of the LRT p-value of ``protassov_test``: is the highest Lomb-Scargle peak of the observed
     light curve unusual among light curves of the null model?
 
@@ -582,21 +582,29 @@ def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walke
     samples[nsims][P], sim_seed, lightcurves) -- the last three are what step 2 drew and made.  One GPU.  Every random number
     comes from ``default_rng(seed)`` in a fixed order (the chain's seed, the picks, the simulator's seed): the same seed gives
     the same result bit for bit.  ``weighted``: by the error bars, the simulated light curves' own included -- Poisson noise
-    at a few counts per epoch leaves epochs with ``dy = 0`` that take all the weight; pass ``weighted=False`` there."""
+    at a few counts per epoch leaves epochs with ``dy = 0`` that take all the weight; pass ``weighted=False`` there.
+    ``nterms``: harmonics per frequency of every periodogram (``Engine.lomb_scargle``), for profiles that are not sinusoidal."""
     frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
     eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
                                                            extension_factor, seed, device, progress, pdf, max_iter)
-    sim_peaks, _ = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted, power=False, peak=True)
+    harmonics = _harmonics(nterms)
+    sim_peaks, _ = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted, power=False, peak=True, **harmonics)
     y = np.asarray(lightcurve.y, dtype=np.float64)
     dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
     eng.set_lightcurves(np.asarray(lightcurve.times, dtype=np.float64), y, dy)
     eng.bound_to = None
     obs, at = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None,
-                               power=False, peak=True)
+                               power=False, peak=True, **harmonics)
     observed_peak = float(obs[0])
     p_value = (1.0 + float(np.sum(sim_peaks >= observed_peak))) / (1.0 + nsims)
     return dict(observed_peak=observed_peak, observed_frequency=float(frequencies[at[0]]) if at[0] >= 0 else float("nan"),
                 sim_peaks=sim_peaks, p_value=p_value, null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+
+
+def _harmonics(nterms):
+    """The keyword of the engine's periodogram calls for ``nterms`` harmonics: none for one term, so that an engine-like
+    object with the one-term signature serves the default."""
+    return {} if nterms == 1 else {"nterms": nterms}
 
 
 def _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise, extension_factor, seed, device,
@@ -633,25 +641,28 @@ def _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma
     return eng, null, samples, sim_seed, out
 
 
-def _observed_power(eng, lightcurve, frequencies, normalization, weighted):
+def _observed_power(eng, lightcurve, frequencies, normalization, weighted, nterms=1):
     """The observed light curve made resident (nobody's evaluator's afterwards), and its periodogram [F]."""
     y = np.asarray(lightcurve.y, dtype=np.float64)
     dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
     eng.set_lightcurves(np.asarray(lightcurve.times, dtype=np.float64), y, dy)
     eng.bound_to = None
-    return eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None)[0]
+    return eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None,
+                            **_harmonics(nterms))[0]
 
 
-def _significance_of_resident_set(eng, observed_power, frequencies, nsims, levels, normalization, weighted):
+def _significance_of_resident_set(eng, observed_power, frequencies, nsims, levels, normalization, weighted, nterms=1):
     """Steps 4 to 6 of ``periodogram_significance`` on an engine that holds the ``nsims`` simulated light curves: the two
     envelope calls and the arithmetic on what comes back (tests drive it with a stand-in engine on the CPU)."""
     from .periodogram import envelope_levels, envelope_ranks
     levels = tuple(float(v) for v in np.atleast_1d(levels))
+    harmonics = _harmonics(nterms)
     if not np.all(np.isfinite(observed_power)):
         k = int(np.flatnonzero(~np.isfinite(observed_power))[0])
         raise ValueError("periodogram_significance: the observed power at frequencies[%d] = %g is not finite" % (k, frequencies[k]))
     ranks = envelope_ranks(nsims, (0.5,) + levels)
-    env = eng.lomb_scargle_envelope(frequencies, ranks=ranks, reference=observed_power, normalization=normalization, weighted=weighted)
+    env = eng.lomb_scargle_envelope(frequencies, ranks=ranks, reference=observed_power, normalization=normalization, weighted=weighted,
+                                    **harmonics)
     quantiles = envelope_levels(env.order_stat, ranks, nsims, (0.5,) + levels)
     median = quantiles[0]
     bad = ~(np.isfinite(median) & (median > 0))
@@ -659,7 +670,7 @@ def _significance_of_resident_set(eng, observed_power, frequencies, nsims, level
         k = int(np.flatnonzero(bad)[0])
         raise ValueError("periodogram_significance: the median power of the simulated light curves at frequencies[%d] = %g is %g, "
                          "not finite and positive" % (k, frequencies[k], median[k]))
-    peaks = eng.lomb_scargle_envelope(frequencies, scale=median, normalization=normalization, weighted=weighted)
+    peaks = eng.lomb_scargle_envelope(frequencies, scale=median, normalization=normalization, weighted=weighted, **harmonics)
     ratio = observed_power / median
     at = int(np.argmax(ratio))                     # (finite over finite and positive: no NaN; the first maximum)
     observed_ratio_peak = float(ratio[at])
@@ -672,7 +683,7 @@ def _significance_of_resident_set(eng, observed_power, frequencies, nsims, level
 
 def periodogram_significance(lightcurve, null_kernel, frequencies, nsims=100, levels=(0.95, 0.997), walkers=12, max_steps=500,
                              sigma_noise=None, extension_factor=2, normalization="standard", weighted=True, seed=None, device=0,
-                             progress=False, pdf="Gaussian", max_iter=400):
+                             progress=False, pdf="Gaussian", max_iter=400, nterms=1):
     """What a red-noise periodicity search reports (Vaughan 2005): the significance of the observed Lomb-Scargle power
     frequency by frequency, against light curves of the null model.  ``periodogram_peak_test`` compares highest RAW peaks,
     which for red-noise nulls sit at the lowest frequencies whatever the data hold; this compares every frequency with the
@@ -692,13 +703,14 @@ def periodogram_significance(lightcurve, null_kernel, frequencies, nsims=100, le
     samples[nsims][P], sim_seed, lightcurves).  A median that is not finite and positive at some frequency raises a
     ValueError naming it.  One GPU; the same seed gives the same result bit for bit.  ``weighted``: by the error bars, the
     simulated light curves' own included -- Poisson noise at a few counts per epoch leaves epochs with ``dy = 0`` that
-    take all the weight; pass ``weighted=False`` there."""
+    take all the weight; pass ``weighted=False`` there.  ``nterms``: harmonics per frequency of every periodogram
+    (``Engine.lomb_scargle``)."""
     from .gp import get_engine
     frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
-    observed_power = _observed_power(get_engine(device), lightcurve, frequencies, normalization, weighted)
+    observed_power = _observed_power(get_engine(device), lightcurve, frequencies, normalization, weighted, nterms)
     eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
                                                            extension_factor, seed, device, progress, pdf, max_iter)
-    res = _significance_of_resident_set(eng, observed_power, frequencies, nsims, levels, normalization, weighted)
+    res = _significance_of_resident_set(eng, observed_power, frequencies, nsims, levels, normalization, weighted, nterms)
     res.update(null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
     return res
 
