@@ -728,7 +728,7 @@ MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs /* [F]
  * nterms, normalization, weighted) alone, bit for bit.  A frequency at which a pivot of the factorisation is not positive
  * gives NaN in that entry.  Errors as for mtg_lomb_scargle, and MTG_E_ARG for nterms outside 1 .. MTG_LS_MAX_TERMS and for
  * N < 2 nterms + 2 (2 nterms + 1 samples are fitted exactly).  mtg_last_solver names "mtg_lomb_scargle_multi_kernel<K,R>"
- * (R light curves per lane: csrc/mtg_ls_multi_plan.h), or mtg_lomb_scargle's kernel for nterms == 1.
+ * (R light curves per lane: csrc/mtg_ls_plan.h), or mtg_lomb_scargle's kernel for nterms == 1.
  */
 enum { MTG_LS_MAX_TERMS = 5 };   /* (not one of the MTG_LS_* normalization macros) */
 MTG_API int mtg_lomb_scargle_multi(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host, cycles per unit time */,

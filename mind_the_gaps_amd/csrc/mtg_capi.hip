@@ -2514,6 +2514,34 @@ static int ls_refuse_terms(mtg_ctx *ctx, const char *who, int nterms, int64_t N)
     return MTG_OK;
 }
 
+// what both periodogram entries refuse about the frequencies, the normalization, the harmonics and the samples (MTG_OK:
+// nothing), in the order of their messages; nothing_asked: mtg_lomb_scargle's three outputs are all NULL
+static int ls_refuse_call(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization, bool nothing_asked)
+{
+    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
+    if (nothing_asked) return fail(ctx, MTG_E_ARG, "%s: power, peak_power and peak_index are all NULL", who);
+    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
+        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
+    const int rc = ls_refuse_terms(ctx, who, nterms, ctx->N);
+    if (rc) return rc;
+    for (int64_t k = 0; k < F; ++k)
+        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
+            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    return MTG_OK;
+}
+
+// the resident set and the call's choices; the frequencies and the peaks (none) are the caller's to set
+static MtgLombScargleArgs ls_resident_args(const mtg_ctx *ctx, int nterms, int normalization, int weighted, double *stats, double *power)
+{
+    MtgLombScargleArgs qa;
+    qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
+    qa.N = ctx->N; qa.t_stride = ctx->t_per_lc ? ctx->N : 0; qa.L = ctx->L;
+    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization; qa.nterms = nterms;
+    qa.stats = stats; qa.F = 0; qa.freqs = nullptr; qa.power = power;
+    qa.peak_power = nullptr; qa.peak_index = nullptr;
+    return qa;
+}
+
 // the kernel that computes the powers, as mtg_last_solver names it
 static void ls_kernel_name(char *out, size_t n, int nterms, int R)
 {
@@ -2528,32 +2556,22 @@ static int lomb_scargle_entry(mtg_ctx *ctx, const char *who, int64_t F, const do
     RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
     int rc = c.ready(false);
     if (rc) return rc;
-    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
-    if (!power && !peak_power && !peak_index) return fail(ctx, MTG_E_ARG, "%s: power, peak_power and peak_index are all NULL", who);
-    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
-        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
-    const int64_t N = ctx->N, L = ctx->L;
-    if ((rc = ls_refuse_terms(ctx, who, nterms, N))) return rc;
-    for (int64_t k = 0; k < F; ++k)
-        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
-            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    if ((rc = ls_refuse_call(ctx, who, F, freqs, nterms, normalization, !power && !peak_power && !peak_index))) return rc;
     if ((rc = c.begin(false))) return rc;
+    const int64_t L = ctx->L;
     // the powers of a slab of light curves at a time: <= 256 MiB of workspace whatever L F is
     int64_t Ls = ((int64_t)1 << 25) / F;
-    const int R = nterms == 1 ? mtg_lomb_scargle_tile(L, !ctx->t_per_lc, weighted) : mtg_ls_multi_tile(nterms, L, !ctx->t_per_lc, weighted);
+    const int R = mtg_ls_tile(nterms, L, !ctx->t_per_lc, weighted);
     Ls = Ls / R * R;   // whole tiles (a light curve's power does not depend on its tile: this only fills the lanes)
     if (Ls < R) Ls = R;
     if (Ls > L) Ls = L;
-    MtgLombScargleArgs qa;
     DevBuf d_freqs, d_stats, d_power, d_peak, d_index;
     const bool want_peak = peak_power || peak_index;
     c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_power, (size_t)Ls * (size_t)F * 8},
                {d_peak, want_peak ? (size_t)L * 8 : 0}, {d_index, want_peak ? (size_t)L * 8 : 0}});
     c.upload(d_freqs.p, freqs, (size_t)F * 8);
-    qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
-    qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.L = L;
-    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization; qa.nterms = nterms;
-    qa.stats = d_stats.as<double>(); qa.F = F; qa.freqs = d_freqs.as<double>(); qa.power = d_power.as<double>();
+    MtgLombScargleArgs qa = ls_resident_args(ctx, nterms, normalization, weighted, d_stats.as<double>(), d_power.as<double>());
+    qa.F = F; qa.freqs = d_freqs.as<double>();
     qa.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
     ls_kernel_name(ctx->last_solver, sizeof ctx->last_solver, nterms, R);
     c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
@@ -2595,14 +2613,8 @@ static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F,
     RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
     int rc = c.ready(false);
     if (rc) return rc;
-    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
-    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
-        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
-    const int64_t N = ctx->N, L = ctx->L;
-    if ((rc = ls_refuse_terms(ctx, who, nterms, N))) return rc;
-    for (int64_t k = 0; k < F; ++k)
-        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
-            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    if ((rc = ls_refuse_call(ctx, who, F, freqs, nterms, normalization, false))) return rc;
+    const int64_t L = ctx->L;
     if (Q < 0 || (Q > 0 && !ranks)) return fail(ctx, MTG_E_ARG, "%s: Q = %d ranks%s", who, Q, Q < 0 ? "" : ", ranks is NULL");
     if (Q > 0 && !order_stat) return fail(ctx, MTG_E_ARG, "%s: Q = %d ranks, order_stat is NULL", who, Q);
     for (int q = 0; q < Q; ++q)
@@ -2624,7 +2636,6 @@ static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F,
     const int64_t Fs = mtg_lse_slab_width(L, F, Q, MTG_LSE_BUDGET);
     const bool in_lds = mtg_lse_in_lds(L) != 0;
     const size_t slab_bytes = (size_t)L * (size_t)Fs * 8, temp_bytes = want_columns ? mtg_ls_envelope_temp_bytes(L, Fs) : 0;
-    MtgLombScargleArgs qa;
     MtgLsEnvelopeArgs ea;
     DevBuf d_freqs, d_stats, d_power, d_ranks, d_os, d_valid, d_ref, d_exceed, d_scale, d_peak, d_index, d_ka, d_kb, d_temp;
     const bool sort_global = want_columns && !in_lds;
@@ -2637,11 +2648,8 @@ static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F,
     if (Q > 0) c.upload(d_ranks.p, ranks, (size_t)Q * 8);
     if (reference) c.upload(d_ref.p, reference, (size_t)F * 8);
     if (want_ratio) c.upload(d_scale.p, scale, (size_t)F * 8);
-    qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
-    qa.N = N; qa.t_stride = ctx->t_per_lc ? N : 0; qa.L = L;
-    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization; qa.nterms = nterms;
-    qa.stats = d_stats.as<double>(); qa.power = d_power.as<double>();
-    qa.peak_power = nullptr; qa.peak_index = nullptr;
+    // (the frequencies are each slab's; no peaks)
+    MtgLombScargleArgs qa = ls_resident_args(ctx, nterms, normalization, weighted, d_stats.as<double>(), d_power.as<double>());
     ea.slab = d_power.as<double>(); ea.L = L; ea.Q = Q; ea.ranks = d_ranks.as<int64_t>(); ea.order_stat = d_os.as<double>();
     ea.valid = valid ? d_valid.as<int64_t>() : nullptr; ea.reference = reference ? d_ref.as<double>() : nullptr;
     ea.exceed = exceed ? d_exceed.as<int64_t>() : nullptr; ea.scale = d_scale.as<double>();

@@ -264,14 +264,6 @@ static_assert(std::is_trivially_copyable<MtgPredictArgs>::value && std::is_trivi
               std::is_trivially_copyable<MtgWhitenArgs>::value,
               "passed by value as kernel arguments");
 
-// light curves whose sums one lane of the Lomb-Scargle kernel carries on shared sampling (mtg_lomb_scargle.hip): with the
-// chunk's partial sums 2 x 6 R doubles per lane when every light curve has weights of its own, 2 x (2 R + 4) otherwise
-#ifndef MTG_LS_R_WEIGHTED
-#define MTG_LS_R_WEIGHTED 8
-#endif
-#ifndef MTG_LS_R_UNWEIGHTED
-#define MTG_LS_R_UNWEIGHTED 16
-#endif
 struct MtgLombScargleArgs {
     const double2 *dxt, *yv;
     int64_t N, t_stride, L;   // the resident set: t_stride 0 (shared sampling) or N
@@ -288,10 +280,8 @@ struct MtgLombScargleArgs {
 // (0 = more workgroups than a grid holds)
 void mtg_launch_lomb_scargle_stats(const MtgLombScargleArgs &, hipStream_t);
 int mtg_launch_lomb_scargle(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, hipStream_t);
-// light curves per lane for a set of L (1, 4, or the full tile of the weighting)
-int mtg_lomb_scargle_tile(int64_t L, int shared_sampling, int weighted);
-// ... and with K >= 2 harmonics: mtg_ls_multi_tile(K, L, shared_sampling, weighted)
-#include "mtg_ls_multi_plan.h"
+// light curves per lane for a set of L: mtg_ls_tile(nterms, L, shared_sampling, weighted)
+#include "mtg_ls_plan.h"
 // the powers of one slab with nterms >= 2 (mtg_lomb_scargle_multi.hip; mtg_launch_lomb_scargle dispatches to it and adds
 // the peaks; 0 = more workgroups than a grid holds)
 int mtg_launch_lomb_scargle_multi_powers(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, hipStream_t);

@@ -12,24 +12,12 @@
 // set does not matter.  sum w s^2 is (sum w) - sum w c^2 with sum w = 1.
 //
 // Work: one (cos, sin) pair per (frequency, sample) and 2 FMAs per (frequency, sample, light curve) -- 6 when the
-// weights differ from one light curve to the next.  One lane owns a frequency; a workgroup walks the samples in chunks
-// of MTG_LS_CHUNK staged in LDS, every lane reading the same sample (a broadcast).  On shared sampling a lane carries
-// the sums of a tile of R light curves, so that the pair is computed once per tile (and C, S, CC, CS too when the
-// weights are 1 / N).
-//
-// Budget.  LDS: the 32 KiB (cos, sin) table, the chunk's elapsed times (2 KiB) and its (w, w r) pairs
-// (R x 4 KiB weighted, R x 2 KiB unweighted): 66 KiB for R = 8 weighted / R = 16 unweighted, two workgroups of four waves
-// on a CU's 160 KiB, two waves per SIMD.  Registers: the running totals and the chunk's partial sums, 2 x 6 R doubles
-// weighted, 2 x (2 R + 4) unweighted, under the 256 VGPRs two waves per SIMD leave each lane (profiles/
-// lomb_scargle_resources.txt; no scratch).
-//
-// Order.  Samples ascending; the sums of a chunk start from zero and are added to the running totals at its end.  The
-// arithmetic of one (light curve, frequency) is the same sequence of operations in every instantiation, so that a
-// power depends on (light curve, frequency, normalization, weighted) alone: not on L, the tile, F, the order of the
-// frequencies, or on how the sampling is stored.
-#include "mtg_device.h"
-#include "mtg_math.h"
-#include "mtg_ls_phase.h"
+// weights differ from one light curve to the next.  The sweep over tiles of light curves, chunks of samples and
+// frequencies, its LDS budget and its order of summation are mtg_ls_tile.h's; LsOneTerm below is this unit's model.
+// Registers: the running totals and the chunk's partial sums, 2 x 6 R doubles weighted, 2 x (2 R + 4) unweighted, under
+// the 256 VGPRs two waves per SIMD leave each lane (profiles/lomb_scargle_resources.txt; no scratch).
+#include "mtg_ls_tile.h"
+#include "mtg_ls_peak.h"
 
 namespace {
 
@@ -82,18 +70,6 @@ mtg_lomb_scargle_stats_kernel(const double2 *__restrict__ yv, int64_t N, int wei
     if (tid == 0) stats[l] = make_double4(ybar, yy, sw, 0.0);
 }
 
-struct MtgLsArgs {
-    const double2 *dxt, *yv;
-    int64_t N, t_stride;     // 0 (shared sampling) or N
-    int64_t l0, Ls;          // this launch takes light curves [l0, l0 + Ls)
-    const double4 *stats;    // [L]
-    int64_t F;
-    const double *freqs;     // [F]
-    int nfb;                 // workgroups along the frequencies
-    int normalization;
-    double *power;           // [Ls][F] of this slab
-};
-
 // the trig part of a lane's sums: C, S, sum w c^2, sum w c s
 struct LsTrig {
     double c, s, cc, cs;
@@ -109,136 +85,55 @@ struct LsTrig {
     __device__ __forceinline__ void fold(const LsTrig &o) { c += o.c; s += o.s; cc += o.cc; cs += o.cs; }
 };
 
+// a light curve's sums YC = sum w r c, YS = sum w r s
+struct LsPair {
+    double yc, ys;
+    __device__ __forceinline__ void zero() { yc = ys = 0.0; }
+    __device__ __forceinline__ void fold(const LsPair &o) { yc += o.yc; ys += o.ys; }
+};
+
+// one sinusoid with a floating mean: the closed form of the file header
+struct LsOneTerm {
+    typedef LsTrig Trig;
+    typedef LsPair Data;
+    template <int NT, int R>
+    static __device__ __forceinline__ void accumulate(double co, double si, const double (&wt)[NT], const double (&wr)[R], LsTrig (&pt)[NT],
+                                                      LsPair (&py)[R])
+    {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            if (j < NT) pt[j].add(wt[j], co, si);
+            py[j].yc = __builtin_fma(wr[j], co, py[j].yc);
+            py[j].ys = __builtin_fma(wr[j], si, py[j].ys);
+        }
+    }
+    struct Solve {
+        double CC, SS, CS, det;
+        __device__ __forceinline__ void prepare(const LsTrig &g)
+        {
+#pragma clang fp contract(off)
+            CC = g.cc - g.c * g.c; SS = (1.0 - g.cc) - g.s * g.s; CS = g.cs - g.c * g.s;
+            det = CC * SS - CS * CS;
+        }
+        __device__ __forceinline__ bool solve(const LsPair &y, double *p) const
+        {
+#pragma clang fp contract(off)
+            const double YC = y.yc, YS = y.ys;
+            const double num = (SS * YC) * YC + (CC * YS) * YS - 2.0 * ((CS * YC) * YS);
+            if (!(det > 0.0)) return false;
+            *p = num / det;
+            return true;
+        }
+    };
+};
+
 // R light curves per lane; WEIGHTED: weights from the light curve's own sigma (its trig sums are its own), else 1 / N
-// (the trig sums are the tile's).  LDS chunk: te[CHUNK], then WEIGHTED (w, w r)[R][CHUNK], else w r as pairs of light
-// curves (2j, 2j + 1)[R / 2][CHUNK] (R = 1: [CHUNK] doubles) -- one ds_read_b128 per two sums either way.
+// (the trig sums are the tile's)
 template <int R, bool WEIGHTED>
 __global__ void __launch_bounds__(MTG_LS_THREADS, 2)
 mtg_lomb_scargle_kernel(const MtgLsArgs a)
 {
-#pragma clang fp contract(off)
-    constexpr int CH = MTG_LS_CHUNK;
-    constexpr int NT = WEIGHTED ? R : 1;               // trig sums kept per lane
-    constexpr int NP = WEIGHTED ? R : (R + 1) / 2;     // 16-byte (R = 1 unweighted: 8-byte) columns of the chunk
-    __shared__ MtgLsTab tab;
-    __shared__ double te_s[CH];
-    __shared__ double2 col_s[NP * CH];
-
-    const int tid = threadIdx.x, nth = blockDim.x;
-    mtg_ls_fill_tab(&tab);
-    const int64_t tile = blockIdx.x / a.nfb;
-    const int fb = (int)(blockIdx.x - tile * a.nfb);
-    const int64_t lt = a.l0 + tile * R;                 // first light curve of the tile
-    const int nl = (int)(a.l0 + a.Ls - lt < R ? a.l0 + a.Ls - lt : R);   // light curves in it
-    const int64_t k = (int64_t)fb * nth + tid;
-    const double f = a.freqs[k < a.F ? k : a.F - 1];    // (idle lanes repeat the last frequency and store nothing)
-    const double2 *dxt = a.dxt + lt * a.t_stride;
-    const double t0 = dxt[0].y;
-    const double w0 = 1.0 / (double)a.N;
-
-    LsTrig tt[NT];
-    double tyc[R], tys[R];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) tt[i].zero();
-#pragma unroll
-    for (int i = 0; i < R; ++i) tyc[i] = tys[i] = 0.0;
-
-    for (int64_t n0 = 0; n0 < a.N; n0 += CH) {
-        const int len = (int)(a.N - n0 < CH ? a.N - n0 : CH);
-        __syncthreads();   // the previous chunk has been read (first trip: nothing)
-        for (int i = tid; i < len; i += nth) te_s[i] = dxt[n0 + i].y - t0;
-        if (WEIGHTED) {
-            for (int e = tid; e < R * CH; e += nth) {
-                const int j = e / CH, i = e - j * CH;
-                if (i >= len) continue;
-                double2 o = make_double2(0.0, 0.0);    // a light curve beyond the tile adds zeros and is not stored
-                if (j < nl) {
-                    const double4 st = a.stats[lt + j];
-                    const double2 v = a.yv[(lt + j) * a.N + n0 + i];
-                    const double w = (1.0 / v.y) / st.z;
-                    o = make_double2(w, w * (v.x - st.x));
-                }
-                col_s[j * CH + i] = o;
-            }
-        } else if (R == 1) {
-            const double ybar = a.stats[lt].x;
-            double *col = reinterpret_cast<double *>(col_s);
-            for (int i = tid; i < len; i += nth) col[i] = w0 * (a.yv[lt * a.N + n0 + i].x - ybar);
-        } else {
-            for (int e = tid; e < NP * CH; e += nth) {
-                const int j = e / CH, i = e - j * CH;
-                if (i >= len) continue;
-                double2 o = make_double2(0.0, 0.0);
-                if (2 * j < nl) o.x = w0 * (a.yv[(lt + 2 * j) * a.N + n0 + i].x - a.stats[lt + 2 * j].x);
-                if (2 * j + 1 < nl) o.y = w0 * (a.yv[(lt + 2 * j + 1) * a.N + n0 + i].x - a.stats[lt + 2 * j + 1].x);
-                col_s[j * CH + i] = o;
-            }
-        }
-        __syncthreads();
-
-        LsTrig pt[NT];
-        double pyc[R], pys[R];
-#pragma unroll
-        for (int i = 0; i < NT; ++i) pt[i].zero();
-#pragma unroll
-        for (int i = 0; i < R; ++i) pyc[i] = pys[i] = 0.0;
-        for (int i = 0; i < len; ++i) {
-            double si, co;
-            mtg_cycles_sincos(f, te_s[i], &si, &co, &tab);
-            if (WEIGHTED) {
-#pragma unroll
-                for (int j = 0; j < R; ++j) {
-                    const double2 v = col_s[j * CH + i];
-                    pt[j].add(v.x, co, si);
-                    pyc[j] = __builtin_fma(v.y, co, pyc[j]);
-                    pys[j] = __builtin_fma(v.y, si, pys[j]);
-                }
-            } else {
-                pt[0].add(w0, co, si);
-                if (R == 1) {
-                    const double v = reinterpret_cast<const double *>(col_s)[i];
-                    pyc[0] = __builtin_fma(v, co, pyc[0]);
-                    pys[0] = __builtin_fma(v, si, pys[0]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < R / 2; ++j) {
-                        const double2 v = col_s[j * CH + i];
-                        pyc[2 * j] = __builtin_fma(v.x, co, pyc[2 * j]);
-                        pys[2 * j] = __builtin_fma(v.x, si, pys[2 * j]);
-                        pyc[2 * j + 1] = __builtin_fma(v.y, co, pyc[2 * j + 1]);
-                        pys[2 * j + 1] = __builtin_fma(v.y, si, pys[2 * j + 1]);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) tt[i].fold(pt[i]);
-#pragma unroll
-        for (int i = 0; i < R; ++i) { tyc[i] += pyc[i]; tys[i] += pys[i]; }
-    }
-
-    if (k >= a.F) return;
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        if (j >= nl) continue;
-        const LsTrig &g = tt[WEIGHTED ? j : 0];
-        const double4 st = a.stats[lt + j];
-        const double CC = g.cc - g.c * g.c, SS = (1.0 - g.cc) - g.s * g.s, CS = g.cs - g.c * g.s;
-        const double YC = tyc[j], YS = tys[j], YY = st.y;
-        const double det = CC * SS - CS * CS;
-        const double num = (SS * YC) * YC + (CC * YS) * YS - 2.0 * ((CS * YC) * YS);
-        double out = __builtin_nan("");
-        if (det > 0.0) {
-            const double p = num / det;
-            switch (a.normalization) {
-            case MTG_LS_STANDARD: out = p / YY; break;
-            case MTG_LS_MODEL: out = p / (YY - p); break;
-            case MTG_LS_LOG: out = -log(1.0 - p / YY); break;
-            default: out = p * (0.5 * st.z); break;   // MTG_LS_PSD
-            }
-        }
-        a.power[(lt - a.l0 + j) * a.F + k] = out;
-    }
+    ls_tile_sweep<LsOneTerm, R, WEIGHTED>(a);
 }
 
 // the largest entry of every row of power[Ls][F] and the first index that attains it; NaN entries are passed over (a
@@ -246,36 +141,20 @@ mtg_lomb_scargle_kernel(const MtgLsArgs a)
 __global__ void __launch_bounds__(MTG_LS_THREADS)
 mtg_lomb_scargle_peak_kernel(const double *__restrict__ power, int64_t F, double *__restrict__ peak, int64_t *__restrict__ index)
 {
-    __shared__ double bv[MTG_LS_THREADS];
-    __shared__ int64_t bi[MTG_LS_THREADS];
     const double *row = power + (int64_t)blockIdx.x * F;
-    const int tid = threadIdx.x;
-    double v = 0.0;
-    int64_t at = -1;
-    for (int64_t k = tid; k < F; k += MTG_LS_THREADS) {
-        const double x = row[k];
-        if (x == x && (at < 0 || x > v)) { v = x; at = k; }
-    }
-    bv[tid] = v; bi[tid] = at;
-    __syncthreads();
-    for (int h = MTG_LS_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-            const double x = bv[tid + h];
-            const int64_t xi = bi[tid + h];
-            if (xi >= 0 && (bi[tid] < 0 || x > bv[tid] || (x == bv[tid] && xi < bi[tid]))) { bv[tid] = x; bi[tid] = xi; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (peak) peak[blockIdx.x] = bi[0] < 0 ? __builtin_nan("") : bv[0];
-        if (index) index[blockIdx.x] = bi[0];
+    double v;
+    int64_t at;
+    ls_block_peak<MTG_LS_THREADS>(F, [row](int64_t k) { return row[k]; }, &v, &at);
+    if (threadIdx.x == 0) {
+        if (peak) peak[blockIdx.x] = at < 0 ? __builtin_nan("") : v;
+        if (index) index[blockIdx.x] = at;
     }
 }
 
 template <int R, bool WEIGHTED>
-void ls_launch(const MtgLsArgs &a, int64_t blocks, int threads, hipStream_t s)
+void ls_launch(const MtgLsLaunch &g, hipStream_t s)
 {
-    hipLaunchKernelGGL((mtg_lomb_scargle_kernel<R, WEIGHTED>), dim3((unsigned)blocks), dim3(threads), 0, s, a);
+    hipLaunchKernelGGL((mtg_lomb_scargle_kernel<R, WEIGHTED>), dim3((unsigned)g.blocks), dim3(g.threads), 0, s, g.a);
 }
 
 // the peaks of the slab's rows, where asked for
@@ -288,13 +167,6 @@ void ls_launch_peaks(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls, hipStr
 
 }  // namespace
 
-int mtg_lomb_scargle_tile(int64_t L, int shared_sampling, int weighted)
-{
-    if (!shared_sampling || L <= 1) return 1;
-    if (L <= 4) return 4;
-    return weighted ? MTG_LS_R_WEIGHTED : MTG_LS_R_UNWEIGHTED;
-}
-
 void mtg_launch_lomb_scargle_stats(const MtgLombScargleArgs &q, hipStream_t s)
 {
     hipLaunchKernelGGL(mtg_lomb_scargle_stats_kernel, dim3((unsigned)q.L), dim3(MTG_LS_THREADS), 0, s, q.yv, q.N, q.weighted,
@@ -305,27 +177,20 @@ int mtg_launch_lomb_scargle(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls,
 {
     if (q.nterms > 1) {   // the powers with harmonics come from mtg_lomb_scargle_multi.hip; the peaks are reduced here
         if (!mtg_launch_lomb_scargle_multi_powers(q, l0, Ls, s)) return 0;
-        ls_launch_peaks(q, l0, Ls, s);
-        return 1;
-    }
-    const int R = mtg_lomb_scargle_tile(q.L, q.t_stride == 0, q.weighted);
-    // narrow frequency lists leave most of a wide workgroup idle: one or two waves then (the arithmetic of a lane is the same)
-    const int threads = q.F <= 64 ? 64 : q.F <= 128 ? 128 : MTG_LS_THREADS;
-    const int64_t nfb = (q.F + threads - 1) / threads, tiles = (Ls + R - 1) / R;
-    if (nfb > 0x7fffffff / tiles) return 0;
-    MtgLsArgs a;
-    a.dxt = q.dxt; a.yv = q.yv; a.N = q.N; a.t_stride = q.t_stride; a.l0 = l0; a.Ls = Ls;
-    a.stats = reinterpret_cast<const double4 *>(q.stats); a.F = q.F; a.freqs = q.freqs; a.nfb = (int)nfb;
-    a.normalization = q.normalization; a.power = q.power;
-    const int64_t blocks = nfb * tiles;
-    if (q.weighted) {
-        if (R == 1) ls_launch<1, true>(a, blocks, threads, s);
-        else if (R == 4) ls_launch<4, true>(a, blocks, threads, s);
-        else ls_launch<MTG_LS_R_WEIGHTED, true>(a, blocks, threads, s);
     } else {
-        if (R == 1) ls_launch<1, false>(a, blocks, threads, s);
-        else if (R == 4) ls_launch<4, false>(a, blocks, threads, s);
-        else ls_launch<MTG_LS_R_UNWEIGHTED, false>(a, blocks, threads, s);
+        constexpr int RW = mtg_ls_full_tile(1, 1), RU = mtg_ls_full_tile(1, 0);
+        const int R = mtg_ls_tile(1, q.L, q.t_stride == 0, q.weighted);
+        MtgLsLaunch g;
+        if (!mtg_ls_plan_launch(q, R, l0, Ls, &g)) return 0;
+        if (q.weighted) {
+            if (R == 1) ls_launch<1, true>(g, s);
+            else if (R == 4) ls_launch<4, true>(g, s);
+            else ls_launch<RW, true>(g, s);
+        } else {
+            if (R == 1) ls_launch<1, false>(g, s);
+            else if (R == 4) ls_launch<4, false>(g, s);
+            else ls_launch<RU, false>(g, s);
+        }
     }
     ls_launch_peaks(q, l0, Ls, s);
     return 1;

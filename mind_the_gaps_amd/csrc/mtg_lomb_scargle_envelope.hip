@@ -22,6 +22,7 @@
 // counts by binary search in the sorted keys.
 #include "mtg_device.h"
 #include "mtg_ls_envelope_plan.h"
+#include "mtg_ls_peak.h"
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -167,28 +168,13 @@ __global__ void __launch_bounds__(256)
 mtg_ls_envelope_ratio_peak_kernel(const double *__restrict__ slab, int64_t Fs, int64_t k0, const double *__restrict__ scale,
                                   double *__restrict__ peak, int64_t *__restrict__ index)
 {
-    __shared__ double bv[256];
-    __shared__ int64_t bi[256];
     const double *row = slab + (int64_t)blockIdx.x * Fs;
-    const int tid = threadIdx.x;
-    double v = 0.0;
-    int64_t at = -1;
-    for (int64_t k = tid; k < Fs; k += 256) {
-        const double x = row[k] / scale[k0 + k];
-        if (x == x && (at < 0 || x > v)) { v = x; at = k0 + k; }
-    }
-    bv[tid] = v; bi[tid] = at;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (tid < h) {
-            const double x = bv[tid + h];
-            const int64_t xi = bi[tid + h];
-            if (xi >= 0 && (bi[tid] < 0 || x > bv[tid] || (x == bv[tid] && xi < bi[tid]))) { bv[tid] = x; bi[tid] = xi; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        v = bv[0]; at = bi[0];
+    const double *by = scale + k0;
+    double v;
+    int64_t at;
+    ls_block_peak<256>(Fs, [row, by](int64_t k) { return row[k] / by[k]; }, &v, &at);
+    if (threadIdx.x == 0) {
+        if (at >= 0) at += k0;
         if (k0 > 0) {
             const int64_t before = index[blockIdx.x];
             if (before >= 0 && !(at >= 0 && v > peak[blockIdx.x])) { v = peak[blockIdx.x]; at = before; }

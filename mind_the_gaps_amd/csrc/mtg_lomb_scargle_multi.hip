@@ -11,37 +11,18 @@
 // S_0 = 0): a lane carries 4 K trigonometric sums and, per light curve, the 2 K data sums sum w r sin m phi,
 // sum w r cos m phi (m <= K).
 //
-// One lane owns a frequency; a workgroup walks the samples in chunks of MTG_LS_CHUNK staged in LDS.  The base pair
+// The sweep over tiles of light curves, chunks of samples and frequencies, its LDS budget and its order of summation
+// are mtg_ls_tile.h's, the one-term kernel's too; LsHarmonics<K> below is this unit's model.  The base pair
 // (cos phi, sin phi) is mtg_cycles_sincos's, bit for bit the one-term kernel's; harmonic m follows from harmonic m - 1
-// by one complex multiplication by that pair, m = 2 .. 2 K in this order.  On shared sampling a lane carries a tile of R
-// light curves (mtg_ls_multi_plan.h: R per (K, weighted) such that two waves per SIMD need no scratch), so that pair and
-// harmonics are computed once per tile -- and the trigonometric sums too when the weights are 1 / N.
+// by one complex multiplication by that pair, m = 2 .. 2 K in this order.  The tile of R light curves per lane is
+// mtg_ls_plan.h's: R per (K, weighted) such that two waves per SIMD need no scratch.
 //
 // After the last chunk the 2 K x 2 K matrix is assembled and factored by an unrolled Cholesky in registers: once per
 // (frequency, light curve) weighted, once per lane unweighted (the factor serves the tile).  A pivot that is not
 // positive gives NaN.
-//
-// Order.  Samples ascending; the sums of a chunk start from zero and are added to the running totals at its end.  The
-// arithmetic of one (light curve, frequency) is the same sequence of operations in every instantiation of a (K,
-// weighted), so that a power depends on (light curve, frequency, K, normalization, weighted) alone: not on L, the tile,
-// F, the order of the frequencies, or on how the sampling is stored.
-#include "mtg_device.h"
-#include "mtg_math.h"
-#include "mtg_ls_phase.h"
+#include "mtg_ls_tile.h"
 
 namespace {
-
-struct MtgLsMultiArgs {
-    const double2 *dxt, *yv;
-    int64_t N, t_stride;     // 0 (shared sampling) or N
-    int64_t l0, Ls;          // this launch takes light curves [l0, l0 + Ls)
-    const double4 *stats;    // [L]: ybar, YY, sum sigma^-2 (or N), 0 -- mtg_lomb_scargle_stats_kernel's
-    int64_t F;
-    const double *freqs;     // [F]
-    int nfb;                 // workgroups along the frequencies
-    int normalization;
-    double *power;           // [Ls][F] of this slab
-};
 
 // the trigonometric sums of a lane: c[m - 1] = sum w cos m phi, s[m - 1] = sum w sin m phi, m = 1 .. 2 K
 template <int K>
@@ -139,174 +120,77 @@ struct LsFactor {
     }
 };
 
-// K harmonics, R light curves per lane; WEIGHTED: weights from the light curve's own sigma (its trigonometric sums are
-// its own), else 1 / N (they are the tile's).  LDS chunk as in mtg_lomb_scargle_kernel: te[CHUNK], then WEIGHTED
-// (w, w r)[R][CHUNK], else w r as pairs of light curves (2j, 2j + 1)[R / 2][CHUNK] (R = 1: [CHUNK] doubles).
-template <int K, int R, bool WEIGHTED>
-__global__ void __launch_bounds__(MTG_LS_THREADS, 2)
-mtg_lomb_scargle_multi_kernel(const MtgLsMultiArgs a)
-{
+// K phase-tied harmonics with a floating mean
+template <int K>
+struct LsHarmonics {
+    typedef LsHarm<K> Trig;
+    typedef LsData<K> Data;
+    template <int NT, int R>
+    static __device__ __forceinline__ void accumulate(double c1, double s1, const double (&wt)[NT], const double (&wr)[R], Trig (&pt)[NT],
+                                                      Data (&py)[R])
+    {
 #pragma clang fp contract(off)
-    static_assert(WEIGHTED || R == 1 || R % 2 == 0, "the unweighted chunk is staged as pairs of light curves");
-    constexpr int CH = MTG_LS_CHUNK;
-    constexpr int NT = WEIGHTED ? R : 1;               // sets of trigonometric sums kept per lane
-    constexpr int NP = WEIGHTED ? R : (R + 1) / 2;     // 16-byte (R = 1 unweighted: 8-byte) columns of the chunk
-    __shared__ MtgLsTab tab;
-    __shared__ double te_s[CH];
-    __shared__ double2 col_s[NP * CH];
-
-    const int tid = threadIdx.x, nth = blockDim.x;
-    mtg_ls_fill_tab(&tab);
-    const int64_t tile = blockIdx.x / a.nfb;
-    const int fb = (int)(blockIdx.x - tile * a.nfb);
-    const int64_t lt = a.l0 + tile * R;                 // first light curve of the tile
-    const int nl = (int)(a.l0 + a.Ls - lt < R ? a.l0 + a.Ls - lt : R);   // light curves in it
-    const int64_t k = (int64_t)fb * nth + tid;
-    const double f = a.freqs[k < a.F ? k : a.F - 1];    // (idle lanes repeat the last frequency and store nothing)
-    const double2 *dxt = a.dxt + lt * a.t_stride;
-    const double t0 = dxt[0].y;
-    const double w0 = 1.0 / (double)a.N;
-
-    LsHarm<K> tt[NT];
-    LsData<K> ty[R];
+        double cm = c1, sm = s1;
 #pragma unroll
-    for (int i = 0; i < NT; ++i) tt[i].zero();
-#pragma unroll
-    for (int i = 0; i < R; ++i) ty[i].zero();
-
-    for (int64_t n0 = 0; n0 < a.N; n0 += CH) {
-        const int len = (int)(a.N - n0 < CH ? a.N - n0 : CH);
-        __syncthreads();   // the previous chunk has been read (first trip: nothing)
-        for (int i = tid; i < len; i += nth) te_s[i] = dxt[n0 + i].y - t0;
-        if (WEIGHTED) {
-            for (int e = tid; e < R * CH; e += nth) {
-                const int j = e / CH, i = e - j * CH;
-                if (i >= len) continue;
-                double2 o = make_double2(0.0, 0.0);    // a light curve beyond the tile adds zeros and is not stored
-                if (j < nl) {
-                    const double4 st = a.stats[lt + j];
-                    const double2 v = a.yv[(lt + j) * a.N + n0 + i];
-                    const double w = (1.0 / v.y) / st.z;
-                    o = make_double2(w, w * (v.x - st.x));
-                }
-                col_s[j * CH + i] = o;
+        for (int m = 0; m < 2 * K; ++m) {
+            if (m > 0) {   // (cos, sin)((m + 1) phi) = (cos, sin)(m phi) x (cos, sin)(phi)
+                const double cn = __builtin_fma(cm, c1, -(sm * s1));
+                const double sn = __builtin_fma(sm, c1, cm * s1);
+                cm = cn;
+                sm = sn;
             }
-        } else if (R == 1) {
-            const double ybar = a.stats[lt].x;
-            double *col = reinterpret_cast<double *>(col_s);
-            for (int i = tid; i < len; i += nth) col[i] = w0 * (a.yv[lt * a.N + n0 + i].x - ybar);
-        } else {
-            for (int e = tid; e < NP * CH; e += nth) {
-                const int j = e / CH, i = e - j * CH;
-                if (i >= len) continue;
-                double2 o = make_double2(0.0, 0.0);
-                if (2 * j < nl) o.x = w0 * (a.yv[(lt + 2 * j) * a.N + n0 + i].x - a.stats[lt + 2 * j].x);
-                if (2 * j + 1 < nl) o.y = w0 * (a.yv[(lt + 2 * j + 1) * a.N + n0 + i].x - a.stats[lt + 2 * j + 1].x);
-                col_s[j * CH + i] = o;
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                pt[j].c[m] = __builtin_fma(wt[j], cm, pt[j].c[m]);
+                pt[j].s[m] = __builtin_fma(wt[j], sm, pt[j].s[m]);
             }
-        }
-        __syncthreads();
-
-        LsHarm<K> pt[NT];
-        LsData<K> py[R];
-#pragma unroll
-        for (int i = 0; i < NT; ++i) pt[i].zero();
-#pragma unroll
-        for (int i = 0; i < R; ++i) py[i].zero();
-        for (int i = 0; i < len; ++i) {
-            double s1, c1;
-            mtg_cycles_sincos(f, te_s[i], &s1, &c1, &tab);
-            // the chunk's operands: w per set of trigonometric sums, w r per light curve
-            double wt[NT], wr[R];
-            if (WEIGHTED) {
+            if (m < K) {
 #pragma unroll
                 for (int j = 0; j < R; ++j) {
-                    const double2 v = col_s[j * CH + i];
-                    wt[j] = v.x;
-                    wr[j] = v.y;
-                }
-            } else {
-                wt[0] = w0;
-                if (R == 1) {
-                    wr[0] = reinterpret_cast<const double *>(col_s)[i];
-                } else {
-#pragma unroll
-                    for (int j = 0; j < R / 2; ++j) {
-                        const double2 v = col_s[j * CH + i];
-                        wr[2 * j] = v.x;
-                        wr[2 * j + 1] = v.y;
-                    }
-                }
-            }
-            double cm = c1, sm = s1;
-#pragma unroll
-            for (int m = 0; m < 2 * K; ++m) {
-                if (m > 0) {   // (cos, sin)((m + 1) phi) = (cos, sin)(m phi) x (cos, sin)(phi)
-                    const double cn = __builtin_fma(cm, c1, -(sm * s1));
-                    const double sn = __builtin_fma(sm, c1, cm * s1);
-                    cm = cn;
-                    sm = sn;
-                }
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    pt[j].c[m] = __builtin_fma(wt[j], cm, pt[j].c[m]);
-                    pt[j].s[m] = __builtin_fma(wt[j], sm, pt[j].s[m]);
-                }
-                if (m < K) {
-#pragma unroll
-                    for (int j = 0; j < R; ++j) {
-                        py[j].c[m] = __builtin_fma(wr[j], cm, py[j].c[m]);
-                        py[j].s[m] = __builtin_fma(wr[j], sm, py[j].s[m]);
-                    }
+                    py[j].c[m] = __builtin_fma(wr[j], cm, py[j].c[m]);
+                    py[j].s[m] = __builtin_fma(wr[j], sm, py[j].s[m]);
                 }
             }
         }
-#pragma unroll
-        for (int i = 0; i < NT; ++i) tt[i].fold(pt[i]);
-#pragma unroll
-        for (int i = 0; i < R; ++i) ty[i].fold(py[i]);
     }
+    struct Solve {
+        LsFactor<K> fac;
+        __device__ __forceinline__ void prepare(const Trig &g) { fac.factor(g); }
+        __device__ __forceinline__ bool solve(const Data &y, double *p) const
+        {
+            if (!fac.ok) return false;
+            *p = fac.quad(y);
+            return true;
+        }
+    };
+};
 
-    if (k >= a.F) return;
-    LsFactor<K> fac;
-    if (!WEIGHTED) fac.factor(tt[0]);
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-        if (j >= nl) continue;
-        if (WEIGHTED) fac.factor(tt[j]);
-        const double4 st = a.stats[lt + j];
-        const double YY = st.y;
-        double out = __builtin_nan("");
-        if (fac.ok) {
-            const double p = fac.quad(ty[j]);
-            switch (a.normalization) {
-            case MTG_LS_STANDARD: out = p / YY; break;
-            case MTG_LS_MODEL: out = p / (YY - p); break;
-            case MTG_LS_LOG: out = -log(1.0 - p / YY); break;
-            default: out = p * (0.5 * st.z); break;   // MTG_LS_PSD
-            }
-        }
-        a.power[(lt - a.l0 + j) * a.F + k] = out;
-    }
+// K harmonics, R light curves per lane; WEIGHTED: weights from the light curve's own sigma (its trigonometric sums are
+// its own), else 1 / N (they are the tile's)
+template <int K, int R, bool WEIGHTED>
+__global__ void __launch_bounds__(MTG_LS_THREADS, 2)
+mtg_lomb_scargle_multi_kernel(const MtgLsArgs a)
+{
+    ls_tile_sweep<LsHarmonics<K>, R, WEIGHTED>(a);
 }
 
 template <int K, int R, bool WEIGHTED>
-void lsm_launch(const MtgLsMultiArgs &a, int64_t blocks, int threads, hipStream_t s)
+void lsm_launch(const MtgLsLaunch &g, hipStream_t s)
 {
-    hipLaunchKernelGGL((mtg_lomb_scargle_multi_kernel<K, R, WEIGHTED>), dim3((unsigned)blocks), dim3(threads), 0, s, a);
+    hipLaunchKernelGGL((mtg_lomb_scargle_multi_kernel<K, R, WEIGHTED>), dim3((unsigned)g.blocks), dim3(g.threads), 0, s, g.a);
 }
 
-// the two tiles of a (K, weighted): 1 and the full one of mtg_ls_multi_plan.h
+// the two tiles of a (K, weighted): 1 and the full one of mtg_ls_plan.h
 template <int K>
-void lsm_dispatch(const MtgLsMultiArgs &a, int R, int weighted, int64_t blocks, int threads, hipStream_t s)
+void lsm_dispatch(const MtgLsLaunch &g, int R, int weighted, hipStream_t s)
 {
-    constexpr int RW = mtg_ls_multi_full_tile(K, 1), RU = mtg_ls_multi_full_tile(K, 0);
+    constexpr int RW = mtg_ls_full_tile(K, 1), RU = mtg_ls_full_tile(K, 0);
     if (weighted) {
-        if (R == 1) lsm_launch<K, 1, true>(a, blocks, threads, s);
-        else lsm_launch<K, RW, true>(a, blocks, threads, s);
+        if (R == 1) lsm_launch<K, 1, true>(g, s);
+        else lsm_launch<K, RW, true>(g, s);
     } else {
-        if (R == 1) lsm_launch<K, 1, false>(a, blocks, threads, s);
-        else lsm_launch<K, RU, false>(a, blocks, threads, s);
+        if (R == 1) lsm_launch<K, 1, false>(g, s);
+        else lsm_launch<K, RU, false>(g, s);
     }
 }
 
@@ -314,23 +198,15 @@ void lsm_dispatch(const MtgLsMultiArgs &a, int R, int weighted, int64_t blocks, 
 
 int mtg_launch_lomb_scargle_multi_powers(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls, hipStream_t s)
 {
-    const int R = mtg_ls_multi_tile(q.nterms, q.L, q.t_stride == 0, q.weighted);
-    if (R < 1) return 0;
-    // narrow frequency lists leave most of a wide workgroup idle: one or two waves then (the arithmetic of a lane is the same)
-    const int threads = q.F <= 64 ? 64 : q.F <= 128 ? 128 : MTG_LS_THREADS;
-    const int64_t nfb = (q.F + threads - 1) / threads, tiles = (Ls + R - 1) / R;
-    if (nfb > 0x7fffffff / tiles) return 0;
-    MtgLsMultiArgs a;
-    a.dxt = q.dxt; a.yv = q.yv; a.N = q.N; a.t_stride = q.t_stride; a.l0 = l0; a.Ls = Ls;
-    a.stats = reinterpret_cast<const double4 *>(q.stats); a.F = q.F; a.freqs = q.freqs; a.nfb = (int)nfb;
-    a.normalization = q.normalization; a.power = q.power;
-    const int64_t blocks = nfb * tiles;
+    const int R = mtg_ls_tile(q.nterms, q.L, q.t_stride == 0, q.weighted);
+    MtgLsLaunch g;
+    if (R < 1 || !mtg_ls_plan_launch(q, R, l0, Ls, &g)) return 0;
     switch (q.nterms) {
-    case 2: lsm_dispatch<2>(a, R, q.weighted, blocks, threads, s); break;
-    case 3: lsm_dispatch<3>(a, R, q.weighted, blocks, threads, s); break;
-    case 4: lsm_dispatch<4>(a, R, q.weighted, blocks, threads, s); break;
-    case 5: lsm_dispatch<5>(a, R, q.weighted, blocks, threads, s); break;
-    default: return 0;
+    case 2: lsm_dispatch<2>(g, R, q.weighted, s); break;
+    case 3: lsm_dispatch<3>(g, R, q.weighted, s); break;
+    case 4: lsm_dispatch<4>(g, R, q.weighted, s); break;
+    case 5: lsm_dispatch<5>(g, R, q.weighted, s); break;
+    default: return 0;   // (one term: mtg_lomb_scargle.hip)
     }
     return 1;
 }

@@ -4,7 +4,7 @@ is the GPU side).
 * astropy's chi2 form in numpy float64 (tests/lomb_scargle_multi_numpy.py) against the 50-digit truths of
   tests/golden/lomb_scargle_multi_golden.npz (scripts/make_lomb_scargle_multi_golden.py), and the fixture holds what the
   GPU test relies on; its K = 1 is the tau-free formula of tests/lomb_scargle_numpy.py;
-* the tile planner (csrc/mtg_ls_multi_plan.h through tests/ls_multi_plan_driver.cpp) against a restatement;
+* the tile planner (csrc/mtg_ls_plan.h through tests/ls_multi_plan_driver.cpp) against a restatement, one term included;
 * periodogram.LombScargle takes nterms = 1, 3, 4, 5 and still refuses what the device does not do;
 * the header declares both new entries, the library exports them and the engine binds them with the header's arity.
 """
@@ -93,10 +93,13 @@ def test_one_term_is_the_tau_free_formula(case):
 
 
 def planned_tile(nterms, L, shared, weighted):
-    """mtg_ls_multi_plan.h restated: the largest tile whose running and chunk sums stay within 96 doubles per lane
-    (2 x 6 K R weighted; 2 x (2 K R + 4 K) unweighted, R even: the chunk holds pairs), 1 without shared sampling"""
+    """mtg_ls_plan.h restated: the largest tile whose running and chunk sums stay within 96 doubles per lane
+    (2 x 6 K R weighted; 2 x (2 K R + 4 K) unweighted, R even: the chunk holds pairs), 1 without shared sampling.  One
+    term has the rule of its own kernel: 4 up to four light curves, else 8 weighted and 16 unweighted."""
     if not shared or L <= 1:
         return 1
+    if nterms == 1:
+        return 4 if L <= 4 else 8 if weighted else 16
     if weighted:
         return max(r for r in range(1, 17) if 2 * 6 * nterms * r <= 96 or r == 1)
     return max(r for r in range(2, 17, 2) if 2 * (2 * nterms * r + 4 * nterms) <= 96)
@@ -107,7 +110,7 @@ def test_planner_against_its_restatement():
         exe = os.path.join(tmp, "ls_multi_plan_driver")
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "mind_the_gaps_amd", "csrc"),
                                os.path.join(HERE, "ls_multi_plan_driver.cpp"), "-o", exe])
-        cases = [(K, L, shared, weighted) for K in (2, 3, 4, 5) for L in (1, 2, 3, 4, 5, 8, 9, 11, 37, 2000, 10 ** 6)
+        cases = [(K, L, shared, weighted) for K in (1, 2, 3, 4, 5) for L in (1, 2, 3, 4, 5, 8, 9, 11, 37, 2000, 10 ** 6)
                  for shared in (0, 1) for weighted in (0, 1)]
         r = subprocess.run([exe], input="".join("%d %d %d %d\n" % c for c in cases), capture_output=True, text=True, check=True)
         got = [int(v) for v in r.stdout.split()]
@@ -117,8 +120,13 @@ def test_planner_against_its_restatement():
         # the budget of the issue: K = 5 weighted does not carry the one-term kernel's R = 8
         full = {(K, w): planned_tile(K, 100, 1, w) for K in (2, 3, 4, 5) for w in (0, 1)}
         assert full == {(2, 1): 4, (3, 1): 2, (4, 1): 2, (5, 1): 1, (2, 0): 10, (3, 0): 6, (4, 0): 4, (5, 0): 2}
-        # outside 2 .. 5 there is no tile to launch
-        r = subprocess.run([exe], input="1 10 1 1\n6 10 1 0\n", capture_output=True, text=True, check=True)
+        # one term, pinned for every L above: 1 alone or on a sampling of its own, 4 up to four light curves, then 8 / 16
+        for L in (1, 2, 3, 4, 5, 8, 9, 11, 37, 2000, 10 ** 6):
+            for weighted in (0, 1):
+                assert got[cases.index((1, L, 0, weighted))] == 1
+                assert got[cases.index((1, L, 1, weighted))] == (1 if L <= 1 else 4 if L <= 4 else 8 if weighted else 16)
+        # outside 1 .. 5 there is no tile to launch
+        r = subprocess.run([exe], input="0 10 1 1\n6 10 1 0\n", capture_output=True, text=True, check=True)
         assert r.stdout.split() == ["0", "0"]
 
 
