@@ -213,6 +213,34 @@ void mtg_launch_gp_cond_scatter(const MtgGpCondDrawArgs &, hipStream_t);
 #ifndef MTG_DRAW_T
 #define MTG_DRAW_T 32
 #endif
+#define MTG_DRAW_TS (MTG_DRAW_T + 1)
+static_assert(MTG_DRAW_T % 16 == 0 && 64 % MTG_DRAW_T == 0, "the tile's conflict-free stride and its transposed form");
+
+// The tile of a 64-lane workgroup that owns rows [r0, r0 + 64) of g [B][N] (mtg_gp_draw.hip, mtg_whiten.hip): samples
+// [n0, n0 + nt), nt <= MTG_DRAW_T, between global memory and lane-major rows of `tile` [64][MTG_DRAW_TS], transposed on
+// the way -- one load or store instruction covers 64 / MTG_DRAW_T rows x MTG_DRAW_T consecutive samples.  No barrier in
+// either: the kernel places its own around them.
+__device__ __forceinline__ void mtg_tile_load(double *tile, const double *g, int64_t r0, int64_t B, int64_t N, int64_t n0, int nt)
+{
+    constexpr int RPI = 64 / MTG_DRAW_T;              // rows per transposed instruction
+    const int tr = (int)threadIdx.x / MTG_DRAW_T, tc = (int)threadIdx.x % MTG_DRAW_T;
+#pragma unroll 4
+    for (int i = 0; i < 64; i += RPI) {
+        const int rr = i + tr;
+        if (r0 + rr < B && tc < nt) tile[rr * MTG_DRAW_TS + tc] = g[(r0 + rr) * N + n0 + tc];
+    }
+}
+
+__device__ __forceinline__ void mtg_tile_store(double *g, const double *tile, int64_t r0, int64_t B, int64_t N, int64_t n0, int nt)
+{
+    constexpr int RPI = 64 / MTG_DRAW_T;
+    const int tr = (int)threadIdx.x / MTG_DRAW_T, tc = (int)threadIdx.x % MTG_DRAW_T;
+#pragma unroll 4
+    for (int i = 0; i < 64; i += RPI) {
+        const int rr = i + tr;
+        if (r0 + rr < B && tc < nt) g[(r0 + rr) * N + n0 + tc] = tile[rr * MTG_DRAW_TS + tc];
+    }
+}
 
 struct MtgGpDrawArgs : MtgRowArgs {     // of yv only the sigma^2 half is read
     const double *normals;  // [B][N] standard normals of this slab, or NULL: Philox on the device

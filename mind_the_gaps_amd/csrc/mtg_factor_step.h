@@ -1,6 +1,15 @@
 // mtg_factor_step.h -- the forward step of the semiseparable factorisation with the state in registers (template on
-// the rank J, runtime split NR real slots | complex pairs): coefficient load, generators, decay, the (S, f)
-// recurrence and the pivot; and the switch from a runtime rank to the template.  Shared by mtg_predict_at.hip (factorisation + replay), mtg_gp_draw.hip (the draw y = L sqrt(D) q) and mtg_gp_cond_draw.hip (the same draw on the merged series).
+// the rank J, runtime split NR real slots | complex pairs): coefficient load and row constants, generators, decay, the
+// (S, f) recurrence and the pivot; the state of a forward sweep with its innovation step (PatState); the backward
+// recurrences; and the switch from a runtime rank to the template.
+// Shared by
+//   mtg_predict_at.hip       the factorisation, written out from the step functions (its z is taken off y - mean term by
+//                            term, a rounding of its own), and, through mtg_pat_replay.h, the replay at new times
+//   mtg_predict_terms.hip    the same replay (mtg_pat_replay.h)
+//   mtg_gp_draw.hip          PatState::advance: the draw y = mean + L sqrt(D) q
+//   mtg_whiten.hip           PatState::advance: its inverse q = D^-1/2 L^-1 (y - mean)
+//   mtg_gp_cond_draw.hip     PatState::advance on the merged series
+//   mtg_loglike_grad.hip     the step functions, interleaved with those of mtg_factor_step_tangent.h
 #pragma once
 #include "mtg_math.h"
 #include "mtg_device.h"
@@ -39,6 +48,21 @@ __device__ __forceinline__ void pat_load_coef(const MtgRowArgs &a, int64_t e, Pa
     k.asum = cf[a.lay.asum() * cs];
     k.slope = cf[a.lay.mean(0) * cs];
     k.icpt = cf[a.lay.mean(1) * cs];
+}
+
+// the constants of row e: the diagonal's asum and the mean's slope and intercept into k, and for J > 0 the terms beside
+// them; J = 0 is the white model, which has no term to load (JA: the rank the arrays are sized for, at least 1)
+template <int J, int JA>
+__device__ __forceinline__ void pat_load_row(const MtgRowArgs &a, int64_t e, PatCoef<JA> &k)
+{
+    if constexpr (J > 0) {
+        static_assert(J == JA, "the rank of the coefficients");
+        pat_load_coef<J>(a, e, k);
+    } else {
+        k.asum = a.coef[a.lay.asum() * a.cstride + e];
+        k.slope = a.coef[a.lay.mean(0) * a.cstride + e];
+        k.icpt = a.coef[a.lay.mean(1) * a.cstride + e];
+    }
 }
 
 // generators at time t: the phase at the elapsed time, reduced modulo 2 pi before it is rounded (mtg_math.h)
@@ -96,6 +120,43 @@ __device__ __forceinline__ void pat_pivot(const double *S, const double *U, cons
         D -= U[i] * q;
     }
 }
+
+// The state of a forward sweep, one lane per row: S, f of the recurrence and what the sample before has left -- its
+// W (divided by D), its pivot D and its innovation v (z of the likelihood, sqrt(D) q of a draw).
+template <int J>
+struct PatState {
+    double S[J * (J + 1) / 2], f[J], Wp[J], Dp, vp;
+
+    __device__ __forceinline__ void reset()
+    {
+#pragma unroll
+        for (int i = 0; i < J * (J + 1) / 2; ++i) S[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < J; ++i) { f[i] = 0.0; Wp[i] = 0.0; }
+        Dp = 1.0; vp = 0.0;
+    }
+
+    // the innovation step of the sample at time t, dx after the one before: decay, generators, (S, f) forward, then the
+    // pivot.  D comes in as the sample's diagonal (sigma^2 + asum; k(0) at a noise-free new time) and goes out as its
+    // pivot; -> U^T f, what the samples before predict of this one.  The caller forms the innovation v from it and
+    // hands (D, v) back with leave(); W of this sample is kept here.
+    __device__ __forceinline__ double advance(const PatCoef<J> &k, double dx, double t, double t_first, double &D)
+    {
+#pragma clang fp contract(off)
+        double U[J], V[J], ph[J], Wn[J], uf = 0.0;
+        pat_decay<J>(k, dx, ph);
+        pat_generators<J>(k, t, t_first, U, V);
+        pat_fwd_step<J>(S, f, ph, Wp, Dp, vp);
+#pragma unroll
+        for (int i = 0; i < J; ++i) uf += U[i] * f[i];
+        pat_pivot<J>(S, U, V, Wn, D);
+#pragma unroll
+        for (int i = 0; i < J; ++i) Wp[i] = Wn[i] / D;
+        return uf;
+    }
+
+    __device__ __forceinline__ void leave(double D, double v) { Dp = D; vp = v; }
+};
 
 // ---- the backward recurrences of the new-time prediction (mtg_predict_at.hip, mtg_predict_terms.hip) ----
 // g <- phn o (g + Un xn): g_n from g_{n+1} and sample n + 1

@@ -27,13 +27,14 @@
 #include "mtg_math.h"
 #include "mtg_device.h"
 #include "mtg_factor_step.h"
+#include "mtg_pat_replay.h"
 #include "mtg_sampler_dev.h"
 
 template <int J, bool GIVEN>
 __global__ void __launch_bounds__(64) mtg_gp_cond_draw_kernel(MtgGpCondDrawArgs a)
 {
 #pragma clang fp contract(off)
-    constexpr int JA = J > 0 ? J : 1, SY = JA * (JA + 1) / 2;
+    constexpr int JA = J > 0 ? J : 1;
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // row of this slab
     if (r >= a.B) return;
     const int64_t e = a.row0 + r;                                       // row of the batch
@@ -44,25 +45,16 @@ __global__ void __launch_bounds__(64) mtg_gp_cond_draw_kernel(MtgGpCondDrawArgs 
     double *data = a.data + r * N, *fs = a.fs + r * Mu;
 
     PatCoef<JA> k;
-    double asum;
-    if constexpr (J > 0) {
-        pat_load_coef<J>(a, e, k);
-        asum = k.asum;
-    } else {
-        asum = a.coef[a.lay.asum() * a.cstride + e];
-    }
-    double S[SY], f[JA], Wp[JA], U[JA], V[JA], ph[JA];
-#pragma unroll
-    for (int i = 0; i < SY; ++i) S[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < JA; ++i) { f[i] = 0.0; Wp[i] = 0.0; }
+    pat_load_row<J>(a, e, k);
+    PatState<JA> st;
+    st.reset();
     const double t_first = dxt[0].y;
     // the next epoch (its time, y and sigma^2) and the next new time wait in registers, fetched as soon as the one before
     // is taken, so that the loads run under the step's arithmetic; +inf: none left (the times are finite)
     double te = t_first, tn = Mu > 0 ? a.tu[0] : INFINITY;
     double2 ye = yv[0];
     double tp = tn < te ? tn : te;                                      // the merged point before this one
-    double Dp = 1.0, vp = 0.0, qe0 = 0.0, qe1 = 0.0, qn0 = 0.0, qn1 = 0.0;
+    double qe0 = 0.0, qe1 = 0.0, qn0 = 0.0, qn1 = 0.0;
     bool bad = false;
     const uint64_t g = (uint64_t)(a.draw0 + e);                         // global index of this draw: random counters only
 
@@ -86,23 +78,16 @@ __global__ void __launch_bounds__(64) mtg_gp_cond_draw_kernel(MtgGpCondDrawArgs 
         else te = INFINITY;
         double out = 0.0;
         if (J > 0 || !fresh) {
-            double D = fresh ? 0.0 : dn + asum, uf = 0.0;
+            double D = fresh ? 0.0 : dn + k.asum, uf = 0.0;
             if constexpr (J > 0) {
                 if (fresh) D = k.k0;
-                pat_decay<J>(k, t - tp, ph);
-                pat_generators<J>(k, t, t_first, U, V);
-                pat_fwd_step<J>(S, f, ph, Wp, Dp, vp);
-                double Wn[J];
-#pragma unroll
-                for (int i = 0; i < J; ++i) uf += U[i] * f[i];
-                pat_pivot<J>(S, U, V, Wn, D);
-#pragma unroll
-                for (int i = 0; i < J; ++i) Wp[i] = Wn[i] / D;
+                uf = st.advance(k, t - tp, t, t_first, D);
             }
             bad = bad || !(D > 0.0);
             const double v = sqrt(D) * qi;
             out = v + uf;
-            Dp = D; vp = v; tp = t;
+            st.leave(D, v);
+            tp = t;
         }
         if (fresh) fs[at] = out;
         else data[at] = yn - out;
@@ -114,10 +99,8 @@ __global__ void __launch_bounds__(64) mtg_gp_cond_draw_kernel(MtgGpCondDrawArgs 
 __global__ void __launch_bounds__(64) mtg_gp_cond_scatter_kernel(MtgGpCondDrawArgs a)
 {
 #pragma clang fp contract(off)
-    const int64_t mblocks = (a.M + 63) / 64;
-    const int64_t r = (int64_t)blockIdx.x / mblocks;
-    const int64_t m = ((int64_t)blockIdx.x % mblocks) * 64 + threadIdx.x;
-    if (r >= a.B || m >= a.M) return;
+    int64_t r, m;
+    if (!pat_row_time(a.B, a.M, r, m)) return;
     const int64_t u = a.inv[m];
     a.y[r * a.M + m] = a.status[a.row0 + r] == MTG_ST_OK ? a.mu[r * a.Mu + u] + a.fs[r * a.Mu + u] : NAN;
 }

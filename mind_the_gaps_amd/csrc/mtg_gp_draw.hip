@@ -43,15 +43,12 @@ namespace {
 enum { PURPOSE_GP_DRAW = 12 };
 }
 
-#define MTG_DRAW_TS (MTG_DRAW_T + 1)
-static_assert(MTG_DRAW_T % 16 == 0 && 64 % MTG_DRAW_T == 0, "the tile's conflict-free stride and its transposed form");
-
 template <int J, bool GIVEN>
 __global__ void __launch_bounds__(64) mtg_gp_draw_kernel(MtgGpDrawArgs a)
 {
 #pragma clang fp contract(off)
-    constexpr int JA = J > 0 ? J : 1, SY = JA * (JA + 1) / 2;
-    constexpr int T = MTG_DRAW_T, TS = MTG_DRAW_TS, RPI = 64 / T;    // rows per transposed load / store instruction
+    constexpr int JA = J > 0 ? J : 1;
+    constexpr int T = MTG_DRAW_T, TS = MTG_DRAW_TS;
     __shared__ double s_y[64 * TS];
     __shared__ double s_q[GIVEN ? 64 * TS : 1];
     const int lane = (int)threadIdx.x;
@@ -63,39 +60,22 @@ __global__ void __launch_bounds__(64) mtg_gp_draw_kernel(MtgGpDrawArgs a)
     const int64_t N = a.N;
     const int64_t lc = a.lc_index ? a.lc_index[e] : 0;
     const double2 *yv = a.yv + lc * N, *dxt = a.dxt + lc * a.t_stride;
-    const int tr = lane / T, tc = lane % T;           // this lane's place in a transposed instruction
 
     PatCoef<JA> k;
-    double asum = 0.0, slope = 0.0, icpt = 0.0;
-    if (live) {
-        if constexpr (J > 0) {
-            pat_load_coef<J>(a, e, k);
-            asum = k.asum; slope = k.slope; icpt = k.icpt;
-        } else {                                      // a white model: no term to load, the diagonal and the mean only
-            asum = a.coef[a.lay.asum() * a.cstride + e];
-            slope = a.coef[a.lay.mean(0) * a.cstride + e];
-            icpt = a.coef[a.lay.mean(1) * a.cstride + e];
-        }
-    }
-    double S[SY], f[JA], Wp[JA], U[JA], V[JA], ph[JA];
-#pragma unroll
-    for (int i = 0; i < SY; ++i) S[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < JA; ++i) { f[i] = 0.0; Wp[i] = 0.0; }
+    k.asum = 0.0; k.slope = 0.0; k.icpt = 0.0;
+    if (live) pat_load_row<J>(a, e, k);
+    PatState<JA> st;
+    st.reset();
     const double t_first = dxt[0].y;
-    double Dp = 1.0, vp = 0.0, qa = 0.0, qb = 0.0;
+    double qa = 0.0, qb = 0.0;
     bool bad = false;
     const uint64_t g = (uint64_t)(a.draw0 + e);       // global index of this draw: random counters only
 
     for (int64_t n0 = 0; n0 < N; n0 += T) {
         const int nt = N - n0 < T ? (int)(N - n0) : T;
         if constexpr (GIVEN) {
-            // the caller's normals of samples [n0, n0 + nt) of this workgroup's rows, transposed into lane-major rows
-#pragma unroll 4
-            for (int i = 0; i < 64; i += RPI) {
-                const int rr = i + tr;
-                if (r0 + rr < a.B && tc < nt) s_q[rr * TS + tc] = a.normals[(r0 + rr) * N + n0 + tc];
-            }
+            // the caller's normals of samples [n0, n0 + nt) of this workgroup's rows
+            mtg_tile_load(s_q, a.normals, r0, a.B, N, n0, nt);
             __syncthreads();
         }
         if (live) {
@@ -110,33 +90,18 @@ __global__ void __launch_bounds__(64) mtg_gp_draw_kernel(MtgGpDrawArgs a)
                     qn = (j & 1) ? qb : qa;
                 }
                 const double dx = dxt[n].x, t = dxt[n].y;
-                double D = yv[n].y + asum, uf = 0.0;
-                if constexpr (J > 0) {
-                    pat_decay<J>(k, dx, ph);
-                    pat_generators<J>(k, t, t_first, U, V);
-                    pat_fwd_step<J>(S, f, ph, Wp, Dp, vp);
-                    double Wn[J];
-#pragma unroll
-                    for (int i = 0; i < J; ++i) uf += U[i] * f[i];
-                    pat_pivot<J>(S, U, V, Wn, D);
-#pragma unroll
-                    for (int i = 0; i < J; ++i) Wp[i] = Wn[i] / D;
-                }
+                double D = yv[n].y + k.asum, uf = 0.0;
+                if constexpr (J > 0) uf = st.advance(k, dx, t, t_first, D);
                 bad = bad || !(D > 0.0);
                 const double v = sqrt(D) * qn;
-                s_y[lane * TS + j] = (slope * t + icpt) + (v + uf);
-                Dp = D; vp = v;
+                s_y[lane * TS + j] = (k.slope * t + k.icpt) + (v + uf);
+                st.leave(D, v);
             }
         } else {
             for (int j = 0; j < nt; ++j) s_y[lane * TS + j] = NAN;
         }
         __syncthreads();
-        // the tile, transposed: each store instruction covers RPI rows x T consecutive samples
-#pragma unroll 4
-        for (int i = 0; i < 64; i += RPI) {
-            const int rr = i + tr;
-            if (r0 + rr < a.B && tc < nt) a.y[(r0 + rr) * N + n0 + tc] = s_y[rr * TS + tc];
-        }
+        mtg_tile_store(a.y, s_y, r0, a.B, N, n0, nt);
         __syncthreads();                              // the next tile overwrites s_y (and s_q)
     }
     // a non-positive pivot is known for certain only at the end: the row reads back NaN (a rare row, stored lane-wise).

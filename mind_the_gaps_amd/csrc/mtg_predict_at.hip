@@ -30,12 +30,13 @@
 // Lanes of a wave work on one parameter vector and, the times being handed over in ascending order, on neighbouring
 // t*: they replay the same stored rows, which the vector memory path serves as one broadcast access.
 // Both are templates on J so that S, G and the generators live in registers (no scratch; the generic-J
-// mtg_predict_kernel spills by design).  The replay uses the very step functions of the factorisation, so the S and G it
-// rebuilds are bit for bit those the stored W, D, x were made from; each (row, t*) is a lane of its own, so its
+// mtg_predict_kernel spills by design).  The replay (mtg_pat_replay.h, shared with mtg_predict_terms.hip) uses the very
+// step functions of the factorisation, so the S and G it rebuilds are bit for bit those the stored W, D, x were made from; each (row, t*) is a lane of its own, so its
 // result does not depend on the batch, on M or on the order of ts.
 #include "mtg_math.h"
 #include "mtg_device.h"
 #include "mtg_factor_step.h"
+#include "mtg_pat_replay.h"
 // DATA: row r of a.data stands in for the light curve's y (the conditional draw conditions on y - y~, mtg_gp_cond_draw.hip)
 template <int J, bool DATA>
 __global__ void __launch_bounds__(64) mtg_predict_at_factor_kernel(MtgPredictAtArgs a)
@@ -158,11 +159,9 @@ template <int J>
 __global__ void __launch_bounds__(64) mtg_predict_at_eval_kernel(MtgPredictAtArgs a)
 {
 #pragma clang fp contract(off)
-    constexpr int SY = J * (J + 1) / 2, CK = SY + J, stride = 3 * J + 3;
-    const int64_t mblocks = (a.M + 63) / 64;
-    const int64_t r = (int64_t)blockIdx.x / mblocks;
-    const int64_t m = ((int64_t)blockIdx.x % mblocks) * 64 + threadIdx.x;
-    if (r >= a.B || m >= a.M) return;
+    constexpr int SY = J * (J + 1) / 2;
+    int64_t r, m;
+    if (!pat_row_time(a.B, a.M, r, m)) return;
     const int64_t e = a.row0 + r;
     const int64_t slot = a.order ? a.order[m] : m;     // the times are visited in ascending order, stored where they were given
     if (a.status[e] != MTG_ST_OK) {
@@ -172,143 +171,30 @@ __global__ void __launch_bounds__(64) mtg_predict_at_eval_kernel(MtgPredictAtArg
     }
     PatCoef<J> k;
     pat_load_coef<J>(a, e, k);
-    const int64_t lc = a.lc_index ? a.lc_index[e] : 0;
-    const int64_t N = a.N;
-    const double2 *dxt = a.dxt + lc * a.t_stride;
-    const double *wk = a.work + r * N * stride;
-    const double *ckf = a.ckf + r * a.nck * CK, *ckb = a.ckb + r * a.nck * CK;
+    const PatRow<J> w(a, r, e);
     const double ts = a.ts[slot];
+    const int64_t n0 = pat_locate(w.dxt, w.N, ts);
 
-    // n0: the last sample with t_n <= t* (-1: none)
-    int64_t lo = 0, hi = N;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (dxt[mid].y <= ts) lo = mid + 1; else hi = mid;
-    }
-    const int64_t n0 = lo - 1;
-
-    double Us[J], Wt[J], ph[J], T[SY], v[J];
-    {
-        double Vs[J];
-        pat_generators<J>(k, ts, dxt[0].y, Us, Vs);
-#pragma unroll
-        for (int i = 0; i < J; ++i) Wt[i] = Vs[i];
-    }
+    double Us[J], Wt[J], ph[J], T[SY], v[J];           // Wt: V* until q = S* U* is taken off it; T, v: (S*, f*), then (X*, g*)
+    pat_generators<J>(k, ts, w.dxt[0].y, Us, Wt);
     double mu = k.slope * ts + k.icpt, var = k.k0;
     if (n0 >= 0) {
-        // (S, f) of the checkpoint at or before n0, the stored steps up to n0, then the partial step to t*
-        const int64_t c0 = n0 / MTG_PAT_C;
-        const double *c = ckf + c0 * CK;
-#pragma unroll
-        for (int i = 0; i < SY; ++i) T[i] = c[i];
-#pragma unroll
-        for (int i = 0; i < J; ++i) v[i] = c[SY + i];
-        double phs[J];
-        pat_decay<J>(k, ts - dxt[n0].y, phs);
-        for (int64_t n = c0 * MTG_PAT_C; n <= n0; ++n) {
-            const double *w = wk + n * stride;
-            double Wn[J];
-#pragma unroll
-            for (int i = 0; i < J; ++i) Wn[i] = w[J + i];
-            if (n < n0) {
-#pragma unroll
-                for (int i = 0; i < J; ++i) ph[i] = w[stride + 2 * J + i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < J; ++i) ph[i] = phs[i];
-            }
-            pat_fwd_step<J>(T, v, ph, Wn, w[3 * J], w[3 * J + 1]);
-        }
-        // (pat_pivot's arithmetic, written out: U*^T q is summed from 0 here, not taken off a pivot)
-        double uq = 0.0, uf = 0.0;
-#pragma unroll
-        for (int i = 0; i < J; ++i) {
-            double q = 0.0;
-#pragma unroll
-            for (int j = 0; j < J; ++j) q += T[pat_sy(i, j)] * Us[j];
-            Wt[i] -= q;
-            uq += Us[i] * q;
-            uf += Us[i] * v[i];
-        }
+        pat_replay_fwd<J>(k, w, n0, ts, T, v);
+        double uq, uf;
+        pat_combine_before<J>(PatHeld<J>{T, v}, Us, Wt, uq, uf);
         mu += uf;
         var -= uq;
     }
     const bool use_G = a.want_var && n0 >= 0;      // before the first sample the variance comes from the reversed sweep
-    if (n0 < N - 1) {
-        // (G, g) of the checkpoint at or after n0 + 1 (beyond the last sample: zero), the stored steps down to n0 + 1,
-        // then the partial step to t*
-        const int64_t n1 = n0 + 1;
-        int64_t p = (n1 + MTG_PAT_C - 1) / MTG_PAT_C * MTG_PAT_C;
-        if (p < N) {
-            const double *c = ckb + (p / MTG_PAT_C) * CK;
-            if (use_G) {
-#pragma unroll
-                for (int i = 0; i < SY; ++i) T[i] = c[i];
-            }
-#pragma unroll
-            for (int i = 0; i < J; ++i) v[i] = c[SY + i];
-        } else {
-            p = N;
-#pragma unroll
-            for (int i = 0; i < SY; ++i) T[i] = 0.0;
-#pragma unroll
-            for (int i = 0; i < J; ++i) v[i] = 0.0;
-        }
-        double Un[J];
-        for (int64_t n = p - 1; n >= n1; --n) {
-            const double *w = wk + n * stride;
-            double xn = 0.0;
-            if (n + 1 < N) {
-#pragma unroll
-                for (int i = 0; i < J; ++i) { Un[i] = w[stride + i]; ph[i] = w[stride + 2 * J + i]; }
-                xn = w[stride + 3 * J + 2];
-            } else {
-#pragma unroll
-                for (int i = 0; i < J; ++i) { Un[i] = 0.0; ph[i] = 0.0; }
-            }
-            pat_bwd_g<J>(v, ph, Un, xn);
-            if (use_G) {
-                double Um[J], Wm[J];
-#pragma unroll
-                for (int i = 0; i < J; ++i) { Um[i] = w[i]; Wm[i] = w[J + i]; }
-                pat_bwd_G<J>(T, ph, Um, Wm, w[3 * J]);
-            }
-        }
-        const double *w = wk + n1 * stride;
-        pat_decay<J>(k, dxt[n1].y - ts, ph);
-#pragma unroll
-        for (int i = 0; i < J; ++i) Un[i] = w[i];
-        pat_bwd_g<J>(v, ph, Un, w[3 * J + 2]);
-        double wg = 0.0;
-#pragma unroll
-        for (int i = 0; i < J; ++i) wg += Wt[i] * v[i];
-        mu += wg;
-        if (use_G) {
-            double wxw = 0.0;
-#pragma unroll
-            for (int i = 0; i < J; ++i) {
-                double s = 0.0;
-#pragma unroll
-                for (int j = 0; j < J; ++j) s += ph[i] * ph[j] * T[pat_sy(i, j)] * Wt[j];
-                wxw += Wt[i] * s;
-            }
-            var -= wxw;
-        }
+    if (n0 < w.N - 1) {
+        pat_replay_bwd<J>(k, w, n0, ts, use_G, T, v, ph);
+        mu += pat_combine_wg<J>(Wt, v);
+        if (use_G) var -= pat_combine_quad<J>(ph, T, Wt);
     }
     if (a.want_var && n0 < 0) {
-        // seen from the other end t* lies after the last sample of the reversed series: var* = k(0) - U'^T S' U'
-        const double *c = a.ckr + r * SY;
-        pat_decay<J>(k, dxt[0].y - ts, ph);
-        double Ur[J], Vr[J], usu = 0.0;
-        pat_generators<J>(k, dxt[N - 1].y, ts, Ur, Vr);
-#pragma unroll
-        for (int i = 0; i < J; ++i) {
-            double q = 0.0;
-#pragma unroll
-            for (int j = 0; j < J; ++j) q += ph[i] * ph[j] * c[pat_sy(i, j)] * Ur[j];
-            usu += Ur[i] * q;
-        }
-        var -= usu;
+        double Ur[J];
+        pat_reversed_at<J>(k, w, ts, ph, Ur);
+        var -= pat_combine_quad<J>(ph, w.ckr, Ur);
     }
     a.mu[r * a.M + slot] = mu;
     if (a.want_var) a.var[r * a.M + slot] = var;
@@ -332,10 +218,8 @@ __global__ void __launch_bounds__(64) mtg_predict_at_white_factor_kernel(MtgPred
 __global__ void __launch_bounds__(64) mtg_predict_at_white_eval_kernel(MtgPredictAtArgs a)
 {
 #pragma clang fp contract(off)
-    const int64_t mblocks = (a.M + 63) / 64;
-    const int64_t r = (int64_t)blockIdx.x / mblocks;
-    const int64_t m = ((int64_t)blockIdx.x % mblocks) * 64 + threadIdx.x;
-    if (r >= a.B || m >= a.M) return;
+    int64_t r, m;
+    if (!pat_row_time(a.B, a.M, r, m)) return;
     const int64_t e = a.row0 + r;
     const bool ok = a.status[e] == MTG_ST_OK;
     const double slope = a.coef[a.lay.mean(0) * a.cstride + e], icpt = a.coef[a.lay.mean(1) * a.cstride + e];
