@@ -57,6 +57,9 @@ int main(void)
         for (k = 0; k < 64; ++k) freqs[k] = 0.01 + 0.005 * k;
         if (mtg_lomb_scargle(ctx, 64, freqs, MTG_LS_STANDARD, 1, NULL, &peak, &at) != MTG_OK) goto fail;
         fprintf(stderr, "Lomb-Scargle peak %.4f at %.3f cycles per unit of time\n", peak, at >= 0 ? freqs[at] : 0.0);
+        /* ... and the highest peak of the epoch-folding periodogram: 8 phase bins counted from time 0 */
+        if (mtg_epoch_fold(ctx, 64, freqs, 8, 0.0, MTG_LS_STANDARD, 1, NULL, &peak, &at) != MTG_OK) goto fail;
+        fprintf(stderr, "epoch-folding peak %.4f at %.3f cycles per unit of time\n", peak, at >= 0 ? freqs[at] : 0.0);
     }
     rc = 0;
 fail:

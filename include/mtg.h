@@ -737,6 +737,50 @@ MTG_API int mtg_lomb_scargle_multi(mtg_ctx *ctx, int64_t F, const double *freqs 
                                    double *peak_power /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
 
 /*
+ * Epoch folding (Leahy et al. 1983) of every resident light curve at freqs [F]: fold at the trial frequency, bin by
+ * phase, and ask how much of the variance the binned profile explains -- the statistic for eclipses, dips and narrow
+ * pulses, where a few harmonics are a poor basis.  Weights w_n, ybar, r_n = y_n - ybar, YY = sum w r^2 and sw exactly as
+ * in mtg_lomb_scargle (weighted: sigma_n^-2 / sum sigma^-2, else 1 / N).  With te_n = fl(t_n - time_0) (one IEEE
+ * subtraction) the bin of sample n at frequency f is
+ *   b_n = floor(nbins frac(f te_n)),   the product f te_n taken EXACTLY, frac(x) = x - floor(x) in [0, 1) also for te < 0
+ * -- a function of the stored doubles alone: a sample whose rounded product crosses a bin edge still lands in the bin of
+ * the exact one (csrc/mtg_ls_phase.h, mtg_cycles_bin: |f te| < 2^47, and what it takes to miss).  Per bin
+ *   W_b = sum_{n in b} w_n,   S_b = sum_{n in b} w_n r_n,   c_b = #{n in b}        (samples ascending, one addition each)
+ *   p = sum_{b : c_b > 0} S_b^2 / W_b                                              (bins ascending, as (S_b S_b) / W_b)
+ * (the kernel skips a bin by W_b > 0, the same unless a weight underflows), and
+ *   power = p / YY (standard), p / (YY - p) (model), -log(1 - p / YY) (log), p sw / 2 (psd)
+ * with the MTG_LS_* constants: p = YY - chi^2 of the best piecewise-constant profile, the quantity mtg_lomb_scargle
+ * normalises.  Leahy's chi^2 is 2 x psd.  YY = 0 behaves as in mtg_lomb_scargle (0 / 0).
+ * Outputs, slabs, stream, the read-only resident set and the peak reduction (NaN passed over; a row of nothing else:
+ * NaN and -1) as for mtg_lomb_scargle.  power[l][k] depends on (light curve l, freqs[k], nbins, time_0, normalization,
+ * weighted) alone, bit for bit: not on L, the tile, F, the order of freqs, or how the sampling is stored.
+ * mtg_last_solver names "mtg_epoch_fold_kernel<R,weighted> lanes T" (R light curves per lane, T lanes per workgroup:
+ * csrc/mtg_ef_plan.h), mtg_last_kernel_ms times the pre-pass and the sweeps.
+ * MTG_E_STATE without light curves; MTG_E_ARG for F < 1, a frequency that is not finite or <= 0, nbins outside
+ * 2 .. MTG_EF_MAX_BINS, a time_0 that is not finite, an unknown normalization, N < 2, or all outputs NULL; the context
+ * works as before after an error.
+ */
+enum { MTG_EF_MAX_BINS = 32 };
+MTG_API int mtg_epoch_fold(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host, cycles per unit time */,
+                           int nbins /* 2 .. MTG_EF_MAX_BINS */, double time_0, int normalization, int weighted,
+                           double *power /* [L][F] host, or NULL */,
+                           double *peak_power /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
+
+/*
+ * The folded profiles themselves: mtg_epoch_fold's sweep storing the bins instead of reducing them.  Each output NULL or
+ * [L][F][nbins] on the host: count = c_b, wsum = W_b, wrsum = S_b as above (the weighted mean of bin b is
+ * ybar + S_b / W_b), varsum = sum_{n in b} sigma_n^2 (the error of an unweighted bin mean is sqrt(varsum) / count).
+ * mtg_epoch_fold's p is, bit for bit, what the formula above gives from wsum and wrsum in that order.
+ * Meant for the few frequencies one looks at: every output stays whole on the device, and a call with
+ * L F nbins > MTG_PF_MAX_ENTRIES (256 MiB of workspace with all four asked for) is refused with MTG_E_ARG.  Other errors
+ * as for mtg_epoch_fold.
+ */
+#define MTG_PF_MAX_ENTRIES ((int64_t)1 << 23)
+MTG_API int mtg_phase_fold(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host */, int nbins, double time_0, int weighted,
+                           int64_t *count /* [L][F][nbins] or NULL */, double *wsum /* W_b */, double *wrsum /* S_b */,
+                           double *varsum /* sum of sigma^2 per bin */);
+
+/*
  * What the periodograms of the resident set say about every frequency: reductions of power[l][k] ACROSS the light
  * curves, without the [L][F] array ever leaving the device.  power[l][k] is, by definition and bit for bit, what
  * mtg_lomb_scargle returns for the same resident set, frequency, normalization and weighting (its launcher computes it).

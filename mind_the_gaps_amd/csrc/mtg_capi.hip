@@ -2604,6 +2604,118 @@ MTG_API int mtg_lomb_scargle_multi(mtg_ctx *ctx, int64_t F, const double *freqs,
     return lomb_scargle_entry(ctx, "mtg_lomb_scargle_multi", F, freqs, nterms, normalization, weighted, power, peak_power, peak_index);
 }
 
+// what mtg_epoch_fold and mtg_phase_fold refuse, in the order of their messages (MTG_OK: nothing)
+static int ef_refuse_call(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nbins, double time_0, int normalization,
+                          bool nothing_asked)
+{
+    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
+    if (nothing_asked) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
+    if (nbins < 2 || nbins > MTG_EF_MAX_BINS) return fail(ctx, MTG_E_ARG, "%s: nbins = %d is outside 2 .. %d", who, nbins, MTG_EF_MAX_BINS);
+    if (!std::isfinite(time_0)) return fail(ctx, MTG_E_ARG, "%s: time_0 = %g is not finite", who, time_0);
+    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
+        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
+    if (ctx->N < 2) return fail(ctx, MTG_E_ARG, "%s: N = %lld < 2 samples", who, (long long)ctx->N);
+    for (int64_t k = 0; k < F; ++k)
+        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
+            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    return MTG_OK;
+}
+
+MTG_API int mtg_epoch_fold(mtg_ctx *ctx, int64_t F, const double *freqs, int nbins, double time_0, int normalization, int weighted,
+                           double *power, double *peak_power, int64_t *peak_index)
+{
+    const char *who = "mtg_epoch_fold";
+    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    int rc = c.ready(false);
+    if (rc) return rc;
+    if ((rc = ef_refuse_call(ctx, who, F, freqs, nbins, time_0, normalization, !power && !peak_power && !peak_index))) return rc;
+    if ((rc = c.begin(false))) return rc;
+    const int64_t L = ctx->L;
+    const MtgEfPlan plan = mtg_ef_plan(nbins, F, L, !ctx->t_per_lc, weighted ? 1 : 0);
+    // the powers of a slab of light curves at a time, as mtg_lomb_scargle: <= 256 MiB of workspace whatever L F is
+    int64_t Ls = ((int64_t)1 << 25) / F;
+    Ls = Ls / plan.tile * plan.tile;
+    if (Ls < plan.tile) Ls = plan.tile;
+    if (Ls > L) Ls = L;
+    DevBuf d_freqs, d_stats, d_power, d_peak, d_index;
+    const bool want_peak = peak_power || peak_index;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_power, (size_t)Ls * (size_t)F * 8},
+               {d_peak, want_peak ? (size_t)L * 8 : 0}, {d_index, want_peak ? (size_t)L * 8 : 0}});
+    c.upload(d_freqs.p, freqs, (size_t)F * 8);
+    MtgEpochFoldArgs qa;
+    qa.ls = ls_resident_args(ctx, 1, normalization, weighted, d_stats.as<double>(), d_power.as<double>());
+    qa.ls.F = F; qa.ls.freqs = d_freqs.as<double>();
+    qa.ls.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.ls.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
+    qa.nbins = nbins; qa.time_0 = time_0;
+    qa.wsum = qa.wrsum = qa.varsum = nullptr; qa.count = nullptr;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_epoch_fold_kernel<%d,%d> lanes %d", plan.tile, weighted ? 1 : 0, plan.lanes);
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
+        c.then([&] { return mtg_launch_epoch_fold(qa, plan, l0, rows, c.s); });
+        if (l0 + rows == L) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });   // mtg_last_kernel_ms: up to the last slab's kernels
+        // (the copy is ordered on the stream: the next slab's kernel overwrites the buffer only after it)
+        if (power) c.gather(power + l0 * F, d_power.p, (size_t)rows * (size_t)F * 8);
+        return c.e;
+    });
+    if (c.ok()) ctx->timed = true;
+    if (peak_power) c.gather(peak_power, d_peak.p, (size_t)L * 8);
+    if (peak_index) c.gather(peak_index, d_index.p, (size_t)L * 8);
+    return c.finish(nullptr);
+}
+
+MTG_API int mtg_phase_fold(mtg_ctx *ctx, int64_t F, const double *freqs, int nbins, double time_0, int weighted, int64_t *count,
+                           double *wsum, double *wrsum, double *varsum)
+{
+    const char *who = "mtg_phase_fold";
+    RowCall c{ctx, who, 0, nullptr, nullptr, 0};
+    int rc = c.ready(false);
+    if (rc) return rc;
+    if ((rc = ef_refuse_call(ctx, who, F, freqs, nbins, time_0, MTG_LS_STANDARD, !count && !wsum && !wrsum && !varsum))) return rc;
+    const int64_t L = ctx->L;
+    // every asked-for output whole on the device: at most MTG_PF_MAX_ENTRIES entries each
+    if (F > MTG_PF_MAX_ENTRIES / nbins || L > MTG_PF_MAX_ENTRIES / (F * nbins))
+        return fail(ctx, MTG_E_ARG, "%s: L F nbins = %lld x %lld x %d exceeds %lld entries per output (fold fewer frequencies per call)", who,
+                    (long long)L, (long long)F, nbins, (long long)MTG_PF_MAX_ENTRIES);
+    if ((rc = c.begin(false))) return rc;
+    const MtgEfPlan plan = mtg_ef_plan(nbins, F, L, !ctx->t_per_lc, weighted ? 1 : 0);
+    const size_t bytes = (size_t)L * (size_t)F * (size_t)nbins * 8;
+    const int64_t Ls = L < 32768 ? L : 32768;   // (a multiple of every tile; the counts' grid has a row per light curve)
+    DevBuf d_freqs, d_stats, d_count, d_wsum, d_wrsum, d_varsum;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_count, count ? bytes : 0}, {d_wsum, wsum ? bytes : 0},
+               {d_wrsum, wrsum ? bytes : 0}, {d_varsum, varsum ? bytes : 0}});
+    c.upload(d_freqs.p, freqs, (size_t)F * 8);
+    MtgEpochFoldArgs qa;
+    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, weighted, d_stats.as<double>(), nullptr);
+    qa.ls.F = F; qa.ls.freqs = d_freqs.as<double>();
+    qa.nbins = nbins; qa.time_0 = time_0;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_epoch_fold_kernel<%d,%d> lanes %d", plan.tile, weighted ? 1 : 0, plan.lanes);
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
+        const int64_t at = l0 * F * nbins;
+        qa.count = count ? d_count.as<int64_t>() + at : nullptr;
+        qa.wsum = wsum ? d_wsum.as<double>() + at : nullptr;
+        qa.wrsum = wrsum ? d_wrsum.as<double>() + at : nullptr;
+        qa.varsum = varsum ? d_varsum.as<double>() + at : nullptr;
+        c.then([&] { return mtg_launch_epoch_fold(qa, plan, l0, rows, c.s); });
+        return c.e;
+    });
+    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+    if (c.ok()) ctx->timed = true;
+    if (count) c.gather(count, d_count.p, bytes);
+    if (wsum) c.gather(wsum, d_wsum.p, bytes);
+    if (wrsum) c.gather(wrsum, d_wrsum.p, bytes);
+    if (varsum) c.gather(varsum, d_varsum.p, bytes);
+    return c.finish(nullptr);
+}
+
 // mtg_lomb_scargle_envelope (nterms = 1) and mtg_lomb_scargle_envelope_multi
 static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization,
                                        int weighted, int Q, const int64_t *ranks, double *order_stat, int64_t *valid,

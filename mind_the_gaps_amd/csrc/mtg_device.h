@@ -308,6 +308,9 @@ struct MtgLombScargleArgs {
 // (0 = more workgroups than a grid holds)
 void mtg_launch_lomb_scargle_stats(const MtgLombScargleArgs &, hipStream_t);
 int mtg_launch_lomb_scargle(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, hipStream_t);
+// the peaks of the rows of power[Ls][F] into peak_power / peak_index at l0, where asked for (mtg_launch_lomb_scargle ends
+// with it; mtg_launch_epoch_fold reduces its own powers by it)
+void mtg_launch_lomb_scargle_peaks(const MtgLombScargleArgs &, int64_t l0, int64_t Ls, hipStream_t);
 // light curves per lane for a set of L: mtg_ls_tile(nterms, L, shared_sampling, weighted)
 #include "mtg_ls_plan.h"
 // the powers of one slab with nterms >= 2 (mtg_lomb_scargle_multi.hip; mtg_launch_lomb_scargle dispatches to it and adds
@@ -339,6 +342,21 @@ hipError_t mtg_launch_ls_envelope_columns(const MtgLsEnvelopeArgs &, hipStream_t
 hipError_t mtg_launch_ls_envelope_ratio_peaks(const MtgLsEnvelopeArgs &, hipStream_t);
 // rocPRIM's temporary storage for a slab of Fs columns (0 on the LDS path)
 size_t mtg_ls_envelope_temp_bytes(int64_t L, int64_t Fs);
+
+// One slab [l0, l0 + Ls) of mtg_epoch_fold / mtg_phase_fold (mtg_epoch_fold.hip; tile and lanes: mtg_ef_plan.h).  `ls`
+// is the resident set, the frequencies and the pre-pass statistics as the Lomb-Scargle launcher takes them, its power and
+// peaks the slab's and the call's (NULL with the bins alone).  The bins of the slab, each NULL or [Ls][F][nbins]: wsum
+// and wrsum from the sweep itself, count and varsum from a pass of their own over the same bins.
+#include "mtg_ef_plan.h"
+struct MtgEpochFoldArgs {
+    MtgLombScargleArgs ls;
+    int nbins;
+    double time_0;
+    double *wsum, *wrsum, *varsum;
+    int64_t *count;
+};
+// (hipErrorInvalidValue: more workgroups than a grid holds)
+hipError_t mtg_launch_epoch_fold(const MtgEpochFoldArgs &, const MtgEfPlan &, int64_t l0, int64_t Ls, hipStream_t);
 
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).

@@ -157,15 +157,15 @@ void ls_launch(const MtgLsLaunch &g, hipStream_t s)
     hipLaunchKernelGGL((mtg_lomb_scargle_kernel<R, WEIGHTED>), dim3((unsigned)g.blocks), dim3(g.threads), 0, s, g.a);
 }
 
+}  // namespace
+
 // the peaks of the slab's rows, where asked for
-void ls_launch_peaks(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls, hipStream_t s)
+void mtg_launch_lomb_scargle_peaks(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls, hipStream_t s)
 {
     if (q.peak_power || q.peak_index)
         hipLaunchKernelGGL(mtg_lomb_scargle_peak_kernel, dim3((unsigned)Ls), dim3(MTG_LS_THREADS), 0, s, q.power, q.F,
                            q.peak_power ? q.peak_power + l0 : nullptr, q.peak_index ? q.peak_index + l0 : nullptr);
 }
-
-}  // namespace
 
 void mtg_launch_lomb_scargle_stats(const MtgLombScargleArgs &q, hipStream_t s)
 {
@@ -192,6 +192,6 @@ int mtg_launch_lomb_scargle(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls,
             else ls_launch<RU, false>(g, s);
         }
     }
-    ls_launch_peaks(q, l0, Ls, s);
+    mtg_launch_lomb_scargle_peaks(q, l0, Ls, s);
     return 1;
 }

@@ -42,6 +42,32 @@ __device__ __forceinline__ void mtg_cycles_sincos(double f, double te, double *s
     *cs = __builtin_fma(-cj.y, s, cj.x * c);
 }
 
+// The phase bin floor(nbins frac(f te)) of the epoch-folding kernels (mtg_epoch_fold.hip), nbins in 2 .. 32, with the
+// product taken exactly as above: f te = p + pe, q = p - rint(p) in [-1/2, 1/2] (exact), so that frac(f te) = q + pe
+// mod 1.  nbins q = hi + lo is an exact pair again.  The integer part is split off as above, by the NEAREST integer:
+// n = rint(hi) and g = hi - n in [-1/2, 1/2] are exact whatever the sign and size of hi (hi - floor(hi) is not: just below
+// an integer, or just below zero, it rounds up to 1), so that nbins frac = n + g + d with d = lo + nbins pe (one fma: one
+// rounding, the sign is that of the exact value) and |g + d| < 1: the bin is n where g + d >= 0 and n - 1 where it is
+// negative -- a sample on or next to a bin edge, the case the rounded product gets wrong, is decided by the sign of what
+// is left there.  A negative bin wraps by nbins.
+// Exact for |f te| < 2^47 (beyond, pe no longer is a small correction) as long as g + d does not round to 0 from a
+// non-zero value, which takes g + lo + nbins pe to cancel to 53 digits with g != 0 and nbins no power of two.
+__device__ __forceinline__ int mtg_cycles_bin(double f, double te, int nbins)
+{
+#pragma clang fp contract(off)
+    const double nb = (double)nbins;
+    const double p = f * te;
+    const double pe = __builtin_fma(f, te, -p);
+    const double q = p - __builtin_rint(p);
+    const double hi = nb * q;
+    const double lo = __builtin_fma(nb, q, -hi);
+    const double n = __builtin_rint(hi);
+    const double s = (hi - n) + __builtin_fma(nb, pe, lo);
+    int b = (int)n - (s < 0.0 ? 1 : 0);
+    if (b < 0) b += nbins;
+    return b < 0 ? 0 : b < nbins ? b : nbins - 1;   // (a finite product is inside already: whatever f te is, the index stays in the bins)
+}
+
 // the table, filled by the whole workgroup (the caller's next barrier publishes it)
 __device__ __forceinline__ void mtg_ls_fill_tab(MtgLsTab *tab)
 {

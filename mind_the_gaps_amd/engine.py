@@ -42,7 +42,7 @@ EXPORTS = (
     "mtg_ensemble_shard_info", "mtg_ensemble_shard_profile", "mtg_ensemble_shard_profile_read",
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
     "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope", "mtg_whiten",
-    "mtg_lomb_scargle_multi", "mtg_lomb_scargle_envelope_multi",
+    "mtg_lomb_scargle_multi", "mtg_lomb_scargle_envelope_multi", "mtg_epoch_fold", "mtg_phase_fold",
 )
 
 # include/mtg.h, MTG_WHITEN_NSTATS and the slots of a row of whiten's stats
@@ -53,6 +53,7 @@ TERMS_MEAN = 1 << 31   # include/mtg.h, MTG_TERMS_MEAN: a mask of predict_terms 
 LS_STANDARD, LS_MODEL, LS_LOG, LS_PSD = range(4)
 LS_NORMALIZATIONS = {"standard": LS_STANDARD, "model": LS_MODEL, "log": LS_LOG, "psd": LS_PSD}
 LS_MAX_TERMS = 5   # include/mtg.h, MTG_LS_MAX_TERMS: the harmonics of lomb_scargle(nterms=...)
+EF_MAX_BINS = 32   # include/mtg.h, MTG_EF_MAX_BINS: the phase bins of epoch_fold and phase_fold
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -60,6 +61,7 @@ EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(cty
 
 
 LombScargleEnvelope = collections.namedtuple("LombScargleEnvelope", "order_stat valid exceed peak_ratio peak_ratio_index")
+PhaseFold = collections.namedtuple("PhaseFold", "count wsum wrsum varsum")
 
 
 class EngineUnavailable(RuntimeError):
@@ -346,6 +348,10 @@ def load_library():
     lib.mtg_lomb_scargle_envelope_multi.restype = c_int
     lib.mtg_lomb_scargle_envelope_multi.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64), _dp,
                                                     ctypes.POINTER(c_i64), _dp, ctypes.POINTER(c_i64), _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_epoch_fold.restype = c_int
+    lib.mtg_epoch_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_phase_fold.restype = c_int
+    lib.mtg_phase_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, ctypes.POINTER(c_i64), _dp, _dp, _dp]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_whiten.restype = c_int
     lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
@@ -435,6 +441,7 @@ class Engine:
         self.device = int(device)
         self.N = 0
         self.L = 0
+        self._first_time = None
         self.P = None
         _register_for_exit(self)
 
@@ -488,11 +495,13 @@ class Engine:
             raise ValueError("the input coordinates must be sorted")  # celerite GP.compute wording
         self._check(rc)
         self.N, self.L = N, L
+        self._first_time = float(t.flat[0])
 
     def set_lightcurves_device(self, N, L, t_ptr, y_ptr, dy_ptr, t_per_lc=False, y_offset_ptr=None):
         self._check(self._lib.mtg_set_lightcurves_device(self._ctx, N, L, t_ptr, int(bool(t_per_lc)),
                                                          y_ptr, dy_ptr, y_offset_ptr))
         self.N, self.L = int(N), int(L)
+        self._first_time = None   # (on the device: epoch_fold and phase_fold then need their time_0 spelled out)
 
     def set_model(self, kinds, full_values, free_index, bounds, mean_kind=MEAN_CONSTANT, extra=None):
         kinds = np.ascontiguousarray(kinds, dtype=np.int32)
@@ -845,6 +854,57 @@ class Engine:
         if power and peak:
             return out, pk, ix
         return out if power else (pk, ix)
+
+    def _fold_epoch(self, time_0):
+        """time_0 of epoch_fold and phase_fold: None = the first time of the first resident light curve"""
+        if time_0 is not None:
+            return float(time_0)
+        if self._first_time is None:
+            raise ValueError("time_0=None needs light curves set from the host (set_lightcurves); pass time_0")
+        return self._first_time
+
+    def epoch_fold(self, freqs, nbins=10, time_0=None, normalization="standard", weighted=True, power=True, peak=False):
+        """Epoch-folding periodogram (Leahy et al. 1983) of every resident light curve at ``freqs`` [F]: the light curve
+        folded at each frequency into ``nbins`` phase bins (2 .. 32) counted from ``time_0`` (None: the first time of the
+        first resident light curve), and ``p = sum_b S_b^2 / W_b``, the variance the binned profile explains, in
+        ``lomb_scargle``'s normalisations -- or ``"chi2"``, Leahy's statistic, ``2 x psd`` (the factor applied on the
+        host).  A sample's bin comes from the exact product ``f (t - time_0)``, so the statistic is a function of the
+        stored numbers alone.  Return shapes as ``lomb_scargle``: ``power`` [L][F], and / or with ``peak``
+        ``(peak_power[L], peak_index[L])``.  A model need not be set (mtg_epoch_fold)."""
+        freqs = _f64(np.atleast_1d(freqs)).ravel()
+        chi2 = isinstance(normalization, str) and normalization == "chi2"
+        if isinstance(normalization, str):
+            if not chi2 and normalization not in LS_NORMALIZATIONS:
+                raise ValueError("normalization must be one of %s" % sorted(list(LS_NORMALIZATIONS) + ["chi2"]))
+            normalization = LS_PSD if chi2 else LS_NORMALIZATIONS[normalization]
+        F, L = len(freqs), int(self.L)
+        out = np.full((L, F), np.nan) if power else None
+        pk = np.full(L, np.nan) if peak else None
+        ix = np.full(L, -1, dtype=np.int64) if peak else None
+        self._check(self._lib.mtg_epoch_fold(self._ctx, F, _ptr(freqs), int(nbins), self._fold_epoch(time_0), int(normalization),
+                                             int(bool(weighted)), _ptr(out), _ptr(pk),
+                                             None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        if chi2:   # (a factor of two is exact: the peaks stay where they are)
+            out = None if out is None else 2.0 * out
+            pk = None if pk is None else 2.0 * pk
+        if power and peak:
+            return out, pk, ix
+        return out if power else (pk, ix)
+
+    def phase_fold(self, freqs, nbins=10, time_0=None, weighted=True):
+        """The folded profiles behind ``epoch_fold``, for the few frequencies one looks at: ``PhaseFold(count, wsum,
+        wrsum, varsum)``, each [L][F][nbins] -- the samples in every phase bin, ``W_b = sum w``, ``S_b = sum w (y - ybar)``
+        with ``lomb_scargle``'s weights and mean, and ``sum sigma^2``.  The weighted mean of a bin is
+        ``ybar + wrsum / wsum``; ``epoch_fold``'s ``p`` is ``sum_b wrsum^2 / wsum`` over the bins with samples, bit for
+        bit.  ``L F nbins`` is limited to 2^23 per call (mtg_phase_fold)."""
+        freqs = _f64(np.atleast_1d(freqs)).ravel()
+        shape = (int(self.L), len(freqs), max(int(nbins), 0))
+        count = np.zeros(shape, dtype=np.int64)
+        wsum, wrsum, varsum = np.full(shape, np.nan), np.full(shape, np.nan), np.full(shape, np.nan)
+        self._check(self._lib.mtg_phase_fold(self._ctx, len(freqs), _ptr(freqs), int(nbins), self._fold_epoch(time_0),
+                                             int(bool(weighted)), count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                             _ptr(wsum), _ptr(wrsum), _ptr(varsum)))
+        return PhaseFold(count, wsum, wrsum, varsum)
 
     def lomb_scargle_envelope(self, freqs, ranks=(), reference=None, scale=None, normalization="standard", weighted=True, nterms=1):
         """What the periodograms of the resident set say about every frequency, reduced ACROSS the light curves on the

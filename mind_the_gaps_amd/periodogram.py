@@ -11,37 +11,21 @@ The periodogram is the generalised (floating-mean) one of Zechmeister & Kuerster
 """
 import numpy as np
 
-from .engine import LS_MAX_TERMS, LS_NORMALIZATIONS
+from .engine import EF_MAX_BINS, LS_MAX_TERMS, LS_NORMALIZATIONS
 
-__all__ = ["LombScargle", "envelope_ranks", "envelope_levels"]
+__all__ = ["LombScargle", "EpochFolding", "phase_fold", "envelope_ranks", "envelope_levels"]
 
 
-class LombScargle:
-    """``LombScargle(t, y, dy=None, fit_mean=True, center_data=True, nterms=1, normalization="standard")``.
+class _Periodogram:
+    """What ``LombScargle`` and ``EpochFolding`` share: the data, astropy's automatic frequency grid, and ``power`` through
+    the process-wide engine.  A statistic says in ``_powers(engine, frequencies, normalization)`` which entry it calls."""
 
-    ``t`` [N] (ascending), ``y`` [N] or [L][N] (L light curves on the sampling ``t``), ``dy`` None (unweighted), a scalar,
-    [N] or [L][N].  ``nterms`` = 1, 3, 4 or 5 harmonics (beyond one: astropy's ``chi2`` method, N >= 2 nterms + 2 samples);
-    ``nterms=2`` raises ``NotImplementedError`` here and runs through ``Engine.lomb_scargle(nterms=2)``.  Only astropy's
-    defaults ``fit_mean=True, center_data=True`` exist on the device; anything else raises ``NotImplementedError``."""
-
-    def __init__(self, t, y, dy=None, fit_mean=True, center_data=True, nterms=1, normalization="standard", device=0):
-        for name, value, only in (("fit_mean", fit_mean, True), ("center_data", center_data, True)):
-            if value != only:
-                raise NotImplementedError("LombScargle(%s=%r): only %s=%r runs on the device" % (name, value, name, only))
-        if nterms == 2:
-            raise NotImplementedError("LombScargle(nterms=2): this class takes nterms = 1, 3, 4, 5; two harmonics run through "
-                                      "Engine.lomb_scargle(nterms=2)")
-        if nterms not in range(1, LS_MAX_TERMS + 1):
-            raise NotImplementedError("LombScargle(nterms=%r): nterms = 1 .. %d run on the device" % (nterms, LS_MAX_TERMS))
-        if normalization not in LS_NORMALIZATIONS:
-            raise ValueError("normalization must be one of %s" % sorted(LS_NORMALIZATIONS))
+    def _set_data(self, t, y, dy, device):
         self.t = np.ascontiguousarray(t, dtype=np.float64)
         self.y = np.ascontiguousarray(y, dtype=np.float64)
         if self.t.ndim != 1 or self.y.ndim not in (1, 2) or self.y.shape[-1] != len(self.t):
             raise ValueError("t must be [N] and y [N] or [L][N]")
         self.dy = None if dy is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dy, dtype=np.float64), self.y.shape))
-        self.normalization = normalization
-        self.nterms = int(nterms)
         self.device = device
 
     def autofrequency(self, samples_per_peak=5, nyquist_factor=5, minimum_frequency=None, maximum_frequency=None):
@@ -68,13 +52,84 @@ class LombScargle:
     def power(self, frequency, normalization=None):
         """The periodogram at ``frequency`` (cycles per unit of ``t``) -> [F], or [L][F] for a set."""
         frequency = np.asarray(frequency, dtype=np.float64)
-        out = self._bound_engine().lomb_scargle(frequency.ravel(), normalization=normalization or self.normalization,
-                                                weighted=self.dy is not None, nterms=self.nterms)
+        out = self._powers(self._bound_engine(), frequency.ravel(), normalization or self.normalization)
         return out.reshape(self.y.shape[:-1] + frequency.shape)
 
     def autopower(self, **kwargs):
         frequency = self.autofrequency(**kwargs)
         return frequency, self.power(frequency)
+
+
+class LombScargle(_Periodogram):
+    """``LombScargle(t, y, dy=None, fit_mean=True, center_data=True, nterms=1, normalization="standard")``.
+
+    ``t`` [N] (ascending), ``y`` [N] or [L][N] (L light curves on the sampling ``t``), ``dy`` None (unweighted), a scalar,
+    [N] or [L][N].  ``nterms`` = 1, 3, 4 or 5 harmonics (beyond one: astropy's ``chi2`` method, N >= 2 nterms + 2 samples);
+    ``nterms=2`` raises ``NotImplementedError`` here and runs through ``Engine.lomb_scargle(nterms=2)``.  Only astropy's
+    defaults ``fit_mean=True, center_data=True`` exist on the device; anything else raises ``NotImplementedError``."""
+
+    def __init__(self, t, y, dy=None, fit_mean=True, center_data=True, nterms=1, normalization="standard", device=0):
+        for name, value, only in (("fit_mean", fit_mean, True), ("center_data", center_data, True)):
+            if value != only:
+                raise NotImplementedError("LombScargle(%s=%r): only %s=%r runs on the device" % (name, value, name, only))
+        if nterms == 2:
+            raise NotImplementedError("LombScargle(nterms=2): this class takes nterms = 1, 3, 4, 5; two harmonics run through "
+                                      "Engine.lomb_scargle(nterms=2)")
+        if nterms not in range(1, LS_MAX_TERMS + 1):
+            raise NotImplementedError("LombScargle(nterms=%r): nterms = 1 .. %d run on the device" % (nterms, LS_MAX_TERMS))
+        if normalization not in LS_NORMALIZATIONS:
+            raise ValueError("normalization must be one of %s" % sorted(LS_NORMALIZATIONS))
+        self._set_data(t, y, dy, device)
+        self.normalization = normalization
+        self.nterms = int(nterms)
+
+    def _powers(self, eng, frequency, normalization):
+        return eng.lomb_scargle(frequency, normalization=normalization, weighted=self.dy is not None, nterms=self.nterms)
+
+
+class EpochFolding(_Periodogram):
+    """``EpochFolding(t, y, dy=None, nbins=10, time_0=None, normalization="standard")``: the epoch-folding periodogram of
+    Leahy et al. (1983) with ``LombScargle``'s interface -- ``power``, ``autofrequency``, ``autopower``.  ``nbins`` phase
+    bins (2 .. 32) counted from ``time_0`` (None: ``t[0]``); ``normalization`` one of ``LombScargle``'s or ``"chi2"``
+    (Leahy's statistic, twice ``"psd"``).  ``Engine.epoch_fold`` has the definition."""
+
+    def __init__(self, t, y, dy=None, nbins=10, time_0=None, normalization="standard", device=0):
+        if nbins not in range(2, EF_MAX_BINS + 1):
+            raise ValueError("nbins must lie in 2 .. %d" % EF_MAX_BINS)
+        if normalization != "chi2" and normalization not in LS_NORMALIZATIONS:
+            raise ValueError("normalization must be one of %s" % sorted(list(LS_NORMALIZATIONS) + ["chi2"]))
+        self._set_data(t, y, dy, device)
+        self.normalization = normalization
+        self.nbins = int(nbins)
+        self.time_0 = None if time_0 is None else float(time_0)
+
+    def _powers(self, eng, frequency, normalization):
+        return eng.epoch_fold(frequency, nbins=self.nbins, time_0=self.time_0, normalization=normalization, weighted=self.dy is not None)
+
+
+def phase_fold(timestamps, y, folding_frequency, dy=None, time_0=0, n_bins=10, device=0):
+    """The reference's ``utils.phase_fold``: the light curve folded at ``folding_frequency`` from ``time_0`` into ``n_bins``
+    phase bins -> ``(bin_means, bin_stds, two_phase_bins)``, each over two cycles: the unweighted mean of every bin, its
+    error ``sqrt(sum dy^2) / count`` (NaN without ``dy``) and the bins' phases.  Computed on the device
+    (``Engine.phase_fold``), with a sample's bin taken from the exact product ``f (t - time_0)``.  Two departures from the
+    reference: the phases returned are the bin centres ``(bins + 0.5) / n_bins`` (the reference's ``bins / n_bins + 0.05``
+    is the centre only for ten bins), and an empty bin is NaN in both arrays without a warning (the reference averages an
+    empty slice, which warns)."""
+    t = np.ascontiguousarray(timestamps, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if t.ndim != 1 or y.shape != t.shape:
+        raise ValueError("timestamps and y must be [N]")
+    fold = EpochFolding(t, y, dy=dy, nbins=n_bins, device=device)
+    count, wsum, wrsum, varsum = (a[0, 0] for a in fold._bound_engine().phase_fold([float(folding_frequency)], nbins=fold.nbins,
+                                                                                   time_0=float(time_0), weighted=False))
+    filled = count > 0
+    bin_means = np.full(fold.nbins, np.nan)
+    bin_stds = np.full(fold.nbins, np.nan)
+    bin_means[filled] = y.mean() + wrsum[filled] / wsum[filled]
+    if dy is not None:
+        bin_stds[filled] = np.sqrt(varsum[filled]) / count[filled]
+    bins = (np.arange(fold.nbins) + 0.5) / fold.nbins
+    return np.hstack([bin_means, bin_means]), np.hstack([bin_stds, bin_stds]), np.hstack([bins, bins + 1])
 
 
 def _virtual_index(L, levels):

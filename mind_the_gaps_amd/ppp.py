@@ -568,7 +568,7 @@ def protassov_test(lightcurve, null_kernel, alt_kernel, nsims=100, walkers=12, m
 
 def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walkers=12, max_steps=500, sigma_noise=None,
                           extension_factor=2, normalization="standard", weighted=True, seed=None, device=0, progress=False,
-                          pdf="Gaussian", max_iter=400, nterms=1):
+                          pdf="Gaussian", max_iter=400, nterms=1, statistic="lomb_scargle", nbins=10):
     """The classic companion of the LRT p-value of ``protassov_test``: is the highest Lomb-Scargle peak of the observed
     light curve unusual among light curves of the null model?
 
@@ -583,18 +583,31 @@ def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walke
     comes from ``default_rng(seed)`` in a fixed order (the chain's seed, the picks, the simulator's seed): the same seed gives
     the same result bit for bit.  ``weighted``: by the error bars, the simulated light curves' own included -- Poisson noise
     at a few counts per epoch leaves epochs with ``dy = 0`` that take all the weight; pass ``weighted=False`` there.
-    ``nterms``: harmonics per frequency of every periodogram (``Engine.lomb_scargle``), for profiles that are not sinusoidal."""
+    ``nterms``: harmonics per frequency of every periodogram (``Engine.lomb_scargle``), for profiles that are not sinusoidal.
+    ``statistic="epoch_fold"``: the peaks of the epoch-folding periodogram instead (``Engine.epoch_fold`` with ``nbins``
+    phase bins counted from the first observed time; ``nterms`` must be 1) -- for dips, eclipses and narrow pulses."""
+    if statistic not in ("lomb_scargle", "epoch_fold"):
+        raise ValueError("statistic must be 'lomb_scargle' or 'epoch_fold'")
+    if statistic == "epoch_fold" and nterms != 1:
+        raise ValueError("statistic='epoch_fold' has no harmonics: nterms must be 1")
     frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
     eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
                                                            extension_factor, seed, device, progress, pdf, max_iter)
-    harmonics = _harmonics(nterms)
-    sim_peaks, _ = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted, power=False, peak=True, **harmonics)
+    times = np.asarray(lightcurve.times, dtype=np.float64)
+    if statistic == "epoch_fold":
+        def peaks(weighted):
+            return eng.epoch_fold(frequencies, nbins=nbins, time_0=float(times[0]), normalization=normalization, weighted=weighted,
+                                  power=False, peak=True)
+    else:
+        def peaks(weighted):
+            return eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted, power=False, peak=True,
+                                    **_harmonics(nterms))
+    sim_peaks, _ = peaks(weighted)
     y = np.asarray(lightcurve.y, dtype=np.float64)
     dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
-    eng.set_lightcurves(np.asarray(lightcurve.times, dtype=np.float64), y, dy)
+    eng.set_lightcurves(times, y, dy)
     eng.bound_to = None
-    obs, at = eng.lomb_scargle(frequencies, normalization=normalization, weighted=weighted and lightcurve.dy is not None,
-                               power=False, peak=True, **harmonics)
+    obs, at = peaks(weighted and lightcurve.dy is not None)
     observed_peak = float(obs[0])
     p_value = (1.0 + float(np.sum(sim_peaks >= observed_peak))) / (1.0 + nsims)
     return dict(observed_peak=observed_peak, observed_frequency=float(frequencies[at[0]]) if at[0] >= 0 else float("nan"),
