@@ -781,6 +781,65 @@ MTG_API int mtg_phase_fold(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] h
                            double *varsum /* sum of sigma^2 per bin */);
 
 /*
+ * Foster's weighted wavelet Z-transform (Foster 1996, AJ 112, 1709) of every resident light curve: the time-frequency
+ * view of a periodicity that comes, goes or drifts.  At one (tau, f) it is mtg_lomb_scargle's floating-mean fit with
+ * every sample also weighted by a Gaussian window centred on tau whose width is a fixed number of cycles.
+ * Inputs: freqs [F] > 0 (cycles per unit time), the window centres taus [T] (finite, any order, inside or outside the
+ * time span), a decay constant c >= 0 (Foster's 1 / (8 pi^2) = MTG_WWZ_DECAY) and the weighting: statistical weights
+ * s_n = sigma_n^-2 (weighted != 0) or 1.  For one (light curve, tau, f):
+ *   te_n = fl(t_n - tau) (one IEEE subtraction),  z_n = f te_n (cycles),
+ *   g_n = exp(-4 pi^2 c z_n^2)  (exp(-z^2 / 2) at the default c),  w_n = s_n g_n,
+ *   r_n = y_n - ybar, ybar the weighted mean of mtg_lomb_scargle's pre-pass (the statistic does not depend on it
+ *   mathematically; it is there for the rounding).
+ * With the weighted means <a> = sum w a / sum w:
+ *   C = <cos 2 pi z>, S = <sin 2 pi z>, CC = <cos^2>, CS = <cos sin>, SS = 1 - CC,
+ *   X = <r>, XX = <r^2>, XC = <r cos>, XS = <r sin>,   N_eff = (sum w)^2 / sum w^2,   V_x = XX - X^2,
+ * centred (CC - C^2, SS - S^2, CS - C S, XC - X C, XS - X S) and put through the 2 x 2 formula of mtg_lomb_scargle, they
+ * give V_y, the variance of the fitted local sinusoid, and its coefficients (a, b).  `statistic` selects what is written:
+ */
+#define MTG_WWZ_POWER     0   /* P = V_y / V_x, in [0, 1]: the local generalised Lomb-Scargle power */
+#define MTG_WWZ_Z         1   /* Z = (N_eff - 3) V_y / (2 (V_x - V_y)): Foster's Z                  */
+#define MTG_WWZ_AMPLITUDE 2   /* sqrt(a^2 + b^2): Foster's WWA                                      */
+#define MTG_WWZ_DECAY 0.012665147955292222   /* 1 / (8 pi^2) */
+/*
+ * A determinant that is not positive gives NaN in that entry, and so does a denominator that is not positive: V_x for
+ * P, V_x - V_y for Z (a window that holds no more than the three fitted parameters, or a fit exact to the last bit; the
+ * peaks pass NaN over, an infinity would be every map's peak).  Otherwise N_eff <= 3 gives whatever the formula gives.
+ * With c = 0, P is mtg_lomb_scargle's standard power -- the same quantity, not the same bits: the phase origin is tau --
+ * and N_eff = (sum s)^2 / sum s^2: N unweighted, less than N with error bars that differ.
+ * Supported range: |f|, |t_n - tau| and their products below about 1e150.  Beyond, (4 pi^2 c f) f or te_n te_n
+ * overflows, the exponent becomes inf - inf or 0 inf = NaN, nothing is cut and the entry is NaN: no error is raised.
+ * Range.  Every quantity above is invariant under a common factor on the weights, so g_n is taken relative to the
+ * largest weight of its (tau, f): the exponent is E_n = ((4 pi^2 c f) f) (te_n te_n - te_* te_*), te_* the te_n of
+ * smallest magnitude (found once per (sampling, tau)), every operation rounded.  The largest weight is then 1 and
+ * sum w >= min s: a centre in the middle of a gap at high frequency gives finite numbers, not 0 / 0 from underflow.
+ * Cut.  A weight whose exponent E_n, as the device forms it, exceeds 80 ln 2 is exactly 0: a decision that depends on
+ * (tau, f, sample) alone and drops less than N 2^-80 of sum w.  A cut sample adds exact zeros, so a workgroup skips
+ * every chunk of 256 samples in which all its lanes' weights are cut -- the samples ascend in time, so the kept chunks are
+ * one range that follows from tau and the workgroup's lowest frequency -- without changing one bit of any lane's result.
+ * One lane owns a frequency, a workgroup one tau and a tile of light curves on shared sampling (csrc/mtg_wwz_plan.h);
+ * samples ascending, a chunk's partial sums from zero, folded into running totals.  out[l][j][k] depends on (light
+ * curve l, freqs[k], taus[j], c, statistic, weighted) alone, bit for bit: not on L, the tile, F or T, the order of freqs
+ * or taus, which frequencies share a workgroup, the slabs, or whether the sampling is stored shared or per light curve.
+ * Against a 50-digit evaluation of Foster's formulas as written (no cut, no rescaling) P is within
+ * max(10 rho, 64 sqrt(N) u kappa), kappa the 2-norm condition number of the normalised 3 x 3 normal matrix, and N_eff
+ * within 64 sqrt(N) u relative (tests/test_wwz_gpu.py).
+ *   out         [L][T][F] (host) or NULL: the statistic
+ *   neff        [L][T][F] (host) or NULL: N_eff
+ *   peak        [L] or NULL: the maximum of light curve l's map;  peak_index [L] or NULL: the first j F + k attaining
+ *               it.  Reduced on the device, NaN entries passed over (a map of nothing else: NaN and -1); with out and
+ *               neff NULL nothing of size L T F comes back.  The device workspace is bounded: slabs of light curves.
+ * MTG_E_STATE without light curves; MTG_E_ARG for F < 1 or T < 1, a frequency that is not finite or <= 0, a tau that is
+ * not finite, a decay that is negative or not finite, an unknown statistic, N < 4, L T F beyond int64, or all outputs
+ * NULL; the context works as before after an error.  mtg_last_solver names "mtg_wwz_kernel<R,weighted> lanes T",
+ * mtg_last_kernel_ms runs from the pre-pass to the last slab's kernels.
+ */
+MTG_API int mtg_wwz(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host, cycles per unit time */,
+                    int64_t T, const double *taus /* [T] host */, double decay, int statistic, int weighted,
+                    double *out /* [L][T][F] host, or NULL */, double *neff /* [L][T][F] host, or NULL */,
+                    double *peak /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
+
+/*
  * What the periodograms of the resident set say about every frequency: reductions of power[l][k] ACROSS the light
  * curves, without the [L][F] array ever leaving the device.  power[l][k] is, by definition and bit for bit, what
  * mtg_lomb_scargle returns for the same resident set, frequency, normalization and weighting (its launcher computes it).

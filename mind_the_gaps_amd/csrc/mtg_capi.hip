@@ -2716,6 +2716,65 @@ MTG_API int mtg_phase_fold(mtg_ctx *ctx, int64_t F, const double *freqs, int nbi
     return c.finish(nullptr);
 }
 
+MTG_API int mtg_wwz(mtg_ctx *ctx, int64_t F, const double *freqs, int64_t T, const double *taus, double decay, int statistic, int weighted,
+                    double *out, double *neff, double *peak, int64_t *peak_index)
+{
+    const char *who = "mtg_wwz";
+    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    int rc = c.ready(false);
+    if (rc) return rc;
+    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
+    if (T < 1 || !taus) return fail(ctx, MTG_E_ARG, "%s: need T >= 1 window centres", who);
+    if (!out && !neff && !peak && !peak_index) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
+    if (!std::isfinite(decay) || decay < 0.0) return fail(ctx, MTG_E_ARG, "%s: decay = %g is not a finite constant >= 0", who, decay);
+    if (statistic < MTG_WWZ_POWER || statistic > MTG_WWZ_AMPLITUDE) return fail(ctx, MTG_E_ARG, "%s: unknown statistic %d", who, statistic);
+    if (ctx->N < 4)
+        return fail(ctx, MTG_E_ARG, "%s: N = %lld < 4 samples (a sinusoid with a floating mean fits three exactly)", who, (long long)ctx->N);
+    const int64_t L = ctx->L;
+    if (T > INT64_MAX / 8 / F || L > INT64_MAX / 8 / (T * F))
+        return fail(ctx, MTG_E_ARG, "%s: L T F = %lld x %lld x %lld is beyond int64", who, (long long)L, (long long)T, (long long)F);
+    for (int64_t k = 0; k < F; ++k)
+        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
+            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    for (int64_t j = 0; j < T; ++j)
+        if (!std::isfinite(taus[j])) return fail(ctx, MTG_E_ARG, "%s: taus[%lld] is not finite", who, (long long)j);
+    if ((rc = c.begin(false))) return rc;
+    const MtgWwzPlan plan = mtg_wwz_plan(F, T, L, !ctx->t_per_lc, weighted ? 1 : 0);
+    const int64_t Ls = plan.slab;
+    const size_t map_bytes = (size_t)T * (size_t)F * 8;
+    const bool want_peak = peak || peak_index, want_values = out || want_peak;
+    DevBuf d_freqs, d_taus, d_stats, d_near, d_out, d_neff, d_peak, d_index;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_taus, (size_t)T * 8}, {d_stats, (size_t)L * 32},
+               {d_near, (size_t)(ctx->t_per_lc ? Ls : 1) * (size_t)T * 8}, {d_out, want_values ? (size_t)Ls * map_bytes : 0},
+               {d_neff, neff ? (size_t)Ls * map_bytes : 0}, {d_peak, want_peak ? (size_t)L * 8 : 0}, {d_index, want_peak ? (size_t)L * 8 : 0}});
+    c.upload(d_freqs.p, freqs, (size_t)F * 8);
+    c.upload(d_taus.p, taus, (size_t)T * 8);
+    MtgWwzArgs qa;
+    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, weighted, d_stats.as<double>(), want_values ? d_out.as<double>() : nullptr);
+    qa.ls.F = F; qa.ls.freqs = d_freqs.as<double>();
+    qa.ls.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.ls.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
+    qa.T = T; qa.taus = d_taus.as<double>(); qa.kc = 39.478417604357434 * decay;   // 4 pi^2
+    qa.statistic = statistic; qa.neff = neff ? d_neff.as<double>() : nullptr; qa.nearest = d_near.as<double>();
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_wwz_kernel<%d,%d> lanes %d", plan.tile, weighted ? 1 : 0, plan.lanes);
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
+        c.then([&] { return mtg_launch_wwz(qa, plan, l0, rows, c.s); });
+        if (l0 + rows == L) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });   // mtg_last_kernel_ms: up to the last slab's kernels
+        // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
+        if (out) c.gather(out + l0 * T * F, d_out.p, (size_t)rows * map_bytes);
+        if (neff) c.gather(neff + l0 * T * F, d_neff.p, (size_t)rows * map_bytes);
+        return c.e;
+    });
+    if (c.ok()) ctx->timed = true;
+    if (peak) c.gather(peak, d_peak.p, (size_t)L * 8);
+    if (peak_index) c.gather(peak_index, d_index.p, (size_t)L * 8);
+    return c.finish(nullptr);
+}
+
 // mtg_lomb_scargle_envelope (nterms = 1) and mtg_lomb_scargle_envelope_multi
 static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization,
                                        int weighted, int Q, const int64_t *ranks, double *order_stat, int64_t *valid,

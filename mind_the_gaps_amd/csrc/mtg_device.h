@@ -358,6 +358,22 @@ struct MtgEpochFoldArgs {
 // (hipErrorInvalidValue: more workgroups than a grid holds)
 hipError_t mtg_launch_epoch_fold(const MtgEpochFoldArgs &, const MtgEfPlan &, int64_t l0, int64_t Ls, hipStream_t);
 
+// One slab [l0, l0 + Ls) of mtg_wwz (mtg_wwz.hip; tile, lanes, slab and grid: mtg_wwz_plan.h).  `ls` is the resident set,
+// the frequencies and the pre-pass statistics as the Lomb-Scargle launcher takes them; its power is the slab's values
+// [Ls][T][F] (NULL: N_eff alone) and its peaks are the call's, reduced over a light curve's whole map.
+#include "mtg_wwz_plan.h"
+struct MtgWwzArgs {
+    MtgLombScargleArgs ls;
+    int64_t T;
+    const double *taus;    // [T] on the device
+    double kc;             // 4 pi^2 decay
+    int statistic;         // MTG_WWZ_*
+    double *neff;          // NULL or [Ls][T][F] of the slab
+    double *nearest;       // workspace [Ls][T] (shared sampling: [T]): the squared distance of tau to its nearest sample
+};
+// (hipErrorInvalidValue: more workgroups than a grid holds, or a plan that is not mtg_wwz_plan's)
+hipError_t mtg_launch_wwz(const MtgWwzArgs &, const MtgWwzPlan &, int64_t l0, int64_t Ls, hipStream_t);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

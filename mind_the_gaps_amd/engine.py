@@ -43,6 +43,7 @@ EXPORTS = (
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
     "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope", "mtg_whiten",
     "mtg_lomb_scargle_multi", "mtg_lomb_scargle_envelope_multi", "mtg_epoch_fold", "mtg_phase_fold",
+    "mtg_wwz",
 )
 
 # include/mtg.h, MTG_WHITEN_NSTATS and the slots of a row of whiten's stats
@@ -54,6 +55,10 @@ LS_STANDARD, LS_MODEL, LS_LOG, LS_PSD = range(4)
 LS_NORMALIZATIONS = {"standard": LS_STANDARD, "model": LS_MODEL, "log": LS_LOG, "psd": LS_PSD}
 LS_MAX_TERMS = 5   # include/mtg.h, MTG_LS_MAX_TERMS: the harmonics of lomb_scargle(nterms=...)
 EF_MAX_BINS = 32   # include/mtg.h, MTG_EF_MAX_BINS: the phase bins of epoch_fold and phase_fold
+# include/mtg.h, MTG_WWZ_*: what wwz writes, and Foster's decay constant 1 / (8 pi^2)
+WWZ_POWER, WWZ_Z, WWZ_AMPLITUDE = range(3)
+WWZ_STATISTICS = {"power": WWZ_POWER, "z": WWZ_Z, "amplitude": WWZ_AMPLITUDE}
+WWZ_DECAY = 0.012665147955292222
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -352,6 +357,8 @@ def load_library():
     lib.mtg_epoch_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
     lib.mtg_phase_fold.restype = c_int
     lib.mtg_phase_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, ctypes.POINTER(c_i64), _dp, _dp, _dp]
+    lib.mtg_wwz.restype = c_int
+    lib.mtg_wwz.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, ctypes.c_double, c_int, c_int, _dp, _dp, _dp, ctypes.POINTER(c_i64)]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_whiten.restype = c_int
     lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
@@ -890,6 +897,36 @@ class Engine:
         if power and peak:
             return out, pk, ix
         return out if power else (pk, ix)
+
+    def wwz(self, freqs, taus, decay=WWZ_DECAY, statistic="z", weighted=True, values=True, neff=False, peak=False):
+        """Foster's weighted wavelet Z-transform (1996) of every resident light curve at ``freqs`` [F] and the window
+        centres ``taus`` [T]: at one ``(tau, f)`` the floating-mean fit of ``lomb_scargle`` with every sample also
+        weighted by ``exp(-4 pi^2 decay (f (t - tau))^2)``, a Gaussian window a fixed number of cycles wide (``decay``
+        defaults to Foster's ``1 / (8 pi^2)``; 0 is no window).  ``statistic``: ``"z"`` (Foster's Z), ``"power"`` (the
+        local Lomb-Scargle power in [0, 1]) or ``"amplitude"`` (Foster's WWA).  -> in this order, whatever is asked for:
+        ``values`` the map [L][T][F], ``neff`` the effective number of samples [L][T][F], ``peak`` the two arrays
+        ``peak[L], peak_index[L]``, the maximum of every light curve's map and the first ``j F + k`` attaining it,
+        reduced on the device -- with ``values=False, neff=False`` nothing of size L T F comes back.  One array asked
+        for comes back bare, several as one flat tuple (as ``lomb_scargle``'s ``(power, peak_power, peak_index)``).  A
+        model need not be set (mtg_wwz)."""
+        freqs = _f64(np.atleast_1d(freqs)).ravel()
+        taus = _f64(np.atleast_1d(taus)).ravel()
+        if isinstance(statistic, str):
+            if statistic not in WWZ_STATISTICS:
+                raise ValueError("statistic must be one of %s" % sorted(WWZ_STATISTICS))
+            statistic = WWZ_STATISTICS[statistic]
+        if not (values or neff or peak):
+            raise ValueError("wwz: nothing asked for (values, neff and peak are all False)")
+        F, T, L = len(freqs), len(taus), int(self.L)
+        out = np.full((L, T, F), np.nan) if values else None
+        ne = np.full((L, T, F), np.nan) if neff else None
+        pk = np.full(L, np.nan) if peak else None
+        ix = np.full(L, -1, dtype=np.int64) if peak else None
+        self._check(self._lib.mtg_wwz(self._ctx, F, _ptr(freqs), T, _ptr(taus), float(decay), int(statistic), int(bool(weighted)),
+                                      _ptr(out), _ptr(ne), _ptr(pk),
+                                      None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        got = ([out] if values else []) + ([ne] if neff else []) + ([pk, ix] if peak else [])
+        return got[0] if len(got) == 1 else tuple(got)
 
     def phase_fold(self, freqs, nbins=10, time_0=None, weighted=True):
         """The folded profiles behind ``epoch_fold``, for the few frequencies one looks at: ``PhaseFold(count, wsum,

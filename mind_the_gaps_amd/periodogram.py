@@ -11,9 +11,9 @@ The periodogram is the generalised (floating-mean) one of Zechmeister & Kuerster
 """
 import numpy as np
 
-from .engine import EF_MAX_BINS, LS_MAX_TERMS, LS_NORMALIZATIONS
+from .engine import EF_MAX_BINS, LS_MAX_TERMS, LS_NORMALIZATIONS, WWZ_DECAY, WWZ_STATISTICS
 
-__all__ = ["LombScargle", "EpochFolding", "phase_fold", "envelope_ranks", "envelope_levels"]
+__all__ = ["LombScargle", "EpochFolding", "WWZ", "phase_fold", "envelope_ranks", "envelope_levels"]
 
 
 class _Periodogram:
@@ -105,6 +105,52 @@ class EpochFolding(_Periodogram):
 
     def _powers(self, eng, frequency, normalization):
         return eng.epoch_fold(frequency, nbins=self.nbins, time_0=self.time_0, normalization=normalization, weighted=self.dy is not None)
+
+
+class WWZ(_Periodogram):
+    """``WWZ(t, y, dy=None, decay=1 / (8 pi^2), statistic="z")``: Foster's weighted wavelet Z-transform (1996), the
+    time-frequency map of a light curve (or of a set [L][N] on the sampling ``t``) -- when was a periodicity there, and did
+    its period move?  ``dy=None`` is unweighted, as in ``LombScargle``; ``decay`` is Foster's c, the window
+    ``exp(-4 pi^2 c (f (t - tau))^2)``; ``statistic`` one of ``"z"``, ``"power"``, ``"amplitude"``.  ``power(frequency,
+    tau)`` and ``neff(frequency, tau)`` return [T][F] (a set: [L][T][F]); ``autofrequency`` is ``LombScargle``'s and
+    ``autotau(n)`` spreads n centres evenly over the time span.  ``Engine.wwz`` has the definition."""
+
+    def __init__(self, t, y, dy=None, decay=WWZ_DECAY, statistic="z", device=0):
+        if statistic not in WWZ_STATISTICS:
+            raise ValueError("statistic must be one of %s" % sorted(WWZ_STATISTICS))
+        if not (np.isfinite(decay) and decay >= 0):
+            raise ValueError("decay must be finite and >= 0")
+        self._set_data(t, y, dy, device)
+        self.decay = float(decay)
+        self.statistic = statistic
+
+    def autotau(self, n=50):
+        """``n`` window centres evenly spaced from the first to the last time"""
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        return np.linspace(self.t.min(), self.t.max(), int(n))
+
+    def _map(self, frequency, tau, statistic, **what):
+        frequency = np.asarray(frequency, dtype=np.float64)
+        tau = np.asarray(tau, dtype=np.float64)
+        if statistic not in WWZ_STATISTICS:
+            raise ValueError("statistic must be one of %s" % sorted(WWZ_STATISTICS))
+        out = self._bound_engine().wwz(frequency.ravel(), tau.ravel(), decay=self.decay, statistic=statistic,
+                                       weighted=self.dy is not None, **what)
+        return out.reshape(self.y.shape[:-1] + (tau.size, frequency.size))
+
+    def power(self, frequency, tau, statistic=None):
+        """The map at ``frequency`` [F] and the centres ``tau`` [T] -> [T][F], or [L][T][F] for a set."""
+        return self._map(frequency, tau, statistic or self.statistic, values=True)
+
+    def neff(self, frequency, tau):
+        """Foster's effective number of samples under the window of every ``(tau, frequency)``: shapes as ``power``."""
+        return self._map(frequency, tau, self.statistic, values=False, neff=True)
+
+    def autopower(self, n_tau=50, **kwargs):
+        """-> ``(frequency, tau, map)`` on ``autofrequency(**kwargs)`` and ``autotau(n_tau)``"""
+        frequency, tau = self.autofrequency(**kwargs), self.autotau(n_tau)
+        return frequency, tau, self.power(frequency, tau)
 
 
 def phase_fold(timestamps, y, folding_frequency, dy=None, time_0=0, n_bins=10, device=0):

@@ -568,7 +568,8 @@ def protassov_test(lightcurve, null_kernel, alt_kernel, nsims=100, walkers=12, m
 
 def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walkers=12, max_steps=500, sigma_noise=None,
                           extension_factor=2, normalization="standard", weighted=True, seed=None, device=0, progress=False,
-                          pdf="Gaussian", max_iter=400, nterms=1, statistic="lomb_scargle", nbins=10):
+                          pdf="Gaussian", max_iter=400, nterms=1, statistic="lomb_scargle", nbins=10, taus=None,
+                          decay=_engine.WWZ_DECAY):
     """The classic companion of the LRT p-value of ``protassov_test``: is the highest Lomb-Scargle peak of the observed
     light curve unusual among light curves of the null model?
 
@@ -585,16 +586,25 @@ def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walke
     at a few counts per epoch leaves epochs with ``dy = 0`` that take all the weight; pass ``weighted=False`` there.
     ``nterms``: harmonics per frequency of every periodogram (``Engine.lomb_scargle``), for profiles that are not sinusoidal.
     ``statistic="epoch_fold"``: the peaks of the epoch-folding periodogram instead (``Engine.epoch_fold`` with ``nbins``
-    phase bins counted from the first observed time; ``nterms`` must be 1) -- for dips, eclipses and narrow pulses."""
-    if statistic not in ("lomb_scargle", "epoch_fold"):
-        raise ValueError("statistic must be 'lomb_scargle' or 'epoch_fold'")
-    if statistic == "epoch_fold" and nterms != 1:
-        raise ValueError("statistic='epoch_fold' has no harmonics: nterms must be 1")
+    phase bins counted from the first observed time; ``nterms`` must be 1) -- for dips, eclipses and narrow pulses.
+    ``statistic="wwz"``: the highest value of Foster's Z over the whole time-frequency map (``Engine.wwz`` at
+    ``frequencies`` and the window centres ``taus``, None: 50 evenly spaced over the observed span, with the decay constant
+    ``decay``; ``nterms`` must be 1, ``normalization`` is not used) -- for a periodicity that lasts for part of the light
+    curve only.  No map leaves the device; ``observed_frequency`` is the ridge's frequency and ``observed_tau`` its centre."""
+    if statistic not in ("lomb_scargle", "epoch_fold", "wwz"):
+        raise ValueError("statistic must be 'lomb_scargle', 'epoch_fold' or 'wwz'")
+    if statistic in ("epoch_fold", "wwz") and nterms != 1:
+        raise ValueError("statistic=%r has no harmonics: nterms must be 1" % statistic)
     frequencies = np.ascontiguousarray(np.atleast_1d(frequencies), dtype=np.float64).ravel()
     eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
                                                            extension_factor, seed, device, progress, pdf, max_iter)
     times = np.asarray(lightcurve.times, dtype=np.float64)
-    if statistic == "epoch_fold":
+    if statistic == "wwz":
+        taus = np.linspace(times.min(), times.max(), 50) if taus is None else np.ascontiguousarray(np.atleast_1d(taus), dtype=np.float64).ravel()
+
+        def peaks(weighted):
+            return eng.wwz(frequencies, taus, decay=decay, statistic="z", weighted=weighted, values=False, peak=True)
+    elif statistic == "epoch_fold":
         def peaks(weighted):
             return eng.epoch_fold(frequencies, nbins=nbins, time_0=float(times[0]), normalization=normalization, weighted=weighted,
                                   power=False, peak=True)
@@ -610,8 +620,11 @@ def periodogram_peak_test(lightcurve, null_kernel, frequencies, nsims=100, walke
     obs, at = peaks(weighted and lightcurve.dy is not None)
     observed_peak = float(obs[0])
     p_value = (1.0 + float(np.sum(sim_peaks >= observed_peak))) / (1.0 + nsims)
-    return dict(observed_peak=observed_peak, observed_frequency=float(frequencies[at[0]]) if at[0] >= 0 else float("nan"),
-                sim_peaks=sim_peaks, p_value=p_value, null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+    res = dict(observed_peak=observed_peak, observed_frequency=float(frequencies[at[0] % len(frequencies)]) if at[0] >= 0 else float("nan"),
+               sim_peaks=sim_peaks, p_value=p_value, null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+    if statistic == "wwz":
+        res["observed_tau"] = float(taus[at[0] // len(frequencies)]) if at[0] >= 0 else float("nan")
+    return res
 
 
 def _harmonics(nterms):
