@@ -840,6 +840,45 @@ MTG_API int mtg_wwz(mtg_ctx *ctx, int64_t F, const double *freqs /* [F] host, cy
                     double *peak /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */);
 
 /*
+ * The time-lag view: sums over the pairs of samples of every resident light curve in bins of the lag, from which the
+ * caller normalises the structure function SF^2(tau) = <(y_j - y_i)^2> - <sigma_i^2 + sigma_j^2> and the discrete
+ * correlation function of Edelson & Krolik (1988, ApJ 333, 646) with its error.  Defined on the pairs: gaps cost
+ * nothing, nothing is interpolated.  For light curve l and every pair i < j of its samples:
+ *   lag and bin   tau_ij = fl(t_j - t_i), one IEEE subtraction of the stored times.  The pair belongs to bin b iff
+ *                 edges[b] <= tau_ij < edges[b + 1] (plain double comparisons); pairs below edges[0] or at or above
+ *                 edges[nbins] belong to no bin.  Equal times give tau = 0, which lands in bin 0 when edges[0] == 0.
+ *   residuals     r_n = y_n - ybar_l, ybar_l the unweighted mean mtg_lomb_scargle's pre-pass gives with weighted = 0;
+ *                 sigma_n^2 the stored variance.
+ *   per bin       count = #pairs, lag = sum tau_ij, sf = sum (y_j - y_i)^2, cf = sum r_i r_j, cf2 = sum (r_i r_j)^2,
+ *                 noise = sum (sigma_i^2 + sigma_j^2)
+ * Raw sums only: one sweep serves SF, DCF and their errors.  count and lag depend on the sampling alone but are written
+ * per light curve.  Each output is NULL or [L][nbins] on the host.
+ * Operations.  With d = y_j - y_i and p = r_i r_j (rounded): sf = fma(d, d, sf), cf = cf + p, cf2 = fma(p, p, cf2),
+ * noise = noise + (sigma_i^2 + sigma_j^2), lag = lag + tau.  The direct sums: the prefix-sum identity
+ * sum_j (r_j - r_i)^2 = Q - 2 r_i S + n r_i^2 cancels by var / SF(tau) at the short lags where a red-noise structure
+ * function is read, and is not used.
+ * Order.  A row i forms its partial sum for a bin from zero with j ascending (the times ascend, so for a fixed row the
+ * lag does not decrease and the bin only moves up).  The rows' partials of one (light curve, bin) are then added in an
+ * order fixed by N: lane q of 256 takes the rows q, q + 256, ... ascending, then a binary tree over the lanes.  Every
+ * output entry therefore depends on (light curve l, edges) alone, bit for bit: not on L, which light curves share a
+ * tile, whether the sampling is stored shared or per light curve, the slabs, or which other outputs were asked for.
+ * An empty bin reads exactly 0 in every sum.  No floating-point atomics.
+ * The call runs on the context's stream and only reads the resident set.  A row's partials go through a device
+ * workspace of at most 1 GiB -- slabs of light curves -- unless 8 light curves' alone are larger (csrc/mtg_lag_plan.h).
+ * mtg_last_solver names "mtg_lag_kernel<R,all> lanes 256" (R light curves per lane; all = 0: the kernel that forms sf
+ * alone, taken when nothing else is asked for), mtg_last_kernel_ms runs from the pre-pass through the last reduction.
+ * Against a 50-digit evaluation every sum of c pairs is within max(10 rho, 64 sqrt(c) u) of the sum of its terms'
+ * magnitudes and count is exact (tests/test_lag_gpu.py).
+ * MTG_E_STATE without light curves; MTG_E_ARG for nbins outside 1 .. MTG_LAG_MAX_BINS, an edge that is not finite,
+ * edges[0] < 0, edges not strictly ascending, N < 2, or all six outputs NULL; the context works as before after an error.
+ */
+enum { MTG_LAG_MAX_BINS = 128 };
+MTG_API int mtg_lag_sums(mtg_ctx *ctx, int nbins, const double *edges /* [nbins + 1] host */,
+                         int64_t *count /* [L][nbins] or NULL */, double *lag /* [L][nbins] or NULL */,
+                         double *sf     /* [L][nbins] or NULL */, double *cf  /* [L][nbins] or NULL */,
+                         double *cf2    /* [L][nbins] or NULL */, double *noise /* [L][nbins] or NULL */);
+
+/*
  * What the periodograms of the resident set say about every frequency: reductions of power[l][k] ACROSS the light
  * curves, without the [L][F] array ever leaving the device.  power[l][k] is, by definition and bit for bit, what
  * mtg_lomb_scargle returns for the same resident set, frequency, normalization and weighting (its launcher computes it).

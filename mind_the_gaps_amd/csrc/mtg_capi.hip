@@ -2775,6 +2775,61 @@ MTG_API int mtg_wwz(mtg_ctx *ctx, int64_t F, const double *freqs, int64_t T, con
     return c.finish(nullptr);
 }
 
+MTG_API int mtg_lag_sums(mtg_ctx *ctx, int nbins, const double *edges, int64_t *count, double *lag, double *sf, double *cf, double *cf2,
+                         double *noise)
+{
+    const char *who = "mtg_lag_sums";
+    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    int rc = c.ready(false);
+    if (rc) return rc;
+    if (nbins < 1 || nbins > MTG_LAG_MAX_BINS) return fail(ctx, MTG_E_ARG, "%s: nbins = %d is outside 1 .. %d", who, nbins, MTG_LAG_MAX_BINS);
+    if (!edges) return fail(ctx, MTG_E_ARG, "%s: need nbins + 1 edges", who);
+    if (!count && !lag && !sf && !cf && !cf2 && !noise) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
+    for (int b = 0; b <= nbins; ++b)
+        if (!std::isfinite(edges[b])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] is not finite", who, b);
+    if (edges[0] < 0.0) return fail(ctx, MTG_E_ARG, "%s: edges[0] = %g is negative", who, edges[0]);
+    for (int b = 0; b < nbins; ++b)
+        if (!(edges[b] < edges[b + 1])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] = %g is not above edges[%d] = %g", who, b + 1, edges[b + 1], b, edges[b]);
+    if (ctx->N < 2) return fail(ctx, MTG_E_ARG, "%s: N = %lld < 2 samples (no pairs)", who, (long long)ctx->N);
+    if ((rc = c.begin(false))) return rc;
+    const int64_t L = ctx->L;
+    const int what = (count ? MTG_LAG_COUNT : 0) | (lag ? MTG_LAG_LAG : 0) | (sf ? MTG_LAG_SF : 0) | (cf ? MTG_LAG_CF : 0) |
+                     (cf2 ? MTG_LAG_CF2 : 0) | (noise ? MTG_LAG_NOISE : 0);
+    const MtgLagPlan plan = mtg_lag_plan(ctx->N, nbins, L, !ctx->t_per_lc, what);
+    const size_t out_bytes = (size_t)L * (size_t)nbins * 8;
+    DevBuf d_edges, d_stats, d_ws, d_count, d_lag, d_sf, d_cf, d_cf2, d_noise;
+    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_stats, (size_t)L * 32}, {d_ws, (size_t)plan.ws_bytes}, {d_count, count ? out_bytes : 0},
+               {d_lag, lag ? out_bytes : 0}, {d_sf, sf ? out_bytes : 0}, {d_cf, cf ? out_bytes : 0}, {d_cf2, cf2 ? out_bytes : 0},
+               {d_noise, noise ? out_bytes : 0}});
+    c.upload(d_edges.p, edges, (size_t)(nbins + 1) * 8);
+    MtgLagArgs qa;
+    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, 0, d_stats.as<double>(), nullptr);
+    qa.nbins = nbins; qa.edges = d_edges.as<double>(); qa.ws = d_ws.as<double>();
+    qa.count = count ? d_count.as<int64_t>() : nullptr; qa.lag = lag ? d_lag.as<double>() : nullptr;
+    qa.sf = sf ? d_sf.as<double>() : nullptr; qa.cf = cf ? d_cf.as<double>() : nullptr;
+    qa.cf2 = cf2 ? d_cf2.as<double>() : nullptr; qa.noise = noise ? d_noise.as<double>() : nullptr;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_lag_kernel<%d,%d> lanes %d", plan.tile, plan.all, (int)MTG_LAG_LANES);
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(L, plan.slab, [&](int64_t l0, int64_t rows) {
+        // (the next slab's sweep overwrites the workspace only after this slab's reduction: one stream)
+        c.then([&] { return mtg_launch_lag(qa, plan, l0, rows, c.s); });
+        return c.e;
+    });
+    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+    if (c.ok()) ctx->timed = true;
+    if (count) c.gather(count, d_count.p, out_bytes);
+    if (lag) c.gather(lag, d_lag.p, out_bytes);
+    if (sf) c.gather(sf, d_sf.p, out_bytes);
+    if (cf) c.gather(cf, d_cf.p, out_bytes);
+    if (cf2) c.gather(cf2, d_cf2.p, out_bytes);
+    if (noise) c.gather(noise, d_noise.p, out_bytes);
+    return c.finish(nullptr);
+}
+
 // mtg_lomb_scargle_envelope (nterms = 1) and mtg_lomb_scargle_envelope_multi
 static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization,
                                        int weighted, int Q, const int64_t *ranks, double *order_stat, int64_t *valid,

@@ -374,6 +374,21 @@ struct MtgWwzArgs {
 // (hipErrorInvalidValue: more workgroups than a grid holds, or a plan that is not mtg_wwz_plan's)
 hipError_t mtg_launch_wwz(const MtgWwzArgs &, const MtgWwzPlan &, int64_t l0, int64_t Ls, hipStream_t);
 
+// One slab [l0, l0 + Ls) of mtg_lag_sums (mtg_lag.hip; tile, workspace and slab: mtg_lag_plan.h).  `ls` is the resident
+// set and the pre-pass statistics (unweighted) as the Lomb-Scargle launcher takes them; the frequencies, power and peaks
+// are not read.  The outputs are the call's, each NULL or [L][nbins] on the device, written at l0.
+#include "mtg_lag_plan.h"
+struct MtgLagArgs {
+    MtgLombScargleArgs ls;
+    int nbins;
+    const double *edges;   // [nbins + 1] on the device
+    double *ws;            // plan.ws_bytes
+    int64_t *count;
+    double *lag, *sf, *cf, *cf2, *noise;
+};
+// (hipErrorInvalidValue: more workgroups than a grid holds, or a plan that is not mtg_lag_plan's for these outputs)
+hipError_t mtg_launch_lag(const MtgLagArgs &, const MtgLagPlan &, int64_t l0, int64_t Ls, hipStream_t);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

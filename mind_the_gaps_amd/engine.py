@@ -43,7 +43,7 @@ EXPORTS = (
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
     "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope", "mtg_whiten",
     "mtg_lomb_scargle_multi", "mtg_lomb_scargle_envelope_multi", "mtg_epoch_fold", "mtg_phase_fold",
-    "mtg_wwz",
+    "mtg_wwz", "mtg_lag_sums",
 )
 
 # include/mtg.h, MTG_WHITEN_NSTATS and the slots of a row of whiten's stats
@@ -59,6 +59,8 @@ EF_MAX_BINS = 32   # include/mtg.h, MTG_EF_MAX_BINS: the phase bins of epoch_fol
 WWZ_POWER, WWZ_Z, WWZ_AMPLITUDE = range(3)
 WWZ_STATISTICS = {"power": WWZ_POWER, "z": WWZ_Z, "amplitude": WWZ_AMPLITUDE}
 WWZ_DECAY = 0.012665147955292222
+LAG_MAX_BINS = 128   # include/mtg.h, MTG_LAG_MAX_BINS: the lag bins of lag_sums
+LAG_SUMS = ("count", "lag", "sf", "cf", "cf2", "noise")   # mtg_lag_sums' outputs, in its order
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -359,6 +361,8 @@ def load_library():
     lib.mtg_phase_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, ctypes.POINTER(c_i64), _dp, _dp, _dp]
     lib.mtg_wwz.restype = c_int
     lib.mtg_wwz.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, ctypes.c_double, c_int, c_int, _dp, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lag_sums.restype = c_int
+    lib.mtg_lag_sums.argtypes = [c_vp, c_int, _dp, ctypes.POINTER(c_i64), _dp, _dp, _dp, _dp, _dp]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_whiten.restype = c_int
     lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
@@ -927,6 +931,27 @@ class Engine:
                                       None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         got = ([out] if values else []) + ([ne] if neff else []) + ([pk, ix] if peak else [])
         return got[0] if len(got) == 1 else tuple(got)
+
+    def lag_sums(self, edges, count=True, lag=True, sf=True, cf=False, cf2=False, noise=False):
+        """Sums over the pairs ``i < j`` of every resident light curve in the lag bins ``edges[b] <= t_j - t_i <
+        edges[b + 1]`` (``edges`` [nbins + 1], ascending from ``edges[0] >= 0``, 1 .. 128 bins) -> a dict of the arrays
+        asked for, each [L][nbins]: ``count`` the pairs (int64), ``lag`` the sum of their lags, ``sf`` of
+        ``(y_j - y_i)^2``, ``cf`` of ``r_i r_j`` with ``r = y - mean(y)``, ``cf2`` of ``(r_i r_j)^2``, ``noise`` of
+        ``sigma_i^2 + sigma_j^2``.  Raw sums: ``timedomain.StructureFunction`` and ``DiscreteCorrelation`` normalise
+        them.  An entry depends on its light curve and the edges alone, bit for bit; with ``sf`` alone a lighter kernel
+        runs.  A model need not be set (mtg_lag_sums)."""
+        edges = _f64(np.atleast_1d(edges)).ravel()
+        want = dict(zip(LAG_SUMS, (count, lag, sf, cf, cf2, noise)))
+        if not any(want.values()):
+            raise ValueError("lag_sums: nothing asked for")
+        if len(edges) < 2:
+            raise ValueError("lag_sums: need at least two edges")
+        shape = (int(self.L), len(edges) - 1)
+        out = {k: (np.zeros(shape, dtype=np.int64) if k == "count" else np.full(shape, np.nan)) for k in LAG_SUMS if want[k]}
+        ptrs = [None if k not in out else out[k].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if k == "count" else _ptr(out[k])
+                for k in LAG_SUMS]
+        self._check(self._lib.mtg_lag_sums(self._ctx, len(edges) - 1, _ptr(edges), *ptrs))
+        return out
 
     def phase_fold(self, freqs, nbins=10, time_0=None, weighted=True):
         """The folded profiles behind ``epoch_fold``, for the few frequencies one looks at: ``PhaseFold(count, wsum,

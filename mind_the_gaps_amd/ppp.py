@@ -741,6 +741,76 @@ def periodogram_significance(lightcurve, null_kernel, frequencies, nsims=100, le
     return res
 
 
+def _lag_statistic(eng, Y, DY, edges, statistic, subtract_noise):
+    """The structure function or the discrete correlation function [L][nbins] of the light curves resident on ``eng``
+    (``Y``, ``DY`` [L][N]: the same ones on the host, for the variances the correlation function is normalised by)."""
+    from .timedomain import dcf_from_sums, sf_from_sums
+    if statistic == "sf":
+        sums = eng.lag_sums(edges, count=True, lag=True, sf=True, noise=subtract_noise)
+        return sf_from_sums(sums, subtract_noise)[1]
+    sums = eng.lag_sums(edges, count=True, lag=True, sf=False, cf=True, cf2=True)
+    s2 = np.mean((Y - Y.mean(axis=1, keepdims=True)) ** 2, axis=1)
+    e2 = np.mean(DY ** 2, axis=1) if subtract_noise else np.zeros(len(Y))
+    return dcf_from_sums(sums, s2, e2)[1]
+
+
+def _lag_levels(observed, sims, levels):
+    """The host arithmetic of ``lag_significance``: ``observed`` [nbins] against ``sims`` [nsims][nbins] -> dict(median,
+    lower, upper, share_above, share_below).  A bin in which the observed value or any simulation is NaN (an empty bin) is
+    NaN in every output."""
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if np.any(levels <= 0.5) or np.any(levels >= 1.0):
+        raise ValueError("levels must lie in (0.5, 1)")
+    ok = np.isfinite(observed) & np.all(np.isfinite(sims), axis=0)
+    safe = np.where(ok[None, :], sims, 0.0)
+    blank = lambda a: np.where(ok, a, np.nan)
+    return dict(median=blank(np.quantile(safe, 0.5, axis=0)), lower=blank(np.quantile(safe, 1.0 - levels, axis=0)),
+                upper=blank(np.quantile(safe, levels, axis=0)),
+                share_above=blank(np.mean(safe >= np.where(ok, observed, 0.0)[None, :], axis=0)),
+                share_below=blank(np.mean(safe <= np.where(ok, observed, 0.0)[None, :], axis=0)))
+
+
+def lag_significance(lightcurve, null_kernel, edges, statistic="sf", nsims=100, levels=(0.95, 0.997), walkers=12, max_steps=500,
+                     sigma_noise=None, extension_factor=2, subtract_noise=True, seed=None, device=0, progress=False,
+                     pdf="Gaussian", max_iter=400):
+    """``periodogram_significance`` in the time-lag view: is the observed structure function (``statistic="sf"``) or
+    discrete correlation function (``"dcf"``) in the lag bins ``edges`` (``timedomain.lag_bins``) unusual, bin by bin,
+    among light curves of the null model?
+
+    1. the observed light curve's statistic (``Engine.lag_sums``, normalised by ``timedomain``);
+    2. and 3. the null chain, the ``nsims`` posterior picks and the simulated set of ``periodogram_peak_test``: the same
+       ones for the same seed, left resident on the device;
+    4. one ``Engine.lag_sums`` call on that set, and ``np.quantile`` over the [nsims][nbins] values on the host.
+
+    Returns dict(lag[nbins] the mean lag of each bin, count[nbins], observed[nbins], median[nbins], lower[len(levels)][nbins]
+    and upper[len(levels)][nbins] -- the quantiles ``1 - level`` and ``level`` --, share_above[nbins] and share_below[nbins]
+    -- the shares of simulations at or above and at or below the observed value --, sims[nsims][nbins], null,
+    samples[nsims][P], sim_seed, lightcurves).  A bin without pairs is NaN throughout.  ``subtract_noise``: the
+    measurement-noise term of either statistic, from the error bars (the simulated light curves' own included).  There is
+    no trial-corrected p-value over the bins.  One GPU; the same seed gives the same result bit for bit."""
+    from .gp import get_engine
+    from .timedomain import sf_from_sums
+    if statistic not in ("sf", "dcf"):
+        raise ValueError("statistic must be 'sf' or 'dcf'")
+    edges = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64).ravel()
+    times = np.asarray(lightcurve.times, dtype=np.float64)
+    y = np.asarray(lightcurve.y, dtype=np.float64)
+    noise = bool(subtract_noise) and lightcurve.dy is not None
+    dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
+    eng = get_engine(device)
+    eng.set_lightcurves(times, y, dy)
+    eng.bound_to = None
+    observed = _lag_statistic(eng, y[None, :], dy[None, :], edges, statistic, noise)[0]
+    lag, _, count = sf_from_sums(eng.lag_sums(edges, count=True, lag=True, sf=True), False)
+    eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
+                                                           extension_factor, seed, device, progress, pdf, max_iter)
+    sims = _lag_statistic(eng, np.asarray(out["rates"], dtype=np.float64), np.asarray(out["dy"], dtype=np.float64), edges,
+                          statistic, bool(subtract_noise))
+    res = dict(lag=lag[0], count=count[0], observed=observed, sims=sims, null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+    res.update(_lag_levels(observed, sims, levels))
+    return res
+
+
 def _seed_schedule(seed, nsims):
     """Every random number protassov_test itself draws, from ONE ``default_rng(seed)``, in the order every bit-for-bit
     guarantee of the sharded run rests on.  A generator of two steps: ``next`` gives the two chain seeds, ``send(null)``
