@@ -879,6 +879,49 @@ MTG_API int mtg_lag_sums(mtg_ctx *ctx, int nbins, const double *edges /* [nbins 
                          double *cf2    /* [L][nbins] or NULL */, double *noise /* [L][nbins] or NULL */);
 
 /*
+ * The lag between TWO series on different irregular samplings -- what Edelson & Krolik (1988) wrote the discrete
+ * correlation function for: sums over the pairs (resident sample i, companion sample j) of every resident light curve l
+ * and a companion series given with the call, in bins of the signed lag.  The companion has M samples at the ascending
+ * times t2 (equal times allowed) and the values y2: one row for every light curve (L2 == 1) or a row per light curve
+ * (L2 == L; row l goes with light curve l).  It is uploaded for the call and not kept.
+ *   lag and bin   tau_ij = fl(t2_j - t_i), one IEEE subtraction; positive when the companion lags the resident series.
+ *                 The pair belongs to bin b iff edges[b] <= tau_ij < edges[b + 1]; edges may be negative; a pair outside
+ *                 [edges[0], edges[nbins]) belongs to no bin.  Every (i, j) is a pair: there is no i < j.
+ *   residuals     r_i = y_i - ybar_l as in mtg_lag_sums; s_j = y2_j - ybar2, with ybar2 what the same unweighted
+ *                 pre-pass gives for the companion row taken as a light curve of M samples.
+ *   per bin       count = #pairs, lag = sum tau_ij, cf = sum r_i s_j, cf2 = sum (r_i s_j)^2, and the local moments
+ *                 sa = sum r_i, sb = sum s_j, saa = sum r_i^2, sbb = sum s_j^2 over the pairs of the bin, from which
+ *                 the host forms the locally normalised correlation of Lehar et al. (1992) and Welsh (1999).
+ * Operations.  With p = r_i s_j (rounded): cf = cf + p, cf2 = fma(p, p, cf2), sb = sb + s_j, sbb = fma(s_j, s_j, sbb),
+ * lag = lag + tau.  A row i contributes fl(r_i c) to sa and fl(fl(r_i^2) c) to saa, c its pair count in the bin: this is
+ * the definition.
+ * Order.  A row i forms its partial for a bin from zero with j ascending (for a fixed row the lag does not decrease, so
+ * the bin only moves up).  The rows' partials of one (light curve, bin) are added as in mtg_lag_sums: lane q of 256 takes
+ * the rows q, q + 256, ... ascending, then a binary tree over the lanes.  Every output entry depends on (resident light
+ * curve l, its companion row, t2, edges) alone, bit for bit: not on L, which light curves share a tile, L2 == 1 or
+ * L2 == L with identical rows, whether the resident sampling is stored shared or per light curve, the slabs, or which
+ * other outputs were asked for.  An empty bin reads exactly 0 in every sum.  No floating-point atomics.
+ * With edges[0] > 0 and the companion equal to the resident light curve (M == N, the same times and values), count, lag,
+ * cf and cf2 equal mtg_lag_sums' bit for bit.
+ * The call runs on the context's stream and only reads the resident set.  Workspace and slabs as mtg_lag_sums
+ * (csrc/mtg_cross_plan.h).  mtg_last_solver names "mtg_cross_kernel<R,per,all> lanes 256" (R light curves per lane;
+ * per = 1: a companion row per light curve, taken when L2 == L > 1; all = 0: the kernel that forms count, lag, cf and cf2
+ * alone, taken when no local moment is asked for), mtg_last_kernel_ms runs from the pre-pass through the last reduction.
+ * Against an exact evaluation every sum of c pairs is within max(10 rho, 64 sqrt(c) u) of the sum of its terms'
+ * magnitudes and count is exact (tests/test_cross_gpu.py).
+ * MTG_E_STATE without light curves; MTG_E_ARG for M < 1 or M >= 2^28, L2 not 1 or L, a t2 or y2 entry that is not
+ * finite, t2 descending, nbins outside 1 .. MTG_LAG_MAX_BINS, an edge that is not finite, edges not strictly ascending,
+ * or all eight outputs NULL -- the message names the offending index; the context works as before after an error.
+ */
+MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2 /* [M] host, ascending */,
+                           int64_t L2 /* 1 or L */, const double *y2 /* [L2][M] host */,
+                           int nbins, const double *edges /* [nbins + 1] host, may be negative */,
+                           int64_t *count /* [L][nbins] or NULL */, double *lag /* [L][nbins] or NULL */,
+                           double *cf     /* [L][nbins] or NULL */, double *cf2 /* [L][nbins] or NULL */,
+                           double *sa     /* [L][nbins] or NULL */, double *sb  /* [L][nbins] or NULL */,
+                           double *saa    /* [L][nbins] or NULL */, double *sbb /* [L][nbins] or NULL */);
+
+/*
  * What the periodograms of the resident set say about every frequency: reductions of power[l][k] ACROSS the light
  * curves, without the [L][F] array ever leaving the device.  power[l][k] is, by definition and bit for bit, what
  * mtg_lomb_scargle returns for the same resident set, frequency, normalization and weighting (its launcher computes it).

@@ -2830,6 +2830,86 @@ MTG_API int mtg_lag_sums(mtg_ctx *ctx, int nbins, const double *edges, int64_t *
     return c.finish(nullptr);
 }
 
+MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2, const double *y2, int nbins, const double *edges,
+                           int64_t *count, double *lag, double *cf, double *cf2, double *sa, double *sb, double *saa, double *sbb)
+{
+    const char *who = "mtg_cross_sums";
+    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
+    int rc = c.ready(false);
+    if (rc) return rc;
+    const int64_t L = ctx->L;
+    if (M < 1 || M >= MTG_CROSS_MAX_M) return fail(ctx, MTG_E_ARG, "%s: M = %lld is outside 1 .. 2^28 - 1", who, (long long)M);
+    if (L2 != 1 && L2 != L) return fail(ctx, MTG_E_ARG, "%s: L2 = %lld is neither 1 nor L = %lld", who, (long long)L2, (long long)L);
+    if (!t2 || !y2) return fail(ctx, MTG_E_ARG, "%s: need the companion's M times and L2 x M values", who);
+    if (nbins < 1 || nbins > MTG_LAG_MAX_BINS) return fail(ctx, MTG_E_ARG, "%s: nbins = %d is outside 1 .. %d", who, nbins, MTG_LAG_MAX_BINS);
+    if (!edges) return fail(ctx, MTG_E_ARG, "%s: need nbins + 1 edges", who);
+    if (!count && !lag && !cf && !cf2 && !sa && !sb && !saa && !sbb) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
+    for (int b = 0; b <= nbins; ++b)
+        if (!std::isfinite(edges[b])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] is not finite", who, b);
+    for (int b = 0; b < nbins; ++b)
+        if (!(edges[b] < edges[b + 1])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] = %g is not above edges[%d] = %g", who, b + 1, edges[b + 1], b, edges[b]);
+    for (int64_t j = 0; j < M; ++j) {
+        if (!std::isfinite(t2[j])) return fail(ctx, MTG_E_ARG, "%s: t2[%lld] is not finite", who, (long long)j);
+        if (j > 0 && t2[j] < t2[j - 1])
+            return fail(ctx, MTG_E_ARG, "%s: t2[%lld] = %g is below t2[%lld] = %g (the times must ascend)", who, (long long)j, t2[j],
+                        (long long)(j - 1), t2[j - 1]);
+    }
+    for (int64_t k = 0; k < L2 * M; ++k)
+        if (!std::isfinite(y2[k])) return fail(ctx, MTG_E_ARG, "%s: y2[%lld][%lld] is not finite", who, (long long)(k / M), (long long)(k % M));
+    if ((rc = c.begin(false))) return rc;
+    const int what = (count ? MTG_CROSS_COUNT : 0) | (lag ? MTG_CROSS_LAG : 0) | (cf ? MTG_CROSS_CF : 0) | (cf2 ? MTG_CROSS_CF2 : 0) |
+                     (sa ? MTG_CROSS_SA : 0) | (sb ? MTG_CROSS_SB : 0) | (saa ? MTG_CROSS_SAA : 0) | (sbb ? MTG_CROSS_SBB : 0);
+    // (a set of one light curve has L2 == 1 == L: the shared-companion kernel, the same arithmetic)
+    const MtgCrossPlan plan = mtg_cross_plan(ctx->N, M, nbins, L, !ctx->t_per_lc, L2 == L && L > 1, what);
+    const size_t out_bytes = (size_t)L * (size_t)nbins * 8, rows2 = (size_t)L2 * (size_t)M;
+    // the companion as the pre-pass reads a light curve: (value, variance) pairs; the variance is not read unweighted
+    std::vector<double2> pairs(rows2);
+    for (size_t k = 0; k < rows2; ++k) pairs[k] = make_double2(y2[k], 1.0);
+    DevBuf d_edges, d_stats, d_t2, d_yv2, d_stats2, d_ws, d_count, d_lag, d_cf, d_cf2, d_sa, d_sb, d_saa, d_sbb;
+    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_stats, (size_t)L * 32}, {d_t2, (size_t)M * 8}, {d_yv2, rows2 * 16},
+               {d_stats2, (size_t)L2 * 32}, {d_ws, (size_t)plan.ws_bytes}, {d_count, count ? out_bytes : 0}, {d_lag, lag ? out_bytes : 0},
+               {d_cf, cf ? out_bytes : 0}, {d_cf2, cf2 ? out_bytes : 0}, {d_sa, sa ? out_bytes : 0}, {d_sb, sb ? out_bytes : 0},
+               {d_saa, saa ? out_bytes : 0}, {d_sbb, sbb ? out_bytes : 0}});
+    c.upload(d_edges.p, edges, (size_t)(nbins + 1) * 8);
+    c.upload(d_t2.p, t2, (size_t)M * 8);
+    c.upload(d_yv2.p, pairs.data(), rows2 * 16);
+    MtgCrossArgs qa;
+    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, 0, d_stats.as<double>(), nullptr);
+    MtgLombScargleArgs companion = qa.ls;      // the same pre-pass on the companion's rows as light curves of M samples
+    companion.dxt = nullptr; companion.yv = d_yv2.as<double2>(); companion.N = M; companion.t_stride = 0; companion.L = L2;
+    companion.stats = d_stats2.as<double>();
+    qa.M = M; qa.t2 = d_t2.as<double>(); qa.yv2 = d_yv2.as<double2>(); qa.stats2 = d_stats2.as<double>();
+    qa.nbins = nbins; qa.edges = d_edges.as<double>(); qa.ws = d_ws.as<double>();
+    qa.count = count ? d_count.as<int64_t>() : nullptr; qa.lag = lag ? d_lag.as<double>() : nullptr;
+    qa.cf = cf ? d_cf.as<double>() : nullptr; qa.cf2 = cf2 ? d_cf2.as<double>() : nullptr;
+    qa.sa = sa ? d_sa.as<double>() : nullptr; qa.sb = sb ? d_sb.as<double>() : nullptr;
+    qa.saa = saa ? d_saa.as<double>() : nullptr; qa.sbb = sbb ? d_sbb.as<double>() : nullptr;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_cross_kernel<%d,%d,%d> lanes %d", plan.tile, plan.per, plan.all,
+             (int)MTG_CROSS_LANES);
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
+        mtg_launch_lomb_scargle_stats(companion, c.s);
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(L, plan.slab, [&](int64_t l0, int64_t rows) {
+        // (the next slab's sweep overwrites the workspace only after this slab's reduction: one stream)
+        c.then([&] { return mtg_launch_cross(qa, plan, l0, rows, c.s); });
+        return c.e;
+    });
+    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+    if (c.ok()) ctx->timed = true;
+    if (count) c.gather(count, d_count.p, out_bytes);
+    if (lag) c.gather(lag, d_lag.p, out_bytes);
+    if (cf) c.gather(cf, d_cf.p, out_bytes);
+    if (cf2) c.gather(cf2, d_cf2.p, out_bytes);
+    if (sa) c.gather(sa, d_sa.p, out_bytes);
+    if (sb) c.gather(sb, d_sb.p, out_bytes);
+    if (saa) c.gather(saa, d_saa.p, out_bytes);
+    if (sbb) c.gather(sbb, d_sbb.p, out_bytes);
+    return c.finish(nullptr);   // (waits for the stream: `pairs` outlives its upload)
+}
+
 // mtg_lomb_scargle_envelope (nterms = 1) and mtg_lomb_scargle_envelope_multi
 static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization,
                                        int weighted, int Q, const int64_t *ranks, double *order_stat, int64_t *valid,

@@ -389,6 +389,26 @@ struct MtgLagArgs {
 // (hipErrorInvalidValue: more workgroups than a grid holds, or a plan that is not mtg_lag_plan's for these outputs)
 hipError_t mtg_launch_lag(const MtgLagArgs &, const MtgLagPlan &, int64_t l0, int64_t Ls, hipStream_t);
 
+// One slab [l0, l0 + Ls) of mtg_cross_sums (mtg_cross.hip; instantiation, workspace and slab: mtg_cross_plan.h).  `ls` is
+// the resident set and its pre-pass statistics (unweighted); the companion is its times, its values as (y2, anything)
+// pairs, [1][M] or [L][M] as plan.per says, and the same pre-pass's statistics of those rows.  The outputs are the
+// call's, each NULL or [L][nbins] on the device, written at l0.
+#include "mtg_cross_plan.h"
+struct MtgCrossArgs {
+    MtgLombScargleArgs ls;
+    int64_t M;
+    const double *t2;        // [M] on the device
+    const double2 *yv2;      // [L2][M]
+    const double *stats2;    // [L2][4]
+    int nbins;
+    const double *edges;     // [nbins + 1] on the device
+    double *ws;              // plan.ws_bytes
+    int64_t *count;
+    double *lag, *cf, *cf2, *sa, *sb, *saa, *sbb;
+};
+// (hipErrorInvalidValue: more workgroups than a grid holds, or a plan that is not mtg_cross_plan's for these outputs)
+hipError_t mtg_launch_cross(const MtgCrossArgs &, const MtgCrossPlan &, int64_t l0, int64_t Ls, hipStream_t);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

@@ -19,11 +19,12 @@
 //
 // Order.  A row's partial sum for a bin starts from zero and takes the columns ascending; it is written once to the
 // workspace of mtg_lag_plan.h (zeros for the bins the row never enters).  mtg_lag_reduce_kernel then adds the rows of
-// one (light curve, bin): lane q the rows q, q + 256, ... ascending, then a binary tree over the lanes.  The arithmetic
+// one (light curve, bin) by mtg_row_reduce.h: lane q the rows q, q + 256, ... ascending, then a binary tree over the lanes.  The arithmetic
 // of a light curve is the same sequence of operations in every instantiation: an output depends on (light curve, edges)
 // alone.  No atomics.  No scratch: profiles/lag_resources.txt.  The C entry: mtg_capi.hip.
 #include "mtg_device.h"
 #include "mtg_lag_plan.h"
+#include "mtg_row_reduce.h"
 
 namespace {
 
@@ -154,32 +155,6 @@ mtg_lag_kernel(const MtgLagKernelArgs a)
     }
     // the bin the row ended in, and zeros for the bins it never entered
     for (int bb = b < 0 ? 0 : b; bb < nb; ++bb) flush(bb);
-}
-
-// sum of v over the workgroup in a fixed order (a binary tree over the lanes): `red` holds MTG_LAG_LANES entries
-template <class V>
-__device__ __forceinline__ V lag_block_sum(V v, V *red)
-{
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int h = MTG_LAG_LANES / 2; h > 0; h >>= 1) {
-        if (tid < h) red[tid] = red[tid] + red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-// rows q, q + 256, ... ascending per lane, then the tree
-template <class V>
-__device__ __forceinline__ V lag_row_sum(const V *rows, int64_t N, V *red)
-{
-#pragma clang fp contract(off)
-    V s = 0;
-    for (int64_t n = threadIdx.x; n < N; n += MTG_LAG_LANES) s = s + rows[n];
-    return lag_block_sum(s, red);
 }
 
 struct MtgLagOut {

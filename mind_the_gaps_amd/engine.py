@@ -43,7 +43,7 @@ EXPORTS = (
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
     "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope", "mtg_whiten",
     "mtg_lomb_scargle_multi", "mtg_lomb_scargle_envelope_multi", "mtg_epoch_fold", "mtg_phase_fold",
-    "mtg_wwz", "mtg_lag_sums",
+    "mtg_wwz", "mtg_lag_sums", "mtg_cross_sums",
 )
 
 # include/mtg.h, MTG_WHITEN_NSTATS and the slots of a row of whiten's stats
@@ -61,6 +61,8 @@ WWZ_STATISTICS = {"power": WWZ_POWER, "z": WWZ_Z, "amplitude": WWZ_AMPLITUDE}
 WWZ_DECAY = 0.012665147955292222
 LAG_MAX_BINS = 128   # include/mtg.h, MTG_LAG_MAX_BINS: the lag bins of lag_sums
 LAG_SUMS = ("count", "lag", "sf", "cf", "cf2", "noise")   # mtg_lag_sums' outputs, in its order
+CROSS_SUMS = ("count", "lag", "cf", "cf2", "sa", "sb", "saa", "sbb")   # mtg_cross_sums' outputs, in its order
+CROSS_MAX_M = 1 << 28   # include/mtg.h: the companion of cross_sums has fewer samples than this
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -363,6 +365,8 @@ def load_library():
     lib.mtg_wwz.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, ctypes.c_double, c_int, c_int, _dp, _dp, _dp, ctypes.POINTER(c_i64)]
     lib.mtg_lag_sums.restype = c_int
     lib.mtg_lag_sums.argtypes = [c_vp, c_int, _dp, ctypes.POINTER(c_i64), _dp, _dp, _dp, _dp, _dp]
+    lib.mtg_cross_sums.restype = c_int
+    lib.mtg_cross_sums.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, c_int, _dp, ctypes.POINTER(c_i64), _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_whiten.restype = c_int
     lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
@@ -951,6 +955,35 @@ class Engine:
         ptrs = [None if k not in out else out[k].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if k == "count" else _ptr(out[k])
                 for k in LAG_SUMS]
         self._check(self._lib.mtg_lag_sums(self._ctx, len(edges) - 1, _ptr(edges), *ptrs))
+        return out
+
+    def cross_sums(self, t2, y2, edges, count=True, lag=True, cf=True, cf2=False, sa=False, sb=False, saa=False, sbb=False):
+        """Sums over the pairs (resident sample i, companion sample j) of every resident light curve and a companion
+        series -- ``t2`` [M] ascending, ``y2`` [M] (one series for every light curve) or [L][M] (row l goes with light
+        curve l) -- in the bins ``edges[b] <= t2_j - t_i < edges[b + 1]`` of the SIGNED lag (``edges`` [nbins + 1],
+        strictly ascending, may be negative, 1 .. 128 bins; positive: the companion lags) -> a dict of the arrays asked
+        for, each [L][nbins]: ``count`` the pairs (int64), ``lag`` the sum of their lags, ``cf`` of ``r_i s_j`` with
+        ``r = y - mean(y)`` and ``s = y2 - mean(y2)``, ``cf2`` of its square, and the local moments ``sa`` of ``r_i``,
+        ``sb`` of ``s_j``, ``saa`` of ``r_i^2``, ``sbb`` of ``s_j^2`` over the pairs of each bin.  Raw sums:
+        ``timedomain.ccf_from_sums`` normalises them.  An entry depends on its light curve, its companion row, ``t2`` and
+        the edges alone, bit for bit; without a local moment a lighter kernel runs.  A model need not be set
+        (mtg_cross_sums)."""
+        edges = _f64(np.atleast_1d(edges)).ravel()
+        t2 = _f64(np.atleast_1d(t2))
+        y2 = _f64(y2)
+        want = dict(zip(CROSS_SUMS, (count, lag, cf, cf2, sa, sb, saa, sbb)))
+        if not any(want.values()):
+            raise ValueError("cross_sums: nothing asked for")
+        if len(edges) < 2:
+            raise ValueError("cross_sums: need at least two edges")
+        if t2.ndim != 1 or y2.ndim not in (1, 2) or y2.shape[-1] != len(t2):
+            raise ValueError("cross_sums: t2 must be [M] and y2 [M] or [L][M]")
+        L2 = 1 if y2.ndim == 1 else y2.shape[0]
+        shape = (int(self.L), len(edges) - 1)
+        out = {k: (np.zeros(shape, dtype=np.int64) if k == "count" else np.full(shape, np.nan)) for k in CROSS_SUMS if want[k]}
+        ptrs = [None if k not in out else out[k].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if k == "count" else _ptr(out[k])
+                for k in CROSS_SUMS]
+        self._check(self._lib.mtg_cross_sums(self._ctx, len(t2), _ptr(t2), L2, _ptr(y2), len(edges) - 1, _ptr(edges), *ptrs))
         return out
 
     def phase_fold(self, freqs, nbins=10, time_0=None, weighted=True):

@@ -811,6 +811,91 @@ def lag_significance(lightcurve, null_kernel, edges, statistic="sf", nsims=100, 
     return res
 
 
+def _cross_statistic(eng, Y, DY, t2, y2, dy2, edges, normalization, subtract_noise):
+    """(mean lag, CCF, count), each [L][nbins], of the light curves resident on ``eng`` (``Y``, ``DY`` [L][N]: the same ones
+    on the host, for the variances of the global normalisation) against the one companion ``t2, y2, dy2`` (``dy2`` None:
+    no noise term): one ``cross_sums`` call."""
+    from .timedomain import ccf_from_sums
+    local = normalization == "local"
+    sums = eng.cross_sums(t2, y2, edges, count=True, lag=True, cf=True, cf2=True, sa=local, sb=local, saa=local, sbb=local)
+    s2a = np.mean((Y - Y.mean(axis=1, keepdims=True)) ** 2, axis=1)
+    s2b = float(np.mean((y2 - y2.mean()) ** 2))
+    e2a = np.mean(DY ** 2, axis=1) if subtract_noise else np.zeros(len(Y))
+    e2b = float(np.mean(dy2 ** 2)) if subtract_noise and dy2 is not None else 0.0
+    lag, ccf, _, count = ccf_from_sums(sums, s2a, s2b, e2a, e2b, normalization)
+    return lag, ccf, count
+
+
+def _cross_peaks(lag, ccf):
+    """Per row of ``ccf`` [L][nbins]: (the largest |CCF| over the finite bins, the mean lag of that bin: the first such
+    bin); NaN for a row without a finite bin."""
+    mag = np.where(np.isfinite(ccf), np.abs(ccf), -1.0)
+    at = np.argmax(mag, axis=1)
+    rows = np.arange(len(ccf))
+    none = mag[rows, at] < 0
+    return np.where(none, np.nan, mag[rows, at]), np.where(none, np.nan, lag[rows, at])
+
+
+def _cross_global_p(observed_peak, sim_peaks):
+    """``(1 + #{simulations whose peak is at or above the observed one}) / (1 + nsims)``: a simulation without a finite
+    bin (NaN) does not count as above; an observed CCF without one gives NaN."""
+    sim_peaks = np.asarray(sim_peaks, dtype=np.float64)
+    if not np.isfinite(observed_peak):
+        return float("nan")
+    return (1.0 + float(np.sum(sim_peaks >= observed_peak))) / (1.0 + len(sim_peaks))
+
+
+def cross_lag_significance(lightcurve, companion, null_kernel, edges, nsims=100, levels=(0.95, 0.997), normalization="global",
+                           walkers=12, max_steps=500, sigma_noise=None, extension_factor=2, subtract_noise=True, seed=None, device=0,
+                           progress=False, pdf="Gaussian", max_iter=400):
+    """Is the cross-correlation of ``lightcurve`` with ``companion`` (a second light curve on its own sampling: ``times``,
+    ``y``, ``dy`` or None) in the signed lag bins ``edges`` (``timedomain.cross_lag_bins``; positive: the companion lags)
+    unusual if the light curve is red noise of ``null_kernel``, INDEPENDENT of the companion?
+
+    1. the observed CCF (``Engine.cross_sums``, normalised by ``timedomain.ccf_from_sums``, ``normalization`` "global" or
+       "local");
+    2. and 3. the null chain, the ``nsims`` posterior picks and the simulated set of ``lag_significance``: the same ones for
+       the same seed, left resident on the device;
+    4. ONE ``Engine.cross_sums`` call of that set against the observed companion, and ``np.quantile`` over the
+       [nsims][nbins] values on the host, bin by bin;
+    5. over the bins: ``peak`` = the largest ``|CCF|`` of the finite bins, of the observation and of every simulation, and
+       ``p_global = (1 + #{simulations with peak >= observed}) / (1 + nsims)`` -- the trial-corrected significance.
+
+    Returns dict(lag[nbins], count[nbins], observed[nbins], median, lower[len(levels)][nbins], upper, share_above,
+    share_below as ``lag_significance``; peak, peak_lag the observation's; sim_peaks[nsims], sim_peak_lags[nsims];
+    p_global; sims[nsims][nbins], null, samples[nsims][P], sim_seed, lightcurves).  A bin with fewer than two pairs is NaN
+    throughout.  ``subtract_noise``: the measurement-noise terms of the global normalisation, from the error bars (the
+    simulated light curves' own included).  One GPU; the same seed gives the same result bit for bit."""
+    from .gp import get_engine
+    if normalization not in ("global", "local"):
+        raise ValueError("normalization must be 'global' or 'local'")
+    edges = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64).ravel()
+    times = np.asarray(lightcurve.times, dtype=np.float64)
+    y = np.asarray(lightcurve.y, dtype=np.float64)
+    noise = bool(subtract_noise) and lightcurve.dy is not None
+    dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
+    t2 = np.ascontiguousarray(companion.times, dtype=np.float64)
+    y2 = np.ascontiguousarray(companion.y, dtype=np.float64)
+    dy2 = None if getattr(companion, "dy", None) is None else np.asarray(companion.dy, dtype=np.float64)
+    if t2.ndim != 1 or y2.shape != t2.shape:
+        raise ValueError("the companion must be one series: times [M] and y [M]")
+    eng = get_engine(device)
+    eng.set_lightcurves(times, y, dy)
+    eng.bound_to = None
+    lag, observed, count = _cross_statistic(eng, y[None, :], dy[None, :], t2, y2, dy2, edges, normalization, noise)
+    peak, peak_lag = _cross_peaks(lag, observed)
+    eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
+                                                           extension_factor, seed, device, progress, pdf, max_iter)
+    sim_lag, sims, _ = _cross_statistic(eng, np.asarray(out["rates"], dtype=np.float64), np.asarray(out["dy"], dtype=np.float64), t2, y2,
+                                        dy2, edges, normalization, bool(subtract_noise))
+    sim_peaks, sim_peak_lags = _cross_peaks(sim_lag, sims)
+    res = dict(lag=lag[0], count=count[0], observed=observed[0], sims=sims, peak=float(peak[0]), peak_lag=float(peak_lag[0]),
+               sim_peaks=sim_peaks, sim_peak_lags=sim_peak_lags, p_global=_cross_global_p(float(peak[0]), sim_peaks),
+               null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+    res.update(_lag_levels(observed[0], sims, levels))
+    return res
+
+
 def _seed_schedule(seed, nsims):
     """Every random number protassov_test itself draws, from ONE ``default_rng(seed)``, in the order every bit-for-bit
     guarantee of the sharded run rests on.  A generator of two steps: ``next`` gives the two chain seeds, ``send(null)``
