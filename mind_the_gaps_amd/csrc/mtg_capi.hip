@@ -1003,6 +1003,69 @@ struct PredictAtRoom {
     }
 };
 
+// what mtg_lag_sums and mtg_cross_sums refuse about their bins, in the order both always did (lag: no negative lags)
+int lag_refuse_edges(mtg_ctx *ctx, const char *who, int nbins, const double *edges, bool nothing_asked, bool allow_negative)
+{
+    if (nbins < 1 || nbins > MTG_LAG_MAX_BINS) return fail(ctx, MTG_E_ARG, "%s: nbins = %d is outside 1 .. %d", who, nbins, MTG_LAG_MAX_BINS);
+    if (!edges) return fail(ctx, MTG_E_ARG, "%s: need nbins + 1 edges", who);
+    if (nothing_asked) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
+    for (int b = 0; b <= nbins; ++b)
+        if (!std::isfinite(edges[b])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] is not finite", who, b);
+    if (!allow_negative && edges[0] < 0.0) return fail(ctx, MTG_E_ARG, "%s: edges[0] = %g is negative", who, edges[0]);
+    for (int b = 0; b < nbins; ++b)
+        if (!(edges[b] < edges[b + 1])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] = %g is not above edges[%d] = %g", who, b + 1, edges[b + 1], b, edges[b]);
+    return MTG_OK;
+}
+
+// The K optional outputs of a lag-bin entry, each NULL or [L][nbins] of 8-byte entries, in the order of its arguments --
+// which is the order of the planner's MTG_LAG_* / MTG_CROSS_* bits: where the host wants each and its room on the device.
+template <int K>
+struct LagOutputs {
+    void *host[K];
+    DevBuf dev[K];
+    size_t bytes = 0;
+    int what() const
+    {
+        int bits = 0;
+        for (int k = 0; k < K; ++k) bits |= host[k] ? 1 << k : 0;
+        return bits;
+    }
+    void reserve(RowCall &c, int64_t L, int nbins)
+    {
+        bytes = (size_t)L * (size_t)nbins * 8;
+        for (int k = 0; k < K; ++k) c.reserve({{dev[k], host[k] ? bytes : 0}});
+    }
+    template <class T = double> T *at(int k) const { return host[k] ? dev[k].template as<T>() : nullptr; }   // on the device
+    void gather(RowCall &c)
+    {
+        for (int k = 0; k < K; ++k)
+            if (host[k]) c.gather(host[k], dev[k].p, bytes);
+    }
+};
+static_assert(MTG_LAG_COUNT == 1 << 0 && MTG_LAG_LAG == 1 << 1 && MTG_LAG_SF == 1 << 2 && MTG_LAG_CF == 1 << 3 && MTG_LAG_CF2 == 1 << 4 &&
+                  MTG_LAG_NOISE == 1 << 5, "bit k is output k of mtg_lag_sums");
+static_assert(MTG_CROSS_COUNT == 1 << 0 && MTG_CROSS_LAG == 1 << 1 && MTG_CROSS_CF == 1 << 2 && MTG_CROSS_CF2 == 1 << 3 && MTG_CROSS_SA == 1 << 4 &&
+                  MTG_CROSS_SB == 1 << 5 && MTG_CROSS_SAA == 1 << 6 && MTG_CROSS_SBB == 1 << 7, "bit k is output k of mtg_cross_sums");
+
+// the pre-pass (`stats`) and every slab's launch between the call's two events (mtg_last_kernel_ms)
+template <class Stats, class Launch>
+void lag_run_slabs(RowCall &c, int64_t L, int64_t slab, Stats stats, Launch launch)
+{
+    mtg_ctx *ctx = c.ctx;
+    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
+    c.then([&] {
+        stats();
+        return hipGetLastError();
+    });
+    if (c.ok()) c.e = for_each_slab(L, slab, [&](int64_t l0, int64_t rows) {
+        // (the next slab's sweep overwrites the workspace only after this slab's reduction: one stream)
+        c.then([&] { return launch(l0, rows); });
+        return c.e;
+    });
+    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
+    if (c.ok()) ctx->timed = true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2782,51 +2845,25 @@ MTG_API int mtg_lag_sums(mtg_ctx *ctx, int nbins, const double *edges, int64_t *
     RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
     int rc = c.ready(false);
     if (rc) return rc;
-    if (nbins < 1 || nbins > MTG_LAG_MAX_BINS) return fail(ctx, MTG_E_ARG, "%s: nbins = %d is outside 1 .. %d", who, nbins, MTG_LAG_MAX_BINS);
-    if (!edges) return fail(ctx, MTG_E_ARG, "%s: need nbins + 1 edges", who);
-    if (!count && !lag && !sf && !cf && !cf2 && !noise) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
-    for (int b = 0; b <= nbins; ++b)
-        if (!std::isfinite(edges[b])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] is not finite", who, b);
-    if (edges[0] < 0.0) return fail(ctx, MTG_E_ARG, "%s: edges[0] = %g is negative", who, edges[0]);
-    for (int b = 0; b < nbins; ++b)
-        if (!(edges[b] < edges[b + 1])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] = %g is not above edges[%d] = %g", who, b + 1, edges[b + 1], b, edges[b]);
+    LagOutputs<6> out;
+    out.host[0] = count; out.host[1] = lag; out.host[2] = sf; out.host[3] = cf; out.host[4] = cf2; out.host[5] = noise;
+    if ((rc = lag_refuse_edges(ctx, who, nbins, edges, out.what() == 0, false))) return rc;
     if (ctx->N < 2) return fail(ctx, MTG_E_ARG, "%s: N = %lld < 2 samples (no pairs)", who, (long long)ctx->N);
     if ((rc = c.begin(false))) return rc;
     const int64_t L = ctx->L;
-    const int what = (count ? MTG_LAG_COUNT : 0) | (lag ? MTG_LAG_LAG : 0) | (sf ? MTG_LAG_SF : 0) | (cf ? MTG_LAG_CF : 0) |
-                     (cf2 ? MTG_LAG_CF2 : 0) | (noise ? MTG_LAG_NOISE : 0);
-    const MtgLagPlan plan = mtg_lag_plan(ctx->N, nbins, L, !ctx->t_per_lc, what);
-    const size_t out_bytes = (size_t)L * (size_t)nbins * 8;
-    DevBuf d_edges, d_stats, d_ws, d_count, d_lag, d_sf, d_cf, d_cf2, d_noise;
-    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_stats, (size_t)L * 32}, {d_ws, (size_t)plan.ws_bytes}, {d_count, count ? out_bytes : 0},
-               {d_lag, lag ? out_bytes : 0}, {d_sf, sf ? out_bytes : 0}, {d_cf, cf ? out_bytes : 0}, {d_cf2, cf2 ? out_bytes : 0},
-               {d_noise, noise ? out_bytes : 0}});
+    const MtgLagPlan plan = mtg_lag_plan(ctx->N, nbins, L, !ctx->t_per_lc, out.what());
+    DevBuf d_edges, d_stats, d_ws;
+    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_stats, (size_t)L * 32}, {d_ws, (size_t)plan.ws_bytes}});
+    out.reserve(c, L, nbins);
     c.upload(d_edges.p, edges, (size_t)(nbins + 1) * 8);
     MtgLagArgs qa;
     qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, 0, d_stats.as<double>(), nullptr);
     qa.nbins = nbins; qa.edges = d_edges.as<double>(); qa.ws = d_ws.as<double>();
-    qa.count = count ? d_count.as<int64_t>() : nullptr; qa.lag = lag ? d_lag.as<double>() : nullptr;
-    qa.sf = sf ? d_sf.as<double>() : nullptr; qa.cf = cf ? d_cf.as<double>() : nullptr;
-    qa.cf2 = cf2 ? d_cf2.as<double>() : nullptr; qa.noise = noise ? d_noise.as<double>() : nullptr;
+    qa.count = out.at<int64_t>(0); qa.lag = out.at(1); qa.sf = out.at(2); qa.cf = out.at(3); qa.cf2 = out.at(4); qa.noise = out.at(5);
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_lag_kernel<%d,%d> lanes %d", plan.tile, plan.all, (int)MTG_LAG_LANES);
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(L, plan.slab, [&](int64_t l0, int64_t rows) {
-        // (the next slab's sweep overwrites the workspace only after this slab's reduction: one stream)
-        c.then([&] { return mtg_launch_lag(qa, plan, l0, rows, c.s); });
-        return c.e;
-    });
-    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
-    if (c.ok()) ctx->timed = true;
-    if (count) c.gather(count, d_count.p, out_bytes);
-    if (lag) c.gather(lag, d_lag.p, out_bytes);
-    if (sf) c.gather(sf, d_sf.p, out_bytes);
-    if (cf) c.gather(cf, d_cf.p, out_bytes);
-    if (cf2) c.gather(cf2, d_cf2.p, out_bytes);
-    if (noise) c.gather(noise, d_noise.p, out_bytes);
+    lag_run_slabs(c, L, plan.slab, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); },
+                  [&](int64_t l0, int64_t rows) { return mtg_launch_lag(qa, plan, l0, rows, c.s); });
+    out.gather(c);
     return c.finish(nullptr);
 }
 
@@ -2838,16 +2875,13 @@ MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2
     int rc = c.ready(false);
     if (rc) return rc;
     const int64_t L = ctx->L;
+    LagOutputs<8> out;
+    out.host[0] = count; out.host[1] = lag; out.host[2] = cf; out.host[3] = cf2;
+    out.host[4] = sa; out.host[5] = sb; out.host[6] = saa; out.host[7] = sbb;
     if (M < 1 || M >= MTG_CROSS_MAX_M) return fail(ctx, MTG_E_ARG, "%s: M = %lld is outside 1 .. 2^28 - 1", who, (long long)M);
     if (L2 != 1 && L2 != L) return fail(ctx, MTG_E_ARG, "%s: L2 = %lld is neither 1 nor L = %lld", who, (long long)L2, (long long)L);
     if (!t2 || !y2) return fail(ctx, MTG_E_ARG, "%s: need the companion's M times and L2 x M values", who);
-    if (nbins < 1 || nbins > MTG_LAG_MAX_BINS) return fail(ctx, MTG_E_ARG, "%s: nbins = %d is outside 1 .. %d", who, nbins, MTG_LAG_MAX_BINS);
-    if (!edges) return fail(ctx, MTG_E_ARG, "%s: need nbins + 1 edges", who);
-    if (!count && !lag && !cf && !cf2 && !sa && !sb && !saa && !sbb) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
-    for (int b = 0; b <= nbins; ++b)
-        if (!std::isfinite(edges[b])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] is not finite", who, b);
-    for (int b = 0; b < nbins; ++b)
-        if (!(edges[b] < edges[b + 1])) return fail(ctx, MTG_E_ARG, "%s: edges[%d] = %g is not above edges[%d] = %g", who, b + 1, edges[b + 1], b, edges[b]);
+    if ((rc = lag_refuse_edges(ctx, who, nbins, edges, out.what() == 0, true))) return rc;
     for (int64_t j = 0; j < M; ++j) {
         if (!std::isfinite(t2[j])) return fail(ctx, MTG_E_ARG, "%s: t2[%lld] is not finite", who, (long long)j);
         if (j > 0 && t2[j] < t2[j - 1])
@@ -2857,19 +2891,16 @@ MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2
     for (int64_t k = 0; k < L2 * M; ++k)
         if (!std::isfinite(y2[k])) return fail(ctx, MTG_E_ARG, "%s: y2[%lld][%lld] is not finite", who, (long long)(k / M), (long long)(k % M));
     if ((rc = c.begin(false))) return rc;
-    const int what = (count ? MTG_CROSS_COUNT : 0) | (lag ? MTG_CROSS_LAG : 0) | (cf ? MTG_CROSS_CF : 0) | (cf2 ? MTG_CROSS_CF2 : 0) |
-                     (sa ? MTG_CROSS_SA : 0) | (sb ? MTG_CROSS_SB : 0) | (saa ? MTG_CROSS_SAA : 0) | (sbb ? MTG_CROSS_SBB : 0);
     // (a set of one light curve has L2 == 1 == L: the shared-companion kernel, the same arithmetic)
-    const MtgCrossPlan plan = mtg_cross_plan(ctx->N, M, nbins, L, !ctx->t_per_lc, L2 == L && L > 1, what);
-    const size_t out_bytes = (size_t)L * (size_t)nbins * 8, rows2 = (size_t)L2 * (size_t)M;
+    const MtgCrossPlan plan = mtg_cross_plan(ctx->N, M, nbins, L, !ctx->t_per_lc, L2 == L && L > 1, out.what());
+    const size_t rows2 = (size_t)L2 * (size_t)M;
     // the companion as the pre-pass reads a light curve: (value, variance) pairs; the variance is not read unweighted
     std::vector<double2> pairs(rows2);
     for (size_t k = 0; k < rows2; ++k) pairs[k] = make_double2(y2[k], 1.0);
-    DevBuf d_edges, d_stats, d_t2, d_yv2, d_stats2, d_ws, d_count, d_lag, d_cf, d_cf2, d_sa, d_sb, d_saa, d_sbb;
+    DevBuf d_edges, d_stats, d_t2, d_yv2, d_stats2, d_ws;
     c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_stats, (size_t)L * 32}, {d_t2, (size_t)M * 8}, {d_yv2, rows2 * 16},
-               {d_stats2, (size_t)L2 * 32}, {d_ws, (size_t)plan.ws_bytes}, {d_count, count ? out_bytes : 0}, {d_lag, lag ? out_bytes : 0},
-               {d_cf, cf ? out_bytes : 0}, {d_cf2, cf2 ? out_bytes : 0}, {d_sa, sa ? out_bytes : 0}, {d_sb, sb ? out_bytes : 0},
-               {d_saa, saa ? out_bytes : 0}, {d_sbb, sbb ? out_bytes : 0}});
+               {d_stats2, (size_t)L2 * 32}, {d_ws, (size_t)plan.ws_bytes}});
+    out.reserve(c, L, nbins);
     c.upload(d_edges.p, edges, (size_t)(nbins + 1) * 8);
     c.upload(d_t2.p, t2, (size_t)M * 8);
     c.upload(d_yv2.p, pairs.data(), rows2 * 16);
@@ -2880,33 +2911,13 @@ MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2
     companion.stats = d_stats2.as<double>();
     qa.M = M; qa.t2 = d_t2.as<double>(); qa.yv2 = d_yv2.as<double2>(); qa.stats2 = d_stats2.as<double>();
     qa.nbins = nbins; qa.edges = d_edges.as<double>(); qa.ws = d_ws.as<double>();
-    qa.count = count ? d_count.as<int64_t>() : nullptr; qa.lag = lag ? d_lag.as<double>() : nullptr;
-    qa.cf = cf ? d_cf.as<double>() : nullptr; qa.cf2 = cf2 ? d_cf2.as<double>() : nullptr;
-    qa.sa = sa ? d_sa.as<double>() : nullptr; qa.sb = sb ? d_sb.as<double>() : nullptr;
-    qa.saa = saa ? d_saa.as<double>() : nullptr; qa.sbb = sbb ? d_sbb.as<double>() : nullptr;
+    qa.count = out.at<int64_t>(0); qa.lag = out.at(1); qa.cf = out.at(2); qa.cf2 = out.at(3);
+    qa.sa = out.at(4); qa.sb = out.at(5); qa.saa = out.at(6); qa.sbb = out.at(7);
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_cross_kernel<%d,%d,%d> lanes %d", plan.tile, plan.per, plan.all,
              (int)MTG_CROSS_LANES);
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
-        mtg_launch_lomb_scargle_stats(companion, c.s);
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(L, plan.slab, [&](int64_t l0, int64_t rows) {
-        // (the next slab's sweep overwrites the workspace only after this slab's reduction: one stream)
-        c.then([&] { return mtg_launch_cross(qa, plan, l0, rows, c.s); });
-        return c.e;
-    });
-    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
-    if (c.ok()) ctx->timed = true;
-    if (count) c.gather(count, d_count.p, out_bytes);
-    if (lag) c.gather(lag, d_lag.p, out_bytes);
-    if (cf) c.gather(cf, d_cf.p, out_bytes);
-    if (cf2) c.gather(cf2, d_cf2.p, out_bytes);
-    if (sa) c.gather(sa, d_sa.p, out_bytes);
-    if (sb) c.gather(sb, d_sb.p, out_bytes);
-    if (saa) c.gather(saa, d_saa.p, out_bytes);
-    if (sbb) c.gather(sbb, d_sbb.p, out_bytes);
+    lag_run_slabs(c, L, plan.slab, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); mtg_launch_lomb_scargle_stats(companion, c.s); },
+                  [&](int64_t l0, int64_t rows) { return mtg_launch_cross(qa, plan, l0, rows, c.s); });
+    out.gather(c);
     return c.finish(nullptr);   // (waits for the stream: `pairs` outlives its upload)
 }
 

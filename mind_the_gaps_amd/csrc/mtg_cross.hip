@@ -242,13 +242,8 @@ hipError_t cross_launch(const MtgCrossKernelArgs &g, const MtgCrossOut &o, const
 hipError_t mtg_launch_cross(const MtgCrossArgs &q, const MtgCrossPlan &plan, int64_t l0, int64_t Ls, hipStream_t s)
 {
     const MtgLombScargleArgs &ls = q.ls;
-    const int64_t blocks = mtg_cross_blocks(plan, Ls);
-    if (q.nbins < 1 || q.nbins > MTG_LAG_PLAN_MAX_BINS || ls.N < 1 || q.M < 1 || q.M >= MTG_CROSS_MAX_M || blocks == 0 || Ls < 1 ||
-        l0 < 0 || l0 + Ls > ls.L || Ls > 0x7fffffff / q.nbins || (plan.per_lc != 2 && plan.per_lc != 4) || plan.per_tile != 2 ||
-        plan.per_lc != (plan.all ? 4 : 2) || plan.row_blocks != (ls.N + MTG_CROSS_LANES - 1) / MTG_CROSS_LANES ||
-        (plan.tile != 1 && ls.t_stride != 0) ||
-        mtg_lag_ws_bytes(ls.N, q.nbins, plan.tile, plan.per_lc, plan.per_tile, Ls) > plan.ws_bytes)
-        return hipErrorInvalidValue;
+    const int64_t blocks = mtg_lag_launch_blocks(plan, ls.N, ls.t_stride, ls.L, q.nbins, l0, Ls);
+    if (blocks == 0 || q.M < 1 || q.M >= MTG_CROSS_MAX_M || plan.per_lc != (plan.all ? 4 : 2) || plan.per_tile != 2) return hipErrorInvalidValue;
     MtgCrossKernelArgs g;
     g.dxt = ls.dxt; g.yv = ls.yv; g.N = ls.N; g.t_stride = ls.t_stride; g.l0 = l0; g.Ls = Ls;
     g.stats = reinterpret_cast<const double4 *>(ls.stats);

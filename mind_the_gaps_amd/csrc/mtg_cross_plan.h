@@ -33,17 +33,9 @@ enum {
     MTG_CROSS_LIGHT = MTG_CROSS_COUNT | MTG_CROSS_LAG | MTG_CROSS_CF | MTG_CROSS_CF2
 };
 
-struct MtgCrossPlan {
-    int tile;              // light curves per lane: 1, 4 or MTG_CROSS_TILE
+struct MtgCrossPlan : MtgLagPlan {   // all = 0: the kernel that forms count, lag, cf, cf2; 1: the one that forms sb and sbb too
     int per;               // the companion: 0 one row for every light curve, 1 a row per light curve
-    int all;               // 0: the kernel that forms count, lag, cf, cf2; 1: the one that forms sb and sbb too
-    int per_lc;            // workspace arrays with an entry per light curve: 2 or 4
-    int per_tile;          // ... and per tile: 2 (lag, count)
-    int64_t row_blocks;    // workgroups along the resident rows
     int64_t chunks;        // chunks of companion columns
-    int64_t slab;          // light curves per slab: whole tiles, at most L
-    int64_t ws_bytes;      // of one slab
-    int lds_bytes;         // of one workgroup
 };
 
 static constexpr int mtg_cross_lds_bytes(int tile, int per)
@@ -56,27 +48,16 @@ static constexpr int mtg_cross_lds_bytes(int tile, int per)
 static inline MtgCrossPlan mtg_cross_plan(int64_t N, int64_t M, int nbins, int64_t L, int shared_sampling, int companion_per_lc, int what,
                                           int64_t ws_limit = MTG_CROSS_WS_BYTES)
 {
+    const int all = (what & ~MTG_CROSS_LIGHT) ? 1 : 0;
     MtgCrossPlan p;
-    p.tile = !shared_sampling || L == 1 ? 1 : L <= 4 ? 4 : MTG_CROSS_TILE;
+    static_cast<MtgLagPlan &>(p) = mtg_lag_sweep_plan(N, nbins, L, shared_sampling, all, all ? 4 : 2, 2, ws_limit);
     p.per = companion_per_lc ? 1 : 0;
-    p.all = (what & ~MTG_CROSS_LIGHT) ? 1 : 0;
-    p.per_lc = p.all ? 4 : 2;
-    p.per_tile = 2;
-    p.row_blocks = (N + MTG_CROSS_LANES - 1) / MTG_CROSS_LANES;
     p.chunks = (M + MTG_CROSS_CHUNK - 1) / MTG_CROSS_CHUNK;
-    int64_t rows = ws_limit / mtg_lag_ws_bytes(N, nbins, p.tile, p.per_lc, p.per_tile, p.tile) * p.tile;
-    if (rows < p.tile) rows = p.tile;
-    p.slab = rows > L ? L : rows;
-    p.ws_bytes = mtg_lag_ws_bytes(N, nbins, p.tile, p.per_lc, p.per_tile, p.slab);
     p.lds_bytes = mtg_cross_lds_bytes(p.tile, p.per);
     return p;
 }
 
-// workgroups of a launch over `rows` light curves (0: more than a grid holds)
-static inline int64_t mtg_cross_blocks(const MtgCrossPlan &p, int64_t rows)
-{
-    const int64_t tiles = (rows + p.tile - 1) / p.tile;
-    return p.row_blocks > 0x7fffffff / tiles ? 0 : p.row_blocks * tiles;
-}
+// (tests/cross_plan_driver.cpp's name for it)
+static inline int64_t mtg_cross_blocks(const MtgCrossPlan &p, int64_t rows) { return mtg_lag_blocks(p, rows); }
 
 #endif

@@ -386,7 +386,8 @@ struct MtgLagArgs {
     int64_t *count;
     double *lag, *sf, *cf, *cf2, *noise;
 };
-// (hipErrorInvalidValue: more workgroups than a grid holds, or a plan that is not mtg_lag_plan's for these outputs)
+// (hipErrorInvalidValue: more workgroups than a grid holds, a slab outside the set, or a plan that is not mtg_lag_plan's for
+// these sizes and outputs: mtg_lag_launch_blocks)
 hipError_t mtg_launch_lag(const MtgLagArgs &, const MtgLagPlan &, int64_t l0, int64_t Ls, hipStream_t);
 
 // One slab [l0, l0 + Ls) of mtg_cross_sums (mtg_cross.hip; instantiation, workspace and slab: mtg_cross_plan.h).  `ls` is
@@ -406,7 +407,8 @@ struct MtgCrossArgs {
     int64_t *count;
     double *lag, *cf, *cf2, *sa, *sb, *saa, *sbb;
 };
-// (hipErrorInvalidValue: more workgroups than a grid holds, or a plan that is not mtg_cross_plan's for these outputs)
+// (hipErrorInvalidValue: more workgroups than a grid holds, a slab outside the set, or a plan that is not mtg_cross_plan's for
+// these sizes and outputs: mtg_lag_launch_blocks)
 hipError_t mtg_launch_cross(const MtgCrossArgs &, const MtgCrossPlan &, int64_t l0, int64_t Ls, hipStream_t);
 
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);

@@ -204,10 +204,8 @@ hipError_t lag_launch(const MtgLagKernelArgs &g, const MtgLagOut &o, bool all, i
 hipError_t mtg_launch_lag(const MtgLagArgs &q, const MtgLagPlan &plan, int64_t l0, int64_t Ls, hipStream_t s)
 {
     const MtgLombScargleArgs &ls = q.ls;
-    const int64_t blocks = mtg_lag_blocks(plan, Ls);
-    if (q.nbins < 1 || q.nbins > MTG_LAG_PLAN_MAX_BINS || ls.N < 2 || blocks == 0 || Ls > 0x7fffffff / q.nbins ||
-        mtg_lag_ws_bytes(ls.N, q.nbins, plan.tile, plan.per_lc, plan.per_tile, Ls) > plan.ws_bytes)
-        return hipErrorInvalidValue;
+    const int64_t blocks = mtg_lag_launch_blocks(plan, ls.N, ls.t_stride, ls.L, q.nbins, l0, Ls);
+    if (blocks == 0 || ls.N < 2 || plan.per_lc != (plan.all ? 4 : 1) || plan.per_tile != (plan.all ? 2 : 0)) return hipErrorInvalidValue;
     MtgLagKernelArgs g;
     g.dxt = ls.dxt; g.yv = ls.yv; g.N = ls.N; g.t_stride = ls.t_stride; g.l0 = l0; g.Ls = Ls;
     g.stats = reinterpret_cast<const double4 *>(ls.stats);

@@ -31,11 +31,12 @@ enum { MTG_LAG_CHUNK = 256, MTG_LAG_LANES = 256, MTG_LAG_TILE = 8, MTG_LAG_PLAN_
 // which sums a call asks for, as bits; the kernel is compiled for MTG_LAG_SF alone and for everything
 enum { MTG_LAG_COUNT = 1, MTG_LAG_LAG = 2, MTG_LAG_SF = 4, MTG_LAG_CF = 8, MTG_LAG_CF2 = 16, MTG_LAG_NOISE = 32 };
 
+// what both pair sweeps plan (mtg_lag.hip, mtg_cross.hip): mtg_cross_plan.h extends it
 struct MtgLagPlan {
     int tile;              // light curves per lane: 1, 4 or MTG_LAG_TILE
-    int all;               // 0: the kernel that forms sf alone; 1: the one that forms all six
-    int per_lc;            // workspace arrays with an entry per light curve: 1 (sf alone) or 4
-    int per_tile;          // ... and per tile: 0 or 2 (count, lag)
+    int all;               // 0: the lighter kernel of the entry; 1: the one that forms every sum
+    int per_lc;            // workspace arrays with an entry per light curve
+    int per_tile;          // ... and per tile: 0 or 2 (lag, count)
     int64_t row_blocks;    // workgroups along the rows
     int64_t slab;          // light curves per slab: whole tiles, at most L
     int64_t ws_bytes;      // of one slab
@@ -53,19 +54,30 @@ static inline int64_t mtg_lag_ws_bytes(int64_t N, int nbins, int tile, int per_l
     return ((int64_t)per_lc * rows + (int64_t)per_tile * ((rows + tile - 1) / tile)) * nbins * N * 8;
 }
 
-// nbins in 1 .. 128, N >= 2, L >= 1, `what` a non-empty set of MTG_LAG_* bits (the caller's checks)
-static inline MtgLagPlan mtg_lag_plan(int64_t N, int nbins, int64_t L, int shared_sampling, int what)
+// The tile and the slab of a sweep over N rows that keeps per_lc + per_tile arrays, in at most ws_limit bytes of workspace
+// unless one tile alone needs more (lds_bytes is the caller's).
+static inline MtgLagPlan mtg_lag_sweep_plan(int64_t N, int nbins, int64_t L, int shared_sampling, int all, int per_lc, int per_tile,
+                                            int64_t ws_limit)
 {
     MtgLagPlan p;
     p.tile = !shared_sampling || L == 1 ? 1 : L <= 4 ? 4 : MTG_LAG_TILE;
-    p.all = (what & ~MTG_LAG_SF) ? 1 : 0;
-    p.per_lc = p.all ? 4 : 1;
-    p.per_tile = p.all ? 2 : 0;
+    p.all = all;
+    p.per_lc = per_lc;
+    p.per_tile = per_tile;
     p.row_blocks = (N + MTG_LAG_LANES - 1) / MTG_LAG_LANES;
-    int64_t rows = MTG_LAG_WS_BYTES / mtg_lag_ws_bytes(N, nbins, p.tile, p.per_lc, p.per_tile, p.tile) * p.tile;
+    int64_t rows = ws_limit / mtg_lag_ws_bytes(N, nbins, p.tile, p.per_lc, p.per_tile, p.tile) * p.tile;
     if (rows < p.tile) rows = p.tile;
     p.slab = rows > L ? L : rows;
     p.ws_bytes = mtg_lag_ws_bytes(N, nbins, p.tile, p.per_lc, p.per_tile, p.slab);
+    p.lds_bytes = 0;
+    return p;
+}
+
+// nbins in 1 .. 128, N >= 2, L >= 1, `what` a non-empty set of MTG_LAG_* bits (the caller's checks)
+static inline MtgLagPlan mtg_lag_plan(int64_t N, int nbins, int64_t L, int shared_sampling, int what)
+{
+    const int all = (what & ~MTG_LAG_SF) ? 1 : 0;
+    MtgLagPlan p = mtg_lag_sweep_plan(N, nbins, L, shared_sampling, all, all ? 4 : 1, all ? 2 : 0, MTG_LAG_WS_BYTES);
     p.lds_bytes = mtg_lag_lds_bytes(p.tile, p.all);
     return p;
 }
@@ -75,6 +87,18 @@ static inline int64_t mtg_lag_blocks(const MtgLagPlan &p, int64_t rows)
 {
     const int64_t tiles = (rows + p.tile - 1) / p.tile;
     return p.row_blocks > 0x7fffffff / tiles ? 0 : p.row_blocks * tiles;
+}
+
+// Whether the slab [l0, l0 + Ls) of a set of L light curves of N samples can be launched with this plan: the sizes in
+// range, the plan the one its planner makes for them, the workspace within the plan's.  -> its workgroups, 0 if not.
+static inline int64_t mtg_lag_launch_blocks(const MtgLagPlan &p, int64_t N, int64_t t_stride, int64_t L, int nbins, int64_t l0, int64_t Ls)
+{
+    if (nbins < 1 || nbins > MTG_LAG_PLAN_MAX_BINS || N < 1 || Ls < 1 || l0 < 0 || l0 + Ls > L || Ls > 0x7fffffff / nbins ||
+        p.tile < 1 || (p.tile != 1 && t_stride != 0) ||
+        p.row_blocks != (N + MTG_LAG_LANES - 1) / MTG_LAG_LANES ||
+        mtg_lag_ws_bytes(N, nbins, p.tile, p.per_lc, p.per_tile, Ls) > p.ws_bytes)
+        return 0;
+    return mtg_lag_blocks(p, Ls);
 }
 
 #endif
