@@ -890,37 +890,55 @@ int check_ready(mtg_ctx *ctx, bool need_model)
     return MTG_OK;
 }
 
-// One host-pointer call over rows of theta in flight (`who`: mtg_loglike_batch, mtg_loglike_coeffs, mtg_predict,
-// mtg_predict_at, mtg_predict_terms, mtg_gp_draw, mtg_gp_cond_draw, mtg_loglike_grad, mtg_apply_inverse).  The entry runs ready, its own argument checks and
-// begin -- in that order; each returns at once, nothing is queued yet -- then the stages below and its own reservations
-// and launches.  From stage_inputs on nothing returns early: a step runs only while the call is ok(), the first failure
-// is kept -- a HIP error in `e`, or in `rc` the code of a helper that has written its own report -- and finish() is the
-// one way out: it waits for the stream whatever happened, so that the caller's arrays are no longer the target of a
-// queued copy when the call returns, and reports "who: <HIP error>".
-struct RowCall {
+// The stream and the stages of one host-pointer call in flight.  Once the entry has its stream nothing returns early: a
+// step runs only while the call is ok(), the first failure is kept -- a HIP error in `e`, or in `rc` the code of a helper
+// that has written its own report -- and finish() is the one way out: it waits for the stream whatever happened, so that
+// the caller's arrays are no longer the target of a queued copy when the call returns, and reports "who: <HIP error>".
+struct StagedCall {
     mtg_ctx *ctx;
     const char *who;
-    int64_t B;
-    const double *theta;             // [B][P] on the host
-    const int32_t *lc_index;         // [B] on the host, or NULL: light curve 0
-    int add_prior;
     hipStream_t s = nullptr;
-    const int32_t *d_lc = nullptr;   // stage_inputs: lc_index on the device, NULL when lc_index is (never an earlier call's)
     hipError_t e = hipSuccess;
     int rc = MTG_OK;
     struct Room { DevBuf &buf; size_t bytes; };
+    StagedCall(mtg_ctx *ctx_, const char *who_) : ctx(ctx_), who(who_) {}
 
     bool ok() const { return rc == MTG_OK && e == hipSuccess; }
-    int ready(bool need_model = true) { return check_ready(ctx, need_model); }
-    int bad_arguments() { return fail(ctx, MTG_E_ARG, "%s: bad arguments", who); }
-    int begin(bool refuse_profile);
-    void stage_inputs(bool with_theta = true);
-    void expand(MtgRowArgs &head, DevBuf *owner = nullptr);
     template <class F> void then(F step) { if (ok()) e = step(); }   // step() -> hipError_t
     void reserve(std::initializer_list<Room> rooms) { for (const Room &r : rooms) then([&] { return r.buf.reserve(r.bytes); }); }
     void upload(void *dev, const void *host, size_t bytes) { then([&] { return hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s); }); }
     void gather(void *host, const void *dev, size_t bytes) { then([&] { return hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s); }); }
     void sync() { then([&] { return hipStreamSynchronize(s); }); }
+    int finish();
+};
+
+// the stream waited for: the end of every staged call, and the only place where one reports a HIP error
+int StagedCall::finish()
+{
+    const hipError_t drained = hipStreamSynchronize(s);
+    if (ok()) e = drained;
+    if (rc) return rc;
+    return e == hipSuccess ? MTG_OK : fail(ctx, MTG_E_HIP, "%s: %s", who, hipGetErrorString(e));
+}
+
+// One host-pointer call over rows of theta (`who`: mtg_loglike_batch, mtg_loglike_coeffs, mtg_predict, mtg_predict_at,
+// mtg_predict_terms, mtg_gp_draw, mtg_gp_cond_draw, mtg_loglike_grad, mtg_apply_inverse).  The entry runs ready, its own
+// argument checks and begin -- in that order; each returns at once, nothing is queued yet -- then the stages below and its
+// own reservations and launches, and leaves through finish(status).
+struct RowCall : StagedCall {
+    int64_t B;
+    const double *theta;             // [B][P] on the host
+    const int32_t *lc_index;         // [B] on the host, or NULL: light curve 0
+    int add_prior;
+    const int32_t *d_lc = nullptr;   // stage_inputs: lc_index on the device, NULL when lc_index is (never an earlier call's)
+    RowCall(mtg_ctx *ctx_, const char *who_, int64_t B_, const double *theta_, const int32_t *lc_index_, int add_prior_)
+        : StagedCall(ctx_, who_), B(B_), theta(theta_), lc_index(lc_index_), add_prior(add_prior_) {}
+
+    int ready(bool need_model = true) { return check_ready(ctx, need_model); }
+    int bad_arguments() { return fail(ctx, MTG_E_ARG, "%s: bad arguments", who); }
+    int begin(bool refuse_profile);
+    void stage_inputs(bool with_theta = true);
+    void expand(MtgRowArgs &head, DevBuf *owner = nullptr);
     int finish(int32_t *status);
 };
 
@@ -968,14 +986,11 @@ void RowCall::expand(MtgRowArgs &head, DevBuf *owner)
 }
 
 // the statuses on their way to the host behind the entry's own results (NULL: the entry has fetched them), then the
-// stream waited for: the end of every row entry, and the only place where one reports a HIP error
+// stream waited for: the end of every row entry
 int RowCall::finish(int32_t *status)
 {
     if (status) gather(status, ctx->status.p, (size_t)B * 4);
-    const hipError_t drained = hipStreamSynchronize(s);
-    if (ok()) e = drained;
-    if (rc) return rc;
-    return e == hipSuccess ? MTG_OK : fail(ctx, MTG_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    return StagedCall::finish();
 }
 
 // The workspace of one slab of Bs rows of the new-time prediction (mtg_predict_at, mtg_gp_cond_draw) and everything of
@@ -1017,10 +1032,11 @@ int lag_refuse_edges(mtg_ctx *ctx, const char *who, int nbins, const double *edg
     return MTG_OK;
 }
 
-// The K optional outputs of a lag-bin entry, each NULL or [L][nbins] of 8-byte entries, in the order of its arguments --
-// which is the order of the planner's MTG_LAG_* / MTG_CROSS_* bits: where the host wants each and its room on the device.
+// K optional outputs of one entry, each NULL or the same number of 8-byte entries, in the order of its arguments: where
+// the host wants each and its room on the device.  (mtg_lag_sums, mtg_cross_sums: the order of the planner's MTG_LAG_* /
+// MTG_CROSS_* bits.)
 template <int K>
-struct LagOutputs {
+struct OptionalOutputs {
     void *host[K];
     DevBuf dev[K];
     size_t bytes = 0;
@@ -1030,13 +1046,13 @@ struct LagOutputs {
         for (int k = 0; k < K; ++k) bits |= host[k] ? 1 << k : 0;
         return bits;
     }
-    void reserve(RowCall &c, int64_t L, int nbins)
+    void reserve(StagedCall &c, size_t entries)
     {
-        bytes = (size_t)L * (size_t)nbins * 8;
+        bytes = entries * 8;
         for (int k = 0; k < K; ++k) c.reserve({{dev[k], host[k] ? bytes : 0}});
     }
-    template <class T = double> T *at(int k) const { return host[k] ? dev[k].template as<T>() : nullptr; }   // on the device
-    void gather(RowCall &c)
+    template <class T = double> T *at(int k, int64_t entry = 0) const { return host[k] ? dev[k].template as<T>() + entry : nullptr; }   // on the device
+    void gather(StagedCall &c)
     {
         for (int k = 0; k < K; ++k)
             if (host[k]) c.gather(host[k], dev[k].p, bytes);
@@ -1047,23 +1063,82 @@ static_assert(MTG_LAG_COUNT == 1 << 0 && MTG_LAG_LAG == 1 << 1 && MTG_LAG_SF == 
 static_assert(MTG_CROSS_COUNT == 1 << 0 && MTG_CROSS_LAG == 1 << 1 && MTG_CROSS_CF == 1 << 2 && MTG_CROSS_CF2 == 1 << 3 && MTG_CROSS_SA == 1 << 4 &&
                   MTG_CROSS_SB == 1 << 5 && MTG_CROSS_SAA == 1 << 6 && MTG_CROSS_SBB == 1 << 7, "bit k is output k of mtg_cross_sums");
 
-// the pre-pass (`stats`) and every slab's launch between the call's two events (mtg_last_kernel_ms)
-template <class Stats, class Launch>
-void lag_run_slabs(RowCall &c, int64_t L, int64_t slab, Stats stats, Launch launch)
+// One host-pointer call on the resident light curves alone: no model, no rows of theta (`who`: mtg_lomb_scargle / _multi,
+// mtg_lomb_scargle_envelope / _multi, mtg_epoch_fold, mtg_phase_fold, mtg_wwz, mtg_lag_sums, mtg_cross_sums).  The entry
+// runs ready, its refusals and begin -- in that order; each returns at once, nothing is queued yet -- then reserves what
+// is its own, takes the pre-pass arguments from args() (the last of the call's allocations: no hipMalloc behind a queued
+// copy), uploads, queues its kernels with run_slabs(), gathers and leaves through finish().
+struct ResidentCall : StagedCall {
+    DevBuf stats, peak, index;   // args: the pre-pass's [L][4]; reserve_peaks: [L] maxima and where each is
+    using StagedCall::StagedCall;
+
+    int ready() { return check_ready(ctx, false); }
+    // the device and the context's stream, ordered after whatever ran last on a caller's
+    int begin()
+    {
+        if (const int r = use_device(ctx)) return r;
+        s = ctx->stream;
+        return enter_stream(ctx, s);
+    }
+    // room for the maximum of every light curve and the first index attaining it, when either is wanted
+    void reserve_peaks(bool want)
+    {
+        const size_t bytes = want ? (size_t)ctx->L * 8 : 0;
+        reserve({{peak, bytes}, {index, bytes}});
+    }
+    void gather_peaks(double *peak_power, int64_t *peak_index)
+    {
+        if (peak_power) gather(peak_power, peak.p, (size_t)ctx->L * 8);
+        if (peak_index) gather(peak_index, index.p, (size_t)ctx->L * 8);
+    }
+    // The arguments of the pre-pass (mtg_launch_lomb_scargle_stats) and of the sweeps that read its statistics: the resident
+    // set, the call's choices, the F uploaded frequencies (none: 0, NULL), where the powers go and, with want_peak, the peaks.
+    MtgLombScargleArgs args(int nterms, int normalization, int weighted, int64_t F, const double *d_freqs, double *d_power, bool want_peak)
+    {
+        reserve({{stats, (size_t)ctx->L * 32}});
+        reserve_peaks(want_peak);
+        MtgLombScargleArgs qa;
+        qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
+        qa.N = ctx->N; qa.t_stride = ctx->t_per_lc ? ctx->N : 0; qa.L = ctx->L;
+        qa.weighted = weighted ? 1 : 0; qa.normalization = normalization; qa.nterms = nterms;
+        qa.stats = stats.as<double>(); qa.F = F; qa.freqs = d_freqs; qa.power = d_power;
+        qa.peak_power = want_peak ? peak.as<double>() : nullptr; qa.peak_index = want_peak ? index.as<int64_t>() : nullptr;
+        return qa;
+    }
+    // The call's timed work (mtg_last_kernel_ms): the pre-pass, then for the slabs [i0, i0 + n) of `extent`, `slab` at a time,
+    // launch(i0, n) -> hipError_t and collect(i0, n), the slab's copies to the host (none: every output is whole on the
+    // device).  One stream: the next slab's kernels overwrite the workspace only after this slab's kernels and copies.
+    // After the first failure nothing more is queued.
+    template <class Prepass, class Launch, class Collect = void (*)(int64_t, int64_t)>
+    void run_slabs(int64_t extent, int64_t slab, Prepass prepass, Launch launch, Collect collect = [](int64_t, int64_t) {})
+    {
+        then([&] { return hipEventRecord(ctx->ev0, s); });
+        then([&] { return prepass(), hipGetLastError(); });
+        if (ok()) e = for_each_slab(extent, slab, [&](int64_t i0, int64_t n) {
+            then([&] { return launch(i0, n); });
+            if (i0 + n == extent) then([&] { return hipEventRecord(ctx->ev1, s); });   // up to the last slab's kernels
+            collect(i0, n);
+            return e;
+        });
+        if (ok()) ctx->timed = true;
+    }
+};
+
+// the refusals the resident-set entries share, each written once; an entry calls them in the order of its own messages
+int refuse_no_freqs(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs)
 {
-    mtg_ctx *ctx = c.ctx;
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        stats();
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(L, slab, [&](int64_t l0, int64_t rows) {
-        // (the next slab's sweep overwrites the workspace only after this slab's reduction: one stream)
-        c.then([&] { return launch(l0, rows); });
-        return c.e;
-    });
-    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
-    if (c.ok()) ctx->timed = true;
+    return F < 1 || !freqs ? fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who) : MTG_OK;
+}
+int refuse_normalization(mtg_ctx *ctx, const char *who, int normalization)
+{
+    return normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD ? fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization) : MTG_OK;
+}
+int refuse_bad_freqs(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs)
+{
+    for (int64_t k = 0; k < F; ++k)
+        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
+            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    return MTG_OK;
 }
 
 }  // namespace
@@ -2581,28 +2656,11 @@ static int ls_refuse_terms(mtg_ctx *ctx, const char *who, int nterms, int64_t N)
 // nothing), in the order of their messages; nothing_asked: mtg_lomb_scargle's three outputs are all NULL
 static int ls_refuse_call(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization, bool nothing_asked)
 {
-    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
-    if (nothing_asked) return fail(ctx, MTG_E_ARG, "%s: power, peak_power and peak_index are all NULL", who);
-    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
-        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
-    const int rc = ls_refuse_terms(ctx, who, nterms, ctx->N);
+    int rc = refuse_no_freqs(ctx, who, F, freqs);
     if (rc) return rc;
-    for (int64_t k = 0; k < F; ++k)
-        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
-            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
-    return MTG_OK;
-}
-
-// the resident set and the call's choices; the frequencies and the peaks (none) are the caller's to set
-static MtgLombScargleArgs ls_resident_args(const mtg_ctx *ctx, int nterms, int normalization, int weighted, double *stats, double *power)
-{
-    MtgLombScargleArgs qa;
-    qa.dxt = ctx->dxt.as<double2>(); qa.yv = ctx->yv.as<double2>();
-    qa.N = ctx->N; qa.t_stride = ctx->t_per_lc ? ctx->N : 0; qa.L = ctx->L;
-    qa.weighted = weighted ? 1 : 0; qa.normalization = normalization; qa.nterms = nterms;
-    qa.stats = stats; qa.F = 0; qa.freqs = nullptr; qa.power = power;
-    qa.peak_power = nullptr; qa.peak_index = nullptr;
-    return qa;
+    if (nothing_asked) return fail(ctx, MTG_E_ARG, "%s: power, peak_power and peak_index are all NULL", who);
+    if ((rc = refuse_normalization(ctx, who, normalization)) || (rc = ls_refuse_terms(ctx, who, nterms, ctx->N))) return rc;
+    return refuse_bad_freqs(ctx, who, F, freqs);
 }
 
 // the kernel that computes the powers, as mtg_last_solver names it
@@ -2616,43 +2674,24 @@ static void ls_kernel_name(char *out, size_t n, int nterms, int R)
 static int lomb_scargle_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization, int weighted,
                               double *power, double *peak_power, int64_t *peak_index)
 {
-    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
-    int rc = c.ready(false);
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
     if (rc) return rc;
     if ((rc = ls_refuse_call(ctx, who, F, freqs, nterms, normalization, !power && !peak_power && !peak_index))) return rc;
-    if ((rc = c.begin(false))) return rc;
+    if ((rc = c.begin())) return rc;
     const int64_t L = ctx->L;
-    // the powers of a slab of light curves at a time: <= 256 MiB of workspace whatever L F is
-    int64_t Ls = ((int64_t)1 << 25) / F;
     const int R = mtg_ls_tile(nterms, L, !ctx->t_per_lc, weighted);
-    Ls = Ls / R * R;   // whole tiles (a light curve's power does not depend on its tile: this only fills the lanes)
-    if (Ls < R) Ls = R;
-    if (Ls > L) Ls = L;
-    DevBuf d_freqs, d_stats, d_power, d_peak, d_index;
-    const bool want_peak = peak_power || peak_index;
-    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_power, (size_t)Ls * (size_t)F * 8},
-               {d_peak, want_peak ? (size_t)L * 8 : 0}, {d_index, want_peak ? (size_t)L * 8 : 0}});
+    const int64_t Ls = mtg_ls_slab(F, R, L);
+    DevBuf d_freqs, d_power;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_power, (size_t)Ls * (size_t)F * 8}});
+    const MtgLombScargleArgs qa = c.args(nterms, normalization, weighted, F, d_freqs.as<double>(), d_power.as<double>(), peak_power || peak_index);
     c.upload(d_freqs.p, freqs, (size_t)F * 8);
-    MtgLombScargleArgs qa = ls_resident_args(ctx, nterms, normalization, weighted, d_stats.as<double>(), d_power.as<double>());
-    qa.F = F; qa.freqs = d_freqs.as<double>();
-    qa.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
     ls_kernel_name(ctx->last_solver, sizeof ctx->last_solver, nterms, R);
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        mtg_launch_lomb_scargle_stats(qa, c.s);
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
-        c.then([&] { return mtg_launch_lomb_scargle(qa, l0, rows, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
-        if (l0 + rows == L) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });   // mtg_last_kernel_ms: up to the last slab's kernels
-        // (the copy is ordered on the stream: the next slab's kernel overwrites the buffer only after it)
-        if (power) c.gather(power + l0 * F, d_power.p, (size_t)rows * (size_t)F * 8);
-        return c.e;
-    });
-    if (c.ok()) ctx->timed = true;
-    if (peak_power) c.gather(peak_power, d_peak.p, (size_t)L * 8);
-    if (peak_index) c.gather(peak_index, d_index.p, (size_t)L * 8);
-    return c.finish(nullptr);
+    c.run_slabs(L, Ls, [&] { mtg_launch_lomb_scargle_stats(qa, c.s); },
+                [&](int64_t l0, int64_t rows) { return mtg_launch_lomb_scargle(qa, l0, rows, c.s) ? hipGetLastError() : hipErrorInvalidValue; },
+                [&](int64_t l0, int64_t rows) { if (power) c.gather(power + l0 * F, d_power.p, (size_t)rows * (size_t)F * 8); });
+    c.gather_peaks(peak_power, peak_index);
+    return c.finish();
 }
 
 MTG_API int mtg_lomb_scargle(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, double *power,
@@ -2671,122 +2710,85 @@ MTG_API int mtg_lomb_scargle_multi(mtg_ctx *ctx, int64_t F, const double *freqs,
 static int ef_refuse_call(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nbins, double time_0, int normalization,
                           bool nothing_asked)
 {
-    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
+    int rc = refuse_no_freqs(ctx, who, F, freqs);
+    if (rc) return rc;
     if (nothing_asked) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
     if (nbins < 2 || nbins > MTG_EF_MAX_BINS) return fail(ctx, MTG_E_ARG, "%s: nbins = %d is outside 2 .. %d", who, nbins, MTG_EF_MAX_BINS);
     if (!std::isfinite(time_0)) return fail(ctx, MTG_E_ARG, "%s: time_0 = %g is not finite", who, time_0);
-    if (normalization < MTG_LS_STANDARD || normalization > MTG_LS_PSD)
-        return fail(ctx, MTG_E_ARG, "%s: unknown normalization %d", who, normalization);
+    if ((rc = refuse_normalization(ctx, who, normalization))) return rc;
     if (ctx->N < 2) return fail(ctx, MTG_E_ARG, "%s: N = %lld < 2 samples", who, (long long)ctx->N);
-    for (int64_t k = 0; k < F; ++k)
-        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
-            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
-    return MTG_OK;
+    return refuse_bad_freqs(ctx, who, F, freqs);
 }
 
 MTG_API int mtg_epoch_fold(mtg_ctx *ctx, int64_t F, const double *freqs, int nbins, double time_0, int normalization, int weighted,
                            double *power, double *peak_power, int64_t *peak_index)
 {
     const char *who = "mtg_epoch_fold";
-    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
-    int rc = c.ready(false);
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
     if (rc) return rc;
     if ((rc = ef_refuse_call(ctx, who, F, freqs, nbins, time_0, normalization, !power && !peak_power && !peak_index))) return rc;
-    if ((rc = c.begin(false))) return rc;
+    if ((rc = c.begin())) return rc;
     const int64_t L = ctx->L;
     const MtgEfPlan plan = mtg_ef_plan(nbins, F, L, !ctx->t_per_lc, weighted ? 1 : 0);
-    // the powers of a slab of light curves at a time, as mtg_lomb_scargle: <= 256 MiB of workspace whatever L F is
-    int64_t Ls = ((int64_t)1 << 25) / F;
-    Ls = Ls / plan.tile * plan.tile;
-    if (Ls < plan.tile) Ls = plan.tile;
-    if (Ls > L) Ls = L;
-    DevBuf d_freqs, d_stats, d_power, d_peak, d_index;
-    const bool want_peak = peak_power || peak_index;
-    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_power, (size_t)Ls * (size_t)F * 8},
-               {d_peak, want_peak ? (size_t)L * 8 : 0}, {d_index, want_peak ? (size_t)L * 8 : 0}});
-    c.upload(d_freqs.p, freqs, (size_t)F * 8);
+    const int64_t Ls = mtg_ls_slab(F, plan.tile, L);
+    DevBuf d_freqs, d_power;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_power, (size_t)Ls * (size_t)F * 8}});
     MtgEpochFoldArgs qa;
-    qa.ls = ls_resident_args(ctx, 1, normalization, weighted, d_stats.as<double>(), d_power.as<double>());
-    qa.ls.F = F; qa.ls.freqs = d_freqs.as<double>();
-    qa.ls.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.ls.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
+    qa.ls = c.args(1, normalization, weighted, F, d_freqs.as<double>(), d_power.as<double>(), peak_power || peak_index);
+    c.upload(d_freqs.p, freqs, (size_t)F * 8);
     qa.nbins = nbins; qa.time_0 = time_0;
     qa.wsum = qa.wrsum = qa.varsum = nullptr; qa.count = nullptr;
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_epoch_fold_kernel<%d,%d> lanes %d", plan.tile, weighted ? 1 : 0, plan.lanes);
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
-        c.then([&] { return mtg_launch_epoch_fold(qa, plan, l0, rows, c.s); });
-        if (l0 + rows == L) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });   // mtg_last_kernel_ms: up to the last slab's kernels
-        // (the copy is ordered on the stream: the next slab's kernel overwrites the buffer only after it)
-        if (power) c.gather(power + l0 * F, d_power.p, (size_t)rows * (size_t)F * 8);
-        return c.e;
-    });
-    if (c.ok()) ctx->timed = true;
-    if (peak_power) c.gather(peak_power, d_peak.p, (size_t)L * 8);
-    if (peak_index) c.gather(peak_index, d_index.p, (size_t)L * 8);
-    return c.finish(nullptr);
+    c.run_slabs(L, Ls, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); },
+                [&](int64_t l0, int64_t rows) { return mtg_launch_epoch_fold(qa, plan, l0, rows, c.s); },
+                [&](int64_t l0, int64_t rows) { if (power) c.gather(power + l0 * F, d_power.p, (size_t)rows * (size_t)F * 8); });
+    c.gather_peaks(peak_power, peak_index);
+    return c.finish();
 }
 
 MTG_API int mtg_phase_fold(mtg_ctx *ctx, int64_t F, const double *freqs, int nbins, double time_0, int weighted, int64_t *count,
                            double *wsum, double *wrsum, double *varsum)
 {
     const char *who = "mtg_phase_fold";
-    RowCall c{ctx, who, 0, nullptr, nullptr, 0};
-    int rc = c.ready(false);
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
     if (rc) return rc;
-    if ((rc = ef_refuse_call(ctx, who, F, freqs, nbins, time_0, MTG_LS_STANDARD, !count && !wsum && !wrsum && !varsum))) return rc;
+    OptionalOutputs<4> out;
+    out.host[0] = count; out.host[1] = wsum; out.host[2] = wrsum; out.host[3] = varsum;
+    if ((rc = ef_refuse_call(ctx, who, F, freqs, nbins, time_0, MTG_LS_STANDARD, out.what() == 0))) return rc;
     const int64_t L = ctx->L;
     // every asked-for output whole on the device: at most MTG_PF_MAX_ENTRIES entries each
     if (F > MTG_PF_MAX_ENTRIES / nbins || L > MTG_PF_MAX_ENTRIES / (F * nbins))
         return fail(ctx, MTG_E_ARG, "%s: L F nbins = %lld x %lld x %d exceeds %lld entries per output (fold fewer frequencies per call)", who,
                     (long long)L, (long long)F, nbins, (long long)MTG_PF_MAX_ENTRIES);
-    if ((rc = c.begin(false))) return rc;
+    if ((rc = c.begin())) return rc;
     const MtgEfPlan plan = mtg_ef_plan(nbins, F, L, !ctx->t_per_lc, weighted ? 1 : 0);
-    const size_t bytes = (size_t)L * (size_t)F * (size_t)nbins * 8;
-    const int64_t Ls = L < 32768 ? L : 32768;   // (a multiple of every tile; the counts' grid has a row per light curve)
-    DevBuf d_freqs, d_stats, d_count, d_wsum, d_wrsum, d_varsum;
-    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_count, count ? bytes : 0}, {d_wsum, wsum ? bytes : 0},
-               {d_wrsum, wrsum ? bytes : 0}, {d_varsum, varsum ? bytes : 0}});
-    c.upload(d_freqs.p, freqs, (size_t)F * 8);
+    DevBuf d_freqs;
+    c.reserve({{d_freqs, (size_t)F * 8}});
+    out.reserve(c, (size_t)L * (size_t)F * (size_t)nbins);
     MtgEpochFoldArgs qa;
-    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, weighted, d_stats.as<double>(), nullptr);
-    qa.ls.F = F; qa.ls.freqs = d_freqs.as<double>();
+    qa.ls = c.args(1, MTG_LS_STANDARD, weighted, F, d_freqs.as<double>(), nullptr, false);
+    c.upload(d_freqs.p, freqs, (size_t)F * 8);
     qa.nbins = nbins; qa.time_0 = time_0;
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_epoch_fold_kernel<%d,%d> lanes %d", plan.tile, weighted ? 1 : 0, plan.lanes);
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
+    c.run_slabs(L, MTG_PF_SLAB, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); }, [&](int64_t l0, int64_t rows) {
         const int64_t at = l0 * F * nbins;
-        qa.count = count ? d_count.as<int64_t>() + at : nullptr;
-        qa.wsum = wsum ? d_wsum.as<double>() + at : nullptr;
-        qa.wrsum = wrsum ? d_wrsum.as<double>() + at : nullptr;
-        qa.varsum = varsum ? d_varsum.as<double>() + at : nullptr;
-        c.then([&] { return mtg_launch_epoch_fold(qa, plan, l0, rows, c.s); });
-        return c.e;
+        qa.count = out.at<int64_t>(0, at); qa.wsum = out.at(1, at); qa.wrsum = out.at(2, at); qa.varsum = out.at(3, at);
+        return mtg_launch_epoch_fold(qa, plan, l0, rows, c.s);
     });
-    c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
-    if (c.ok()) ctx->timed = true;
-    if (count) c.gather(count, d_count.p, bytes);
-    if (wsum) c.gather(wsum, d_wsum.p, bytes);
-    if (wrsum) c.gather(wrsum, d_wrsum.p, bytes);
-    if (varsum) c.gather(varsum, d_varsum.p, bytes);
-    return c.finish(nullptr);
+    out.gather(c);
+    return c.finish();
 }
 
 MTG_API int mtg_wwz(mtg_ctx *ctx, int64_t F, const double *freqs, int64_t T, const double *taus, double decay, int statistic, int weighted,
                     double *out, double *neff, double *peak, int64_t *peak_index)
 {
     const char *who = "mtg_wwz";
-    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
-    int rc = c.ready(false);
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
     if (rc) return rc;
-    if (F < 1 || !freqs) return fail(ctx, MTG_E_ARG, "%s: need F >= 1 frequencies", who);
+    if ((rc = refuse_no_freqs(ctx, who, F, freqs))) return rc;
     if (T < 1 || !taus) return fail(ctx, MTG_E_ARG, "%s: need T >= 1 window centres", who);
     if (!out && !neff && !peak && !peak_index) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
     if (!std::isfinite(decay) || decay < 0.0) return fail(ctx, MTG_E_ARG, "%s: decay = %g is not a finite constant >= 0", who, decay);
@@ -2796,86 +2798,72 @@ MTG_API int mtg_wwz(mtg_ctx *ctx, int64_t F, const double *freqs, int64_t T, con
     const int64_t L = ctx->L;
     if (T > INT64_MAX / 8 / F || L > INT64_MAX / 8 / (T * F))
         return fail(ctx, MTG_E_ARG, "%s: L T F = %lld x %lld x %lld is beyond int64", who, (long long)L, (long long)T, (long long)F);
-    for (int64_t k = 0; k < F; ++k)
-        if (!std::isfinite(freqs[k]) || freqs[k] <= 0.0)
-            return fail(ctx, MTG_E_ARG, "%s: freqs[%lld] = %g is not a finite positive frequency", who, (long long)k, freqs[k]);
+    if ((rc = refuse_bad_freqs(ctx, who, F, freqs))) return rc;
     for (int64_t j = 0; j < T; ++j)
         if (!std::isfinite(taus[j])) return fail(ctx, MTG_E_ARG, "%s: taus[%lld] is not finite", who, (long long)j);
-    if ((rc = c.begin(false))) return rc;
+    if ((rc = c.begin())) return rc;
     const MtgWwzPlan plan = mtg_wwz_plan(F, T, L, !ctx->t_per_lc, weighted ? 1 : 0);
     const int64_t Ls = plan.slab;
     const size_t map_bytes = (size_t)T * (size_t)F * 8;
     const bool want_peak = peak || peak_index, want_values = out || want_peak;
-    DevBuf d_freqs, d_taus, d_stats, d_near, d_out, d_neff, d_peak, d_index;
-    c.reserve({{d_freqs, (size_t)F * 8}, {d_taus, (size_t)T * 8}, {d_stats, (size_t)L * 32},
-               {d_near, (size_t)(ctx->t_per_lc ? Ls : 1) * (size_t)T * 8}, {d_out, want_values ? (size_t)Ls * map_bytes : 0},
-               {d_neff, neff ? (size_t)Ls * map_bytes : 0}, {d_peak, want_peak ? (size_t)L * 8 : 0}, {d_index, want_peak ? (size_t)L * 8 : 0}});
+    DevBuf d_freqs, d_taus, d_near, d_out, d_neff;
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_taus, (size_t)T * 8}, {d_near, (size_t)(ctx->t_per_lc ? Ls : 1) * (size_t)T * 8},
+               {d_out, want_values ? (size_t)Ls * map_bytes : 0}, {d_neff, neff ? (size_t)Ls * map_bytes : 0}});
+    MtgWwzArgs qa;
+    qa.ls = c.args(1, MTG_LS_STANDARD, weighted, F, d_freqs.as<double>(), d_out.as<double>(), want_peak);
     c.upload(d_freqs.p, freqs, (size_t)F * 8);
     c.upload(d_taus.p, taus, (size_t)T * 8);
-    MtgWwzArgs qa;
-    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, weighted, d_stats.as<double>(), want_values ? d_out.as<double>() : nullptr);
-    qa.ls.F = F; qa.ls.freqs = d_freqs.as<double>();
-    qa.ls.peak_power = want_peak ? d_peak.as<double>() : nullptr; qa.ls.peak_index = want_peak ? d_index.as<int64_t>() : nullptr;
     qa.T = T; qa.taus = d_taus.as<double>(); qa.kc = 39.478417604357434 * decay;   // 4 pi^2
-    qa.statistic = statistic; qa.neff = neff ? d_neff.as<double>() : nullptr; qa.nearest = d_near.as<double>();
+    qa.statistic = statistic; qa.neff = d_neff.as<double>(); qa.nearest = d_near.as<double>();
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_wwz_kernel<%d,%d> lanes %d", plan.tile, weighted ? 1 : 0, plan.lanes);
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        mtg_launch_lomb_scargle_stats(qa.ls, c.s);
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(L, Ls, [&](int64_t l0, int64_t rows) {
-        c.then([&] { return mtg_launch_wwz(qa, plan, l0, rows, c.s); });
-        if (l0 + rows == L) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });   // mtg_last_kernel_ms: up to the last slab's kernels
-        // (the copies are ordered on the stream: the next slab's kernels overwrite the buffers only after them)
-        if (out) c.gather(out + l0 * T * F, d_out.p, (size_t)rows * map_bytes);
-        if (neff) c.gather(neff + l0 * T * F, d_neff.p, (size_t)rows * map_bytes);
-        return c.e;
-    });
-    if (c.ok()) ctx->timed = true;
-    if (peak) c.gather(peak, d_peak.p, (size_t)L * 8);
-    if (peak_index) c.gather(peak_index, d_index.p, (size_t)L * 8);
-    return c.finish(nullptr);
+    c.run_slabs(L, Ls, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); },
+                [&](int64_t l0, int64_t rows) { return mtg_launch_wwz(qa, plan, l0, rows, c.s); },
+                [&](int64_t l0, int64_t rows) {
+                    if (out) c.gather(out + l0 * T * F, d_out.p, (size_t)rows * map_bytes);
+                    if (neff) c.gather(neff + l0 * T * F, d_neff.p, (size_t)rows * map_bytes);
+                });
+    c.gather_peaks(peak, peak_index);
+    return c.finish();
 }
 
 MTG_API int mtg_lag_sums(mtg_ctx *ctx, int nbins, const double *edges, int64_t *count, double *lag, double *sf, double *cf, double *cf2,
                          double *noise)
 {
     const char *who = "mtg_lag_sums";
-    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
-    int rc = c.ready(false);
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
     if (rc) return rc;
-    LagOutputs<6> out;
+    OptionalOutputs<6> out;
     out.host[0] = count; out.host[1] = lag; out.host[2] = sf; out.host[3] = cf; out.host[4] = cf2; out.host[5] = noise;
     if ((rc = lag_refuse_edges(ctx, who, nbins, edges, out.what() == 0, false))) return rc;
     if (ctx->N < 2) return fail(ctx, MTG_E_ARG, "%s: N = %lld < 2 samples (no pairs)", who, (long long)ctx->N);
-    if ((rc = c.begin(false))) return rc;
+    if ((rc = c.begin())) return rc;
     const int64_t L = ctx->L;
     const MtgLagPlan plan = mtg_lag_plan(ctx->N, nbins, L, !ctx->t_per_lc, out.what());
-    DevBuf d_edges, d_stats, d_ws;
-    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_stats, (size_t)L * 32}, {d_ws, (size_t)plan.ws_bytes}});
-    out.reserve(c, L, nbins);
-    c.upload(d_edges.p, edges, (size_t)(nbins + 1) * 8);
+    DevBuf d_edges, d_ws;
+    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_ws, (size_t)plan.ws_bytes}});
+    out.reserve(c, (size_t)L * (size_t)nbins);
     MtgLagArgs qa;
-    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, 0, d_stats.as<double>(), nullptr);
+    qa.ls = c.args(1, MTG_LS_STANDARD, 0, 0, nullptr, nullptr, false);
+    c.upload(d_edges.p, edges, (size_t)(nbins + 1) * 8);
     qa.nbins = nbins; qa.edges = d_edges.as<double>(); qa.ws = d_ws.as<double>();
     qa.count = out.at<int64_t>(0); qa.lag = out.at(1); qa.sf = out.at(2); qa.cf = out.at(3); qa.cf2 = out.at(4); qa.noise = out.at(5);
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_lag_kernel<%d,%d> lanes %d", plan.tile, plan.all, (int)MTG_LAG_LANES);
-    lag_run_slabs(c, L, plan.slab, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); },
-                  [&](int64_t l0, int64_t rows) { return mtg_launch_lag(qa, plan, l0, rows, c.s); });
+    c.run_slabs(L, plan.slab, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); },
+                [&](int64_t l0, int64_t rows) { return mtg_launch_lag(qa, plan, l0, rows, c.s); });
     out.gather(c);
-    return c.finish(nullptr);
+    return c.finish();
 }
 
 MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2, const double *y2, int nbins, const double *edges,
                            int64_t *count, double *lag, double *cf, double *cf2, double *sa, double *sb, double *saa, double *sbb)
 {
     const char *who = "mtg_cross_sums";
-    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
-    int rc = c.ready(false);
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
     if (rc) return rc;
     const int64_t L = ctx->L;
-    LagOutputs<8> out;
+    OptionalOutputs<8> out;
     out.host[0] = count; out.host[1] = lag; out.host[2] = cf; out.host[3] = cf2;
     out.host[4] = sa; out.host[5] = sb; out.host[6] = saa; out.host[7] = sbb;
     if (M < 1 || M >= MTG_CROSS_MAX_M) return fail(ctx, MTG_E_ARG, "%s: M = %lld is outside 1 .. 2^28 - 1", who, (long long)M);
@@ -2890,22 +2878,22 @@ MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2
     }
     for (int64_t k = 0; k < L2 * M; ++k)
         if (!std::isfinite(y2[k])) return fail(ctx, MTG_E_ARG, "%s: y2[%lld][%lld] is not finite", who, (long long)(k / M), (long long)(k % M));
-    if ((rc = c.begin(false))) return rc;
+    if ((rc = c.begin())) return rc;
     // (a set of one light curve has L2 == 1 == L: the shared-companion kernel, the same arithmetic)
     const MtgCrossPlan plan = mtg_cross_plan(ctx->N, M, nbins, L, !ctx->t_per_lc, L2 == L && L > 1, out.what());
     const size_t rows2 = (size_t)L2 * (size_t)M;
     // the companion as the pre-pass reads a light curve: (value, variance) pairs; the variance is not read unweighted
     std::vector<double2> pairs(rows2);
     for (size_t k = 0; k < rows2; ++k) pairs[k] = make_double2(y2[k], 1.0);
-    DevBuf d_edges, d_stats, d_t2, d_yv2, d_stats2, d_ws;
-    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_stats, (size_t)L * 32}, {d_t2, (size_t)M * 8}, {d_yv2, rows2 * 16},
-               {d_stats2, (size_t)L2 * 32}, {d_ws, (size_t)plan.ws_bytes}});
-    out.reserve(c, L, nbins);
+    DevBuf d_edges, d_t2, d_yv2, d_stats2, d_ws;
+    c.reserve({{d_edges, (size_t)(nbins + 1) * 8}, {d_t2, (size_t)M * 8}, {d_yv2, rows2 * 16}, {d_stats2, (size_t)L2 * 32},
+               {d_ws, (size_t)plan.ws_bytes}});
+    out.reserve(c, (size_t)L * (size_t)nbins);
+    MtgCrossArgs qa;
+    qa.ls = c.args(1, MTG_LS_STANDARD, 0, 0, nullptr, nullptr, false);
     c.upload(d_edges.p, edges, (size_t)(nbins + 1) * 8);
     c.upload(d_t2.p, t2, (size_t)M * 8);
     c.upload(d_yv2.p, pairs.data(), rows2 * 16);
-    MtgCrossArgs qa;
-    qa.ls = ls_resident_args(ctx, 1, MTG_LS_STANDARD, 0, d_stats.as<double>(), nullptr);
     MtgLombScargleArgs companion = qa.ls;      // the same pre-pass on the companion's rows as light curves of M samples
     companion.dxt = nullptr; companion.yv = d_yv2.as<double2>(); companion.N = M; companion.t_stride = 0; companion.L = L2;
     companion.stats = d_stats2.as<double>();
@@ -2915,10 +2903,10 @@ MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2
     qa.sa = out.at(4); qa.sb = out.at(5); qa.saa = out.at(6); qa.sbb = out.at(7);
     snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_cross_kernel<%d,%d,%d> lanes %d", plan.tile, plan.per, plan.all,
              (int)MTG_CROSS_LANES);
-    lag_run_slabs(c, L, plan.slab, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); mtg_launch_lomb_scargle_stats(companion, c.s); },
-                  [&](int64_t l0, int64_t rows) { return mtg_launch_cross(qa, plan, l0, rows, c.s); });
+    c.run_slabs(L, plan.slab, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); mtg_launch_lomb_scargle_stats(companion, c.s); },
+                [&](int64_t l0, int64_t rows) { return mtg_launch_cross(qa, plan, l0, rows, c.s); });
     out.gather(c);
-    return c.finish(nullptr);   // (waits for the stream: `pairs` outlives its upload)
+    return c.finish();   // (waits for the stream: `pairs` outlives its upload)
 }
 
 // mtg_lomb_scargle_envelope (nterms = 1) and mtg_lomb_scargle_envelope_multi
@@ -2927,8 +2915,8 @@ static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F,
                                        const double *reference, int64_t *exceed, const double *scale, double *peak_ratio,
                                        int64_t *peak_ratio_index)
 {
-    RowCall c{ctx, who, 0, nullptr, nullptr, 0};   // (no rows of theta: the call's stream and its one way out)
-    int rc = c.ready(false);
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
     if (rc) return rc;
     if ((rc = ls_refuse_call(ctx, who, F, freqs, nterms, normalization, false))) return rc;
     const int64_t L = ctx->L;
@@ -2948,58 +2936,51 @@ static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F,
     for (int64_t k = 0; scale && k < F; ++k)
         if (!std::isfinite(scale[k]) || !(scale[k] > 0.0))
             return fail(ctx, MTG_E_ARG, "%s: scale[%lld] = %g is not finite and positive", who, (long long)k, scale[k]);
-    if ((rc = c.begin(false))) return rc;
+    if ((rc = c.begin())) return rc;
     // a slab of frequencies at a time, every light curve's power at them: mtg_ls_envelope_plan.h
     const int64_t Fs = mtg_lse_slab_width(L, F, Q, MTG_LSE_BUDGET);
     const bool in_lds = mtg_lse_in_lds(L) != 0;
     const size_t slab_bytes = (size_t)L * (size_t)Fs * 8, temp_bytes = want_columns ? mtg_ls_envelope_temp_bytes(L, Fs) : 0;
     MtgLsEnvelopeArgs ea;
-    DevBuf d_freqs, d_stats, d_power, d_ranks, d_os, d_valid, d_ref, d_exceed, d_scale, d_peak, d_index, d_ka, d_kb, d_temp;
+    DevBuf d_freqs, d_power, d_ranks, d_os, d_valid, d_ref, d_exceed, d_scale, d_ka, d_kb, d_temp;
     const bool sort_global = want_columns && !in_lds;
-    c.reserve({{d_freqs, (size_t)F * 8}, {d_stats, (size_t)L * 32}, {d_power, slab_bytes}, {d_ranks, (size_t)Q * 8},
+    c.reserve({{d_freqs, (size_t)F * 8}, {d_power, slab_bytes}, {d_ranks, (size_t)Q * 8},
                {d_os, (size_t)Q * (size_t)Fs * 8}, {d_valid, valid ? (size_t)F * 8 : 0}, {d_ref, reference ? (size_t)F * 8 : 0},
                {d_exceed, exceed ? (size_t)F * 8 : 0}, {d_scale, want_ratio ? (size_t)F * 8 : 0},
-               {d_peak, want_ratio ? (size_t)L * 8 : 0}, {d_index, want_ratio ? (size_t)L * 8 : 0},
                {d_ka, sort_global ? slab_bytes : 0}, {d_kb, sort_global ? slab_bytes : 0}, {d_temp, sort_global ? temp_bytes + 256 : 0}});
+    MtgLombScargleArgs qa = c.args(nterms, normalization, weighted, 0, nullptr, d_power.as<double>(), false);   // (no peaks of the powers)
+    c.reserve_peaks(want_ratio);      // the peaks of the ratios instead
     c.upload(d_freqs.p, freqs, (size_t)F * 8);
     if (Q > 0) c.upload(d_ranks.p, ranks, (size_t)Q * 8);
     if (reference) c.upload(d_ref.p, reference, (size_t)F * 8);
     if (want_ratio) c.upload(d_scale.p, scale, (size_t)F * 8);
-    // (the frequencies are each slab's; no peaks)
-    MtgLombScargleArgs qa = ls_resident_args(ctx, nterms, normalization, weighted, d_stats.as<double>(), d_power.as<double>());
     ea.slab = d_power.as<double>(); ea.L = L; ea.Q = Q; ea.ranks = d_ranks.as<int64_t>(); ea.order_stat = d_os.as<double>();
     ea.valid = valid ? d_valid.as<int64_t>() : nullptr; ea.reference = reference ? d_ref.as<double>() : nullptr;
     ea.exceed = exceed ? d_exceed.as<int64_t>() : nullptr; ea.scale = d_scale.as<double>();
-    ea.peak_ratio = d_peak.as<double>(); ea.peak_ratio_index = d_index.as<int64_t>();
+    ea.peak_ratio = c.peak.as<double>(); ea.peak_ratio_index = c.index.as<int64_t>();
     ea.keys_a = d_ka.p; ea.keys_b = d_kb.p; ea.temp = d_temp.p; ea.temp_bytes = temp_bytes + 256;
     if (!want_columns) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_ls_envelope_ratio_peak_kernel");
     else if (in_lds) snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_ls_envelope_column_kernel<%d>", mtg_lse_columns(L));
     else snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_ls_envelope_select_kernel");
-    c.then([&] { return hipEventRecord(ctx->ev0, c.s); });
-    c.then([&] {
-        mtg_launch_lomb_scargle_stats(qa, c.s);
-        return hipGetLastError();
-    });
-    if (c.ok()) c.e = for_each_slab(F, Fs, [&](int64_t k0, int64_t cols) {
-        qa.F = cols; qa.freqs = d_freqs.as<double>() + k0;
-        ea.Fs = cols; ea.k0 = k0;
-        c.then([&] { return mtg_launch_lomb_scargle(qa, 0, L, c.s) ? hipGetLastError() : hipErrorInvalidValue; });
-        if (want_columns) c.then([&] { return mtg_launch_ls_envelope_columns(ea, c.s); });
-        if (want_ratio) c.then([&] { return mtg_launch_ls_envelope_ratio_peaks(ea, c.s); });
-        if (k0 + cols == F) c.then([&] { return hipEventRecord(ctx->ev1, c.s); });
-        // (the copy is ordered on the stream: the next slab's kernels overwrite the buffer only after it)
-        if (Q > 0) c.then([&] {
-            return hipMemcpy2DAsync(order_stat + k0, (size_t)F * 8, d_os.p, (size_t)cols * 8, (size_t)cols * 8, (size_t)Q,
-                                    hipMemcpyDeviceToHost, c.s);
-        });
-        return c.e;
-    });
-    if (c.ok()) ctx->timed = true;
+    c.run_slabs(F, Fs, [&] { mtg_launch_lomb_scargle_stats(qa, c.s); },
+                [&](int64_t k0, int64_t cols) {
+                    qa.F = cols; qa.freqs = d_freqs.as<double>() + k0;   // the frequencies are each slab's
+                    ea.Fs = cols; ea.k0 = k0;
+                    hipError_t e = mtg_launch_lomb_scargle(qa, 0, L, c.s) ? hipGetLastError() : hipErrorInvalidValue;
+                    if (e == hipSuccess && want_columns) e = mtg_launch_ls_envelope_columns(ea, c.s);
+                    if (e == hipSuccess && want_ratio) e = mtg_launch_ls_envelope_ratio_peaks(ea, c.s);
+                    return e;
+                },
+                [&](int64_t k0, int64_t cols) {
+                    if (Q > 0) c.then([&] {
+                        return hipMemcpy2DAsync(order_stat + k0, (size_t)F * 8, d_os.p, (size_t)cols * 8, (size_t)cols * 8, (size_t)Q,
+                                                hipMemcpyDeviceToHost, c.s);
+                    });
+                });
     if (valid) c.gather(valid, d_valid.p, (size_t)F * 8);
     if (exceed) c.gather(exceed, d_exceed.p, (size_t)F * 8);
-    if (peak_ratio) c.gather(peak_ratio, d_peak.p, (size_t)L * 8);
-    if (peak_ratio_index) c.gather(peak_ratio_index, d_index.p, (size_t)L * 8);
-    return c.finish(nullptr);
+    c.gather_peaks(peak_ratio, peak_ratio_index);
+    return c.finish();
 }
 
 MTG_API int mtg_lomb_scargle_envelope(mtg_ctx *ctx, int64_t F, const double *freqs, int normalization, int weighted, int Q,

@@ -24,6 +24,9 @@
 #include <stdint.h>
 
 enum { MTG_EF_LDS_BUDGET = 80 * 1024, MTG_EF_CHUNK = 256 };
+// light curves per launch of mtg_phase_fold, whose outputs (at most MTG_PF_MAX_ENTRIES entries each, include/mtg.h) stay
+// whole on the device: a multiple of every tile; the counts' grid has a row per light curve
+enum { MTG_PF_SLAB = 32768 };
 
 struct MtgEfPlan {
     int tile;        // light curves per lane: 1, 2 or 4

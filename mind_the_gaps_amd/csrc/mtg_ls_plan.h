@@ -43,4 +43,16 @@ static inline int mtg_ls_tile(int nterms, int64_t L, int shared_sampling, int we
     return full;
 }
 
+// The powers of a slab of light curves at a time (mtg_lomb_scargle, mtg_epoch_fold): at most MTG_LS_SLAB_ENTRIES of them,
+// 256 MiB of workspace whatever L F is.  -> light curves per slab: whole tiles (a light curve's power does not depend on
+// its tile: this only fills the lanes), at least one tile, at most L.
+static constexpr int64_t MTG_LS_SLAB_ENTRIES = (int64_t)1 << 25;
+
+static inline int64_t mtg_ls_slab(int64_t F, int tile, int64_t L)
+{
+    int64_t slab = MTG_LS_SLAB_ENTRIES / F / tile * tile;
+    if (slab < tile) slab = tile;
+    return slab < L ? slab : L;
+}
+
 #endif

@@ -85,6 +85,7 @@ class EngineError(RuntimeError):
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
+_lp = ctypes.POINTER(ctypes.c_int64)
 _lib = None
 
 
@@ -294,17 +295,17 @@ def load_library():
     lib.mtg_set_simulate_pdf_draws.restype = c_int
     lib.mtg_set_simulate_pdf_draws.argtypes = [c_vp, c_i64, c_i64, _dp]
     lib.mtg_simulate_pdf_report.restype = c_int
-    lib.mtg_simulate_pdf_report.argtypes = [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_int)]
+    lib.mtg_simulate_pdf_report.argtypes = [c_vp, _lp, ctypes.POINTER(c_int)]
     lib.mtg_chain_autocorr_plans_built.restype = c_i64
     lib.mtg_chain_autocorr_plans_built.argtypes = [c_vp]
     lib.mtg_set_simulate_draws.restype = c_int
-    lib.mtg_set_simulate_draws.argtypes = [c_vp, c_i64, c_i64, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_set_simulate_draws.argtypes = [c_vp, c_i64, c_i64, _dp, _lp]
     lib.mtg_pair_contexts.restype = c_int
     lib.mtg_pair_contexts.argtypes = [c_vp, c_vp]
     lib.mtg_unpair_contexts.restype = c_int
     lib.mtg_unpair_contexts.argtypes = [c_vp]
     lib.mtg_pair_stats.restype = c_int
-    lib.mtg_pair_stats.argtypes = [c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)]
+    lib.mtg_pair_stats.argtypes = [c_vp, _lp, _lp, ctypes.POINTER(c_int)]
     lib.mtg_set_sort.restype = c_int
     lib.mtg_set_sort.argtypes = [c_vp, c_int]
     lib.mtg_set_stream_base.restype = c_int
@@ -326,7 +327,7 @@ def load_library():
     lib.mtg_ensemble_restore.restype = c_int
     lib.mtg_ensemble_restore.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp]
     lib.mtg_ensemble_get.restype = c_int
-    lib.mtg_ensemble_get.argtypes = [c_vp, _dp, _dp, _dp, _dp, _ip, ctypes.POINTER(c_i64), _ip]
+    lib.mtg_ensemble_get.argtypes = [c_vp, _dp, _dp, _dp, _dp, _ip, _lp, _ip]
     lib.mtg_simulate_tk95.restype = c_int
     lib.mtg_simulate_tk95.argtypes = [c_vp, c_i64, _dp, _dp, c_i64, ctypes.c_uint64, c_i64, ctypes.c_double, ctypes.c_double,
                                       c_i64, _ip, _ip, c_int, ctypes.c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_int]
@@ -348,25 +349,23 @@ def load_library():
     lib.mtg_predict_terms.argtypes = [c_vp, c_i64, _dp, _ip, c_int, ctypes.POINTER(ctypes.c_uint32), c_i64, _dp, _dp, _dp, _ip]
     lib.mtg_gp_draw.restype = c_int
     lib.mtg_lomb_scargle.restype = c_int
-    lib.mtg_lomb_scargle.argtypes = [c_vp, c_i64, _dp, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lomb_scargle.argtypes = [c_vp, c_i64, _dp, c_int, c_int, _dp, _dp, _lp]
     lib.mtg_lomb_scargle_envelope.restype = c_int
-    lib.mtg_lomb_scargle_envelope.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, ctypes.POINTER(c_i64), _dp, ctypes.POINTER(c_i64),
-                                              _dp, ctypes.POINTER(c_i64), _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lomb_scargle_envelope.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, _lp, _dp, _lp, _dp, _lp, _dp, _dp, _lp]
     lib.mtg_lomb_scargle_multi.restype = c_int
-    lib.mtg_lomb_scargle_multi.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lomb_scargle_multi.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, _dp, _dp, _lp]
     lib.mtg_lomb_scargle_envelope_multi.restype = c_int
-    lib.mtg_lomb_scargle_envelope_multi.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, c_int, ctypes.POINTER(c_i64), _dp,
-                                                    ctypes.POINTER(c_i64), _dp, ctypes.POINTER(c_i64), _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_lomb_scargle_envelope_multi.argtypes = [c_vp, c_i64, _dp, c_int, c_int, c_int, c_int, _lp, _dp, _lp, _dp, _lp, _dp, _dp, _lp]
     lib.mtg_epoch_fold.restype = c_int
-    lib.mtg_epoch_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, c_int, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_epoch_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, c_int, _dp, _dp, _lp]
     lib.mtg_phase_fold.restype = c_int
-    lib.mtg_phase_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, ctypes.POINTER(c_i64), _dp, _dp, _dp]
+    lib.mtg_phase_fold.argtypes = [c_vp, c_i64, _dp, c_int, ctypes.c_double, c_int, _lp, _dp, _dp, _dp]
     lib.mtg_wwz.restype = c_int
-    lib.mtg_wwz.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, ctypes.c_double, c_int, c_int, _dp, _dp, _dp, ctypes.POINTER(c_i64)]
+    lib.mtg_wwz.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, ctypes.c_double, c_int, c_int, _dp, _dp, _dp, _lp]
     lib.mtg_lag_sums.restype = c_int
-    lib.mtg_lag_sums.argtypes = [c_vp, c_int, _dp, ctypes.POINTER(c_i64), _dp, _dp, _dp, _dp, _dp]
+    lib.mtg_lag_sums.argtypes = [c_vp, c_int, _dp, _lp, _dp, _dp, _dp, _dp, _dp]
     lib.mtg_cross_sums.restype = c_int
-    lib.mtg_cross_sums.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, c_int, _dp, ctypes.POINTER(c_i64), _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+    lib.mtg_cross_sums.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, c_int, _dp, _lp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_whiten.restype = c_int
     lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
@@ -396,6 +395,32 @@ def _ptr(a):
 
 def _iptr(a):
     return a.ctypes.data_as(_ip) if a is not None else None
+
+
+def _lptr(a):
+    return a.ctypes.data_as(_lp) if a is not None else None
+
+
+def _ls_normalization(normalization, extras=()):
+    """a normalisation by name -> its MTG_LS_* code; integers, and the names in ``extras`` (the caller's to resolve), pass through"""
+    if isinstance(normalization, str) and normalization not in extras:
+        if normalization not in LS_NORMALIZATIONS:
+            raise ValueError("normalization must be one of %s" % sorted(list(LS_NORMALIZATIONS) + list(extras)))
+        return LS_NORMALIZATIONS[normalization]
+    return normalization
+
+
+def _power_and_peak(L, F, power, peak):
+    """-> the outputs of lomb_scargle and epoch_fold (power [L][F], peak_power [L], peak_index [L]; None where not asked
+    for) and ``pick(out, pk, ix)``: what the two return of them"""
+    arrays = (np.full((L, F), np.nan) if power else None, np.full(L, np.nan) if peak else None, np.full(L, -1, dtype=np.int64) if peak else None)
+    return arrays, lambda out, pk, ix: (out, pk, ix) if power and peak else out if power else (pk, ix)
+
+
+def _bin_sums(names, want, shape):
+    """-> the outputs of lag_sums and cross_sums: the dict of the arrays asked for, and the entry's pointers in the order of ``names``"""
+    out = {k: (np.zeros(shape, dtype=np.int64) if k == "count" else np.full(shape, np.nan)) for k in names if want[k]}
+    return out, [_lptr(out.get(k)) if k == "count" else _ptr(out.get(k)) for k in names]
 
 
 _live_engines = None
@@ -852,23 +877,16 @@ class Engine:
         ``nterms=K`` (its ``chi2`` method; mtg_lomb_scargle_multi), for signals that are not sinusoidal; it needs
         N >= 2 K + 2 samples.  A model need not be set (mtg_lomb_scargle)."""
         freqs = _f64(np.atleast_1d(freqs)).ravel()
-        if isinstance(normalization, str):
-            if normalization not in LS_NORMALIZATIONS:
-                raise ValueError("normalization must be one of %s" % sorted(LS_NORMALIZATIONS))
-            normalization = LS_NORMALIZATIONS[normalization]
-        F, L = len(freqs), int(self.L)
-        out = np.full((L, F), np.nan) if power else None
-        pk = np.full(L, np.nan) if peak else None
-        ix = np.full(L, -1, dtype=np.int64) if peak else None
-        outputs = (_ptr(out), _ptr(pk), None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
+        normalization = _ls_normalization(normalization)
+        F = len(freqs)
+        (out, pk, ix), pick = _power_and_peak(int(self.L), F, power, peak)
+        outputs = (_ptr(out), _ptr(pk), _lptr(ix))
         if nterms == 1:
             self._check(self._lib.mtg_lomb_scargle(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), *outputs))
         else:
             self._check(self._lib.mtg_lomb_scargle_multi(self._ctx, F, _ptr(freqs), int(nterms), int(normalization),
                                                          int(bool(weighted)), *outputs))
-        if power and peak:
-            return out, pk, ix
-        return out if power else (pk, ix)
+        return pick(out, pk, ix)
 
     def _fold_epoch(self, time_0):
         """time_0 of epoch_fold and phase_fold: None = the first time of the first resident light curve"""
@@ -887,24 +905,16 @@ class Engine:
         stored numbers alone.  Return shapes as ``lomb_scargle``: ``power`` [L][F], and / or with ``peak``
         ``(peak_power[L], peak_index[L])``.  A model need not be set (mtg_epoch_fold)."""
         freqs = _f64(np.atleast_1d(freqs)).ravel()
-        chi2 = isinstance(normalization, str) and normalization == "chi2"
-        if isinstance(normalization, str):
-            if not chi2 and normalization not in LS_NORMALIZATIONS:
-                raise ValueError("normalization must be one of %s" % sorted(list(LS_NORMALIZATIONS) + ["chi2"]))
-            normalization = LS_PSD if chi2 else LS_NORMALIZATIONS[normalization]
-        F, L = len(freqs), int(self.L)
-        out = np.full((L, F), np.nan) if power else None
-        pk = np.full(L, np.nan) if peak else None
-        ix = np.full(L, -1, dtype=np.int64) if peak else None
-        self._check(self._lib.mtg_epoch_fold(self._ctx, F, _ptr(freqs), int(nbins), self._fold_epoch(time_0), int(normalization),
-                                             int(bool(weighted)), _ptr(out), _ptr(pk),
-                                             None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        normalization = _ls_normalization(normalization, extras=("chi2",))
+        chi2 = isinstance(normalization, str)
+        F = len(freqs)
+        (out, pk, ix), pick = _power_and_peak(int(self.L), F, power, peak)
+        self._check(self._lib.mtg_epoch_fold(self._ctx, F, _ptr(freqs), int(nbins), self._fold_epoch(time_0),
+                                             LS_PSD if chi2 else int(normalization), int(bool(weighted)), _ptr(out), _ptr(pk), _lptr(ix)))
         if chi2:   # (a factor of two is exact: the peaks stay where they are)
             out = None if out is None else 2.0 * out
             pk = None if pk is None else 2.0 * pk
-        if power and peak:
-            return out, pk, ix
-        return out if power else (pk, ix)
+        return pick(out, pk, ix)
 
     def wwz(self, freqs, taus, decay=WWZ_DECAY, statistic="z", weighted=True, values=True, neff=False, peak=False):
         """Foster's weighted wavelet Z-transform (1996) of every resident light curve at ``freqs`` [F] and the window
@@ -931,8 +941,7 @@ class Engine:
         pk = np.full(L, np.nan) if peak else None
         ix = np.full(L, -1, dtype=np.int64) if peak else None
         self._check(self._lib.mtg_wwz(self._ctx, F, _ptr(freqs), T, _ptr(taus), float(decay), int(statistic), int(bool(weighted)),
-                                      _ptr(out), _ptr(ne), _ptr(pk),
-                                      None if ix is None else ix.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+                                      _ptr(out), _ptr(ne), _ptr(pk), _lptr(ix)))
         got = ([out] if values else []) + ([ne] if neff else []) + ([pk, ix] if peak else [])
         return got[0] if len(got) == 1 else tuple(got)
 
@@ -950,10 +959,7 @@ class Engine:
             raise ValueError("lag_sums: nothing asked for")
         if len(edges) < 2:
             raise ValueError("lag_sums: need at least two edges")
-        shape = (int(self.L), len(edges) - 1)
-        out = {k: (np.zeros(shape, dtype=np.int64) if k == "count" else np.full(shape, np.nan)) for k in LAG_SUMS if want[k]}
-        ptrs = [None if k not in out else out[k].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if k == "count" else _ptr(out[k])
-                for k in LAG_SUMS]
+        out, ptrs = _bin_sums(LAG_SUMS, want, (int(self.L), len(edges) - 1))
         self._check(self._lib.mtg_lag_sums(self._ctx, len(edges) - 1, _ptr(edges), *ptrs))
         return out
 
@@ -979,10 +985,7 @@ class Engine:
         if t2.ndim != 1 or y2.ndim not in (1, 2) or y2.shape[-1] != len(t2):
             raise ValueError("cross_sums: t2 must be [M] and y2 [M] or [L][M]")
         L2 = 1 if y2.ndim == 1 else y2.shape[0]
-        shape = (int(self.L), len(edges) - 1)
-        out = {k: (np.zeros(shape, dtype=np.int64) if k == "count" else np.full(shape, np.nan)) for k in CROSS_SUMS if want[k]}
-        ptrs = [None if k not in out else out[k].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if k == "count" else _ptr(out[k])
-                for k in CROSS_SUMS]
+        out, ptrs = _bin_sums(CROSS_SUMS, want, (int(self.L), len(edges) - 1))
         self._check(self._lib.mtg_cross_sums(self._ctx, len(t2), _ptr(t2), L2, _ptr(y2), len(edges) - 1, _ptr(edges), *ptrs))
         return out
 
@@ -997,8 +1000,7 @@ class Engine:
         count = np.zeros(shape, dtype=np.int64)
         wsum, wrsum, varsum = np.full(shape, np.nan), np.full(shape, np.nan), np.full(shape, np.nan)
         self._check(self._lib.mtg_phase_fold(self._ctx, len(freqs), _ptr(freqs), int(nbins), self._fold_epoch(time_0),
-                                             int(bool(weighted)), count.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                             _ptr(wsum), _ptr(wrsum), _ptr(varsum)))
+                                             int(bool(weighted)), _lptr(count), _ptr(wsum), _ptr(wrsum), _ptr(varsum)))
         return PhaseFold(count, wsum, wrsum, varsum)
 
     def lomb_scargle_envelope(self, freqs, ranks=(), reference=None, scale=None, normalization="standard", weighted=True, nterms=1):
@@ -1017,14 +1019,10 @@ class Engine:
 
         A model need not be set (mtg_lomb_scargle_envelope)."""
         freqs = _f64(np.atleast_1d(freqs)).ravel()
-        if isinstance(normalization, str):
-            if normalization not in LS_NORMALIZATIONS:
-                raise ValueError("normalization must be one of %s" % sorted(LS_NORMALIZATIONS))
-            normalization = LS_NORMALIZATIONS[normalization]
+        normalization = _ls_normalization(normalization)
         F, L = len(freqs), int(self.L)
         ranks = np.ascontiguousarray(np.atleast_1d(ranks), dtype=np.int64).ravel()
         Q = len(ranks)
-        ip = lambda a: None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
         order_stat = np.full((Q, F), np.nan) if Q else None
         nvalid = np.zeros(F, dtype=np.int64) if (Q or reference is not None) else None
         exceed = None
@@ -1039,7 +1037,7 @@ class Engine:
             if len(scale) != F:
                 raise ValueError("scale must have one entry per frequency")
             pk, ix = np.full(L, np.nan), np.full(L, -1, dtype=np.int64)
-        rest = (Q, ip(ranks) if Q else None, _ptr(order_stat), ip(nvalid), _ptr(reference), ip(exceed), _ptr(scale), _ptr(pk), ip(ix))
+        rest = (Q, _lptr(ranks) if Q else None, _ptr(order_stat), _lptr(nvalid), _ptr(reference), _lptr(exceed), _ptr(scale), _ptr(pk), _lptr(ix))
         if nterms == 1:
             self._check(self._lib.mtg_lomb_scargle_envelope(self._ctx, F, _ptr(freqs), int(normalization), int(bool(weighted)), *rest))
         else:
@@ -1228,7 +1226,7 @@ class Engine:
         if normals.ndim != 3 or normals.shape[1] != 2 or starts.shape != (normals.shape[0],):
             raise ValueError("normals must be [S][2][nk] and starts [S]")
         self._check(self._lib.mtg_set_simulate_draws(self._ctx, normals.shape[0], normals.shape[2], _ptr(normals),
-                                                     starts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+                                                     _lptr(starts)))
 
     @property
     def acf_plans_built(self):

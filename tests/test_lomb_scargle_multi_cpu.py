@@ -130,6 +130,40 @@ def test_planner_against_its_restatement():
         assert r.stdout.split() == ["0", "0"]
 
 
+def planned_slab(F, tile, L):
+    """mtg_ls_slab restated: at most 2^25 powers on the device, in whole tiles, at least one tile, at most L"""
+    return min(max((2 ** 25 // F) // tile * tile, tile), L)
+
+
+def test_slab_rule_against_its_restatement():
+    """light curves per slab of mtg_lomb_scargle and mtg_epoch_fold (csrc/mtg_ls_plan.h: mtg_ls_slab)"""
+    with tempfile.TemporaryDirectory(prefix="ls_slab_") as tmp:
+        exe = os.path.join(tmp, "ls_multi_plan_driver")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "mind_the_gaps_amd", "csrc"),
+                               os.path.join(HERE, "ls_multi_plan_driver.cpp"), "-o", exe])
+        tiles = sorted({planned_tile(K, 100, 1, w) for K in (1, 2, 3, 4, 5) for w in (0, 1)} | {1, 2, 4})    # mtg_ls_full_tile's, mtg_ef_plan's
+        assert tiles == [1, 2, 4, 6, 8, 10, 16]
+        cases = []
+        for F in (1, 3, 70, 2 ** 21, 2 ** 21 + 1, 2 ** 25 - 1, 2 ** 25, 2 ** 25 + 1):
+            for tile in tiles:
+                one = planned_slab(F, tile, 10 ** 12)      # a slab of a set too large for one
+                cases += [(F, tile, L) for L in sorted({1, 2, tile, tile + 1, max(one - 1, 1), one, one + 1, 3 * one + 1, 10 ** 6})]
+        r = subprocess.run([exe], input="".join("slab %d %d %d\n" % c for c in cases), capture_output=True, text=True, check=True)
+        got = [int(v) for v in r.stdout.split()]
+        assert len(got) == len(cases)
+        for (F, tile, L), slab in zip(cases, got):
+            assert slab == planned_slab(F, tile, L), (F, tile, L, slab)
+            assert slab == L or slab % tile == 0, (F, tile, L, slab)             # whole tiles, unless the whole set
+            assert slab == L or slab >= tile, (F, tile, L, slab)                 # at least one tile, or the whole set
+            assert 1 <= slab <= L
+            assert slab * F <= 2 ** 25 or slab == min(tile, L), (F, tile, L, slab)   # the budget, but where one tile exceeds it
+        # pinned: one frequency keeps 2^25 light curves; 2^21 frequencies 16, whatever the tile divides; past the budget a tile
+        assert got[cases.index((1, 1, 10 ** 6))] == 10 ** 6
+        assert [planned_slab(2 ** 21, tile, 100) for tile in tiles] == [16, 16, 16, 12, 16, 10, 16]
+        assert [planned_slab(2 ** 25 + 1, tile, 100) for tile in tiles] == tiles
+        assert planned_slab(2 ** 25, 1, 100) == 1 and planned_slab(2 ** 25, 4, 3) == 3
+
+
 def test_resource_report_lists_every_instantiation_without_scratch():
     text = open(os.path.join(ROOT, "profiles", "lomb_scargle_multi_resources.txt")).read()
     rows = {m.group(1): [int(v) for v in m.group(2).split()]
