@@ -162,10 +162,7 @@ hipError_t mtg_launch_epoch_fold(const MtgEpochFoldArgs &q, const MtgEfPlan &pla
     const int64_t nfb = (ls.F + plan.lanes - 1) / plan.lanes, tiles = (Ls + R - 1) / R;
     if (nfb > 0x7fffffff / tiles) return hipErrorInvalidValue;
     MtgEfArgs g;
-    MtgLsArgs &a = g.a;
-    a.dxt = ls.dxt; a.yv = ls.yv; a.N = ls.N; a.t_stride = ls.t_stride; a.l0 = l0; a.Ls = Ls;
-    a.stats = reinterpret_cast<const double4 *>(ls.stats); a.F = ls.F; a.freqs = ls.freqs; a.nfb = (int)nfb;
-    a.normalization = ls.normalization; a.power = ls.power;
+    g.a = mtg_ls_args(ls, l0, Ls, nfb);
     g.nbins = q.nbins; g.time_0 = q.time_0; g.wsum = q.wsum; g.wrsum = q.wrsum;
     hipError_t e = hipSuccess;
     if (ls.power || q.wsum || q.wrsum) {

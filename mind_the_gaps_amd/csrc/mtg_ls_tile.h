@@ -1,7 +1,9 @@
 // mtg_ls_tile.h -- the tile sweep of the Lomb-Scargle kernels, written once for one term (mtg_lomb_scargle.hip) and
 // K harmonics (mtg_lomb_scargle_multi.hip).  A model says what a lane accumulates per sample and how the sums become
 // the power p; everything with an edge is here: the ragged last chunk, the partly filled tile, a slab that starts at
-// l0 > 0, idle lanes, and the launch geometry.
+// l0 > 0, idle lanes, and the launch geometry.  The pieces -- mtg_ls_args, LsLane, ls_stage_chunk, ls_read_sample --
+// also serve the two sweeps that keep other sums per lane and so have a chunk loop of their own: mtg_epoch_fold.hip
+// (time origin q.t0 = time_0) and mtg_wwz.hip (a third grid factor, q.t0 = tau, and its own column rule).
 //
 // One lane owns a frequency; a workgroup walks the samples in chunks of MTG_LS_CHUNK staged in LDS, every lane reading
 // the same sample (a broadcast).  On shared sampling a lane carries the sums of a tile of R light curves
@@ -44,6 +46,16 @@ struct MtgLsArgs {
     double *power;           // [Ls][F] of this slab
 };
 
+// the arguments of one slab's launch from the call's: light curves [l0, l0 + Ls), nfb workgroups along the frequencies
+static inline MtgLsArgs mtg_ls_args(const MtgLombScargleArgs &q, int64_t l0, int64_t Ls, int64_t nfb)
+{
+    MtgLsArgs a;
+    a.dxt = q.dxt; a.yv = q.yv; a.N = q.N; a.t_stride = q.t_stride; a.l0 = l0; a.Ls = Ls;
+    a.stats = reinterpret_cast<const double4 *>(q.stats); a.F = q.F; a.freqs = q.freqs; a.nfb = (int)nfb;
+    a.normalization = q.normalization; a.power = q.power;
+    return a;
+}
+
 // The launch of one slab with R light curves per lane: false = more workgroups than a grid holds.  Narrow frequency
 // lists leave most of a wide workgroup idle: one or two waves then (the arithmetic of a lane is the same).
 struct MtgLsLaunch {
@@ -57,10 +69,7 @@ static inline bool mtg_ls_plan_launch(const MtgLombScargleArgs &q, int R, int64_
     const int64_t nfb = (q.F + g->threads - 1) / g->threads, tiles = (Ls + R - 1) / R;
     if (nfb > 0x7fffffff / tiles) return false;
     g->blocks = nfb * tiles;
-    MtgLsArgs &a = g->a;
-    a.dxt = q.dxt; a.yv = q.yv; a.N = q.N; a.t_stride = q.t_stride; a.l0 = l0; a.Ls = Ls;
-    a.stats = reinterpret_cast<const double4 *>(q.stats); a.F = q.F; a.freqs = q.freqs; a.nfb = (int)nfb;
-    a.normalization = q.normalization; a.power = q.power;
+    g->a = mtg_ls_args(q, l0, Ls, nfb);
     return true;
 }
 
@@ -71,12 +80,10 @@ struct LsLane {
     int64_t k;             // the lane's frequency (idle lanes, k >= F, repeat the last one and store nothing)
     double f;
     const double2 *dxt;    // the tile's sampling
-    double t0, w0;         // its first time; 1 / N
+    double t0, w0;         // the origin of the elapsed times: its first time, unless the kernel sets another; 1 / N
     template <int R>
-    __device__ __forceinline__ void locate(const MtgLsArgs &a)
+    __device__ __forceinline__ void locate(const MtgLsArgs &a, int64_t tile, int fb)
     {
-        const int64_t tile = blockIdx.x / a.nfb;
-        const int fb = (int)(blockIdx.x - tile * a.nfb);
         lt = a.l0 + tile * R;
         nl = (int)(a.l0 + a.Ls - lt < R ? a.l0 + a.Ls - lt : R);
         k = (int64_t)fb * blockDim.x + threadIdx.x;
@@ -85,10 +92,24 @@ struct LsLane {
         t0 = dxt[0].y;
         w0 = 1.0 / (double)a.N;
     }
+    // a grid of frequency blocks, fastest, and tiles
+    template <int R>
+    __device__ __forceinline__ void locate(const MtgLsArgs &a)
+    {
+        const int64_t tile = blockIdx.x / a.nfb;
+        locate<R>(a, tile, (int)(blockIdx.x - tile * a.nfb));
+    }
 };
 
-// samples [n0, n0 + len) of the tile into LDS; a light curve beyond the tile adds zeros and is not stored
-template <int R, bool WEIGHTED>
+// What a column of the chunk holds, from a sample's weight and residual: (w, w r) per light curve, and w0 r where the
+// weights are 1 / N.  (mtg_wwz.hip, whose weight gets a factor per lane, has a rule of its own.)
+struct LsColumns {
+    static __device__ __forceinline__ double2 weighted(double w, double r) { return make_double2(w, w * r); }
+    static __device__ __forceinline__ double plain(double w0, double r) { return w0 * r; }
+};
+
+// samples [n0, n0 + len) of the tile into LDS, elapsed from q.t0; a light curve beyond the tile adds zeros and is not stored
+template <int R, bool WEIGHTED, class C = LsColumns>
 __device__ __forceinline__ void ls_stage_chunk(const MtgLsArgs &a, const LsLane &q, int64_t n0, int len, double *te_s, double2 *col_s)
 {
 #pragma clang fp contract(off)
@@ -104,22 +125,21 @@ __device__ __forceinline__ void ls_stage_chunk(const MtgLsArgs &a, const LsLane 
             if (j < q.nl) {
                 const double4 st = a.stats[lt + j];
                 const double2 v = a.yv[(lt + j) * a.N + n0 + i];
-                const double w = (1.0 / v.y) / st.z;
-                o = make_double2(w, w * (v.x - st.x));
+                o = C::weighted((1.0 / v.y) / st.z, v.x - st.x);
             }
             col_s[j * CH + i] = o;
         }
     } else if (R == 1) {
         const double ybar = a.stats[lt].x;
         double *col = reinterpret_cast<double *>(col_s);
-        for (int i = tid; i < len; i += nth) col[i] = q.w0 * (a.yv[lt * a.N + n0 + i].x - ybar);
+        for (int i = tid; i < len; i += nth) col[i] = C::plain(q.w0, a.yv[lt * a.N + n0 + i].x - ybar);
     } else {
         for (int e = tid; e < (R + 1) / 2 * CH; e += nth) {
             const int j = e / CH, i = e - j * CH;
             if (i >= len) continue;
             double2 o = make_double2(0.0, 0.0);
-            if (2 * j < q.nl) o.x = q.w0 * (a.yv[(lt + 2 * j) * a.N + n0 + i].x - a.stats[lt + 2 * j].x);
-            if (2 * j + 1 < q.nl) o.y = q.w0 * (a.yv[(lt + 2 * j + 1) * a.N + n0 + i].x - a.stats[lt + 2 * j + 1].x);
+            if (2 * j < q.nl) o.x = C::plain(q.w0, a.yv[(lt + 2 * j) * a.N + n0 + i].x - a.stats[lt + 2 * j].x);
+            if (2 * j + 1 < q.nl) o.y = C::plain(q.w0, a.yv[(lt + 2 * j + 1) * a.N + n0 + i].x - a.stats[lt + 2 * j + 1].x);
             col_s[j * CH + i] = o;
         }
     }

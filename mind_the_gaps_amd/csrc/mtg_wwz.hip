@@ -10,8 +10,12 @@
 // does not decrease with f or with |te_n|.
 //
 // One lane owns a frequency; a workgroup has one tau and a tile of R light curves on shared sampling, and walks the
-// samples in the chunks of MTG_LS_CHUNK that mtg_ls_tile.h's sweep walks.  Weighted, every light curve has its ten sums;
-// unweighted the six weight and trigonometric sums are the tile's.
+// samples in the chunks of MTG_LS_CHUNK that mtg_ls_tile.h's sweep walks, on that header's pieces: MtgLsArgs inside
+// WwzArgs, LsLane::locate with the tile and the frequency block of a grid that has the centres as a third factor and
+// q.t0 = tau, ls_stage_chunk with the columns (s, r) and r of WwzColumns, ls_read_sample.  The ragged chunk, the partly
+// filled tile, l0 > 0 and idle lanes are that header's; the chunk range, te^2 - te_*^2, the cut, the window, the ten
+// sums, the solve and the [Ls][T][F] store are this file's.  Weighted, every light curve has its ten sums; unweighted
+// the six weight and trigonometric sums are the tile's.
 //
 // Skipping.  A chunk all of whose samples are cut at the workgroup's lowest frequency is cut at every lane's (E is
 // monotone in f), and the sample of a chunk nearest to tau is one of its ends or lies across tau (the times ascend, and
@@ -34,18 +38,19 @@ namespace {
 #define MTG_WWZ_CUT (80.0 * 0x1.62e42fefa39efp-1)   /* 80 ln 2 */
 
 struct WwzArgs {
-    const double2 *dxt, *yv;
-    int64_t N, t_stride;     // 0 (shared sampling) or N
-    int64_t l0, Ls;          // this launch takes light curves [l0, l0 + Ls)
-    const double4 *stats;    // [L]: ybar, YY, sum sigma^-2 (or N), 0 -- mtg_lomb_scargle_stats_kernel's
-    int64_t F, T;
-    const double *freqs;     // [F]
+    MtgLsArgs a;             // (power: NULL or the values [Ls][T][F] of this slab; normalization unused)
+    int64_t T;
     const double *taus;      // [T]
-    int nfb;                 // workgroups along the frequencies
     double kc;               // 4 pi^2 c
     int statistic;
     const double *near2;     // [samplings of the slab][T]: te_* te_*
-    double *out, *neff;      // NULL or [Ls][T][F] of this slab
+    double *neff;            // NULL or [Ls][T][F] of this slab
+};
+
+// the chunk's columns hold (s, r) and r: the weight of a sample is s times the lane's window (unweighted the window alone)
+struct WwzColumns {
+    static __device__ __forceinline__ double2 weighted(double s, double r) { return make_double2(s, r); }
+    static __device__ __forceinline__ double plain(double, double r) { return r; }
 };
 
 // te_* te_* of every (sampling of the slab, tau): the sample on either side of tau by bisection of the ascending times
@@ -135,7 +140,7 @@ __device__ __forceinline__ double wwz_solve(const WwzTrig &t, const WwzData &d, 
 // else 1 (the weight and trigonometric sums are the tile's)
 template <int R, bool WEIGHTED>
 __global__ void __launch_bounds__(MTG_WWZ_MAX_LANES, 2)
-mtg_wwz_kernel(const WwzArgs a)
+mtg_wwz_kernel(const WwzArgs g)
 {
 #pragma clang fp contract(off)
     static_assert(WEIGHTED || R == 1 || R % 2 == 0, "the unweighted chunk is staged as pairs of light curves");
@@ -149,24 +154,21 @@ mtg_wwz_kernel(const WwzArgs a)
     __shared__ int range_s[2];
 
     mtg_ls_fill_tab(&tab);
+    const MtgLsArgs &a = g.a;
     const int tid = threadIdx.x, nth = blockDim.x;
     // workgroup -> (tile, tau, frequency block), the frequency blocks fastest
-    const int64_t per_tile = (int64_t)a.nfb * a.T;
+    const int64_t per_tile = (int64_t)a.nfb * g.T;
     const int64_t tile = blockIdx.x / per_tile;
     const int64_t rest = blockIdx.x - tile * per_tile;
     const int64_t jt = rest / a.nfb;
-    const int fb = (int)(rest - jt * a.nfb);
-    const int64_t lt = a.l0 + tile * R;                                          // first light curve of the tile
-    const int nl = (int)(a.l0 + a.Ls - lt < R ? a.l0 + a.Ls - lt : R);           // light curves in it
-    const int64_t k = (int64_t)fb * nth + tid;                                   // idle lanes repeat the last frequency
-    const double f = a.freqs[k < a.F ? k : a.F - 1];
-    const double2 *dxt = a.dxt + lt * a.t_stride;
-    const double tau = a.taus[jt];
-    const double ts2 = a.near2[(a.t_stride ? lt - a.l0 : 0) * a.T + jt];
-    const double af = (a.kc * f) * f;
+    LsLane q;
+    q.locate<R>(a, tile, (int)(rest - jt * a.nfb));
+    q.t0 = g.taus[jt];   // elapsed times from the window's centre
+    const double ts2 = g.near2[(a.t_stride ? q.lt - a.l0 : 0) * g.T + jt];
+    const double af = (g.kc * q.f) * q.f;
 
     // the workgroup's lowest frequency, then the range of chunks it keeps
-    red[tid] = f;
+    red[tid] = q.f;
     if (tid == 0) { range_s[0] = 0x7fffffff; range_s[1] = 0; }
     __syncthreads();
     for (int h = nth / 2; h > 0; h >>= 1) {
@@ -174,11 +176,11 @@ mtg_wwz_kernel(const WwzArgs a)
         __syncthreads();
     }
     const double flow = red[0];
-    const double alow = (a.kc * flow) * flow;
+    const double alow = (g.kc * flow) * flow;
     const int nch = (int)((a.N + CH - 1) / CH);
     for (int c = tid; c < nch; c += nth) {
         const int64_t n0 = (int64_t)c * CH, n1 = (a.N - n0 < CH ? a.N : n0 + CH) - 1;
-        const double te0 = dxt[n0].y - tau, te1 = dxt[n1].y - tau;
+        const double te0 = q.dxt[n0].y - q.t0, te1 = q.dxt[n1].y - q.t0;
         const double m = te0 >= 0.0 ? te0 : te1 <= 0.0 ? -te1 : 0.0;   // the least |te| a sample of the chunk can have
         const double E = alow * (m * m - ts2);
         if (!(E > MTG_WWZ_CUT)) {
@@ -200,39 +202,8 @@ mtg_wwz_kernel(const WwzArgs a)
         const int64_t n0 = (int64_t)c * CH;
         const int len = (int)(a.N - n0 < CH ? a.N - n0 : CH);
         __syncthreads();   // the previous chunk has been read (first trip: the range)
-        for (int i = tid; i < len; i += nth) {
-            const double te = dxt[n0 + i].y - tau;
-            te_s[i] = te;
-            dd_s[i] = te * te - ts2;
-        }
-        // the columns: weighted (s, r) per light curve, else r as pairs of light curves (R = 1: plain doubles); a light
-        // curve beyond the tile adds zeros and is not stored
-        if (WEIGHTED) {
-            for (int e = tid; e < R * CH; e += nth) {
-                const int j = e / CH, i = e - j * CH;
-                if (i >= len) continue;
-                double2 o = make_double2(0.0, 0.0);
-                if (j < nl) {
-                    const double4 st = a.stats[lt + j];
-                    const double2 v = a.yv[(lt + j) * a.N + n0 + i];
-                    o = make_double2((1.0 / v.y) / st.z, v.x - st.x);
-                }
-                col_s[j * CH + i] = o;
-            }
-        } else if (R == 1) {
-            const double ybar = a.stats[lt].x;
-            double *col = reinterpret_cast<double *>(col_s);
-            for (int i = tid; i < len; i += nth) col[i] = a.yv[lt * a.N + n0 + i].x - ybar;
-        } else {
-            for (int e = tid; e < NP * CH; e += nth) {
-                const int j = e / CH, i = e - j * CH;
-                if (i >= len) continue;
-                double2 o = make_double2(0.0, 0.0);
-                if (2 * j < nl) o.x = a.yv[(lt + 2 * j) * a.N + n0 + i].x - a.stats[lt + 2 * j].x;
-                if (2 * j + 1 < nl) o.y = a.yv[(lt + 2 * j + 1) * a.N + n0 + i].x - a.stats[lt + 2 * j + 1].x;
-                col_s[j * CH + i] = o;
-            }
-        }
+        ls_stage_chunk<R, WEIGHTED, WwzColumns>(a, q, n0, len, te_s, col_s);
+        for (int i = tid; i < len; i += nth) dd_s[i] = te_s[i] * te_s[i] - ts2;   // (te_s[i] is this thread's own store)
         __syncthreads();
 
         WwzTrig pt[NT];
@@ -244,29 +215,15 @@ mtg_wwz_kernel(const WwzArgs a)
         for (int i = 0; i < len; ++i) {
             const double E = af * dd_s[i];
             if (E > MTG_WWZ_CUT) continue;   // the cut: this sample's weight is 0
-            const double g = exp(-E);
-            double si, co;
-            mtg_cycles_sincos(f, te_s[i], &si, &co, &tab);
-            if (WEIGHTED) {
+            const double win = exp(-E);
+            double si, co, s[NT], r[R];
+            mtg_cycles_sincos(q.f, te_s[i], &si, &co, &tab);
+            ls_read_sample<R, WEIGHTED>(col_s, i, 1.0, s, r);
 #pragma unroll
-                for (int j = 0; j < R; ++j) {
-                    const double2 v = col_s[j * CH + i];
-                    const double wg = v.x * g;
-                    pt[j].add(wg, co, si);
-                    py[j].add(wg, v.y, co, si);
-                }
-            } else {
-                pt[0].add(g, co, si);
-                if (R == 1) {
-                    py[0].add(g, reinterpret_cast<const double *>(col_s)[i], co, si);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < R / 2; ++j) {
-                        const double2 v = col_s[j * CH + i];
-                        py[2 * j].add(g, v.x, co, si);
-                        py[2 * j + 1].add(g, v.y, co, si);
-                    }
-                }
+            for (int j = 0; j < R; ++j) {
+                const double wg = WEIGHTED ? s[j < NT ? j : 0] * win : win;   // unweighted: the window alone, no factor
+                if (j < NT) pt[j].add(wg, co, si);
+                py[j].add(wg, r[j], co, si);
             }
         }
 #pragma unroll
@@ -275,15 +232,15 @@ mtg_wwz_kernel(const WwzArgs a)
         for (int i = 0; i < R; ++i) ty[i].fold(py[i]);
     }
 
-    if (k >= a.F) return;
+    if (q.k >= a.F) return;
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-        if (j >= nl) continue;
+        if (j >= q.nl) continue;
         double ne;
-        const double v = wwz_solve(tt[WEIGHTED ? j : 0], ty[j], a.statistic, &ne);
-        const int64_t at = ((lt - a.l0 + j) * a.T + jt) * a.F + k;
-        if (a.out) a.out[at] = v;
-        if (a.neff) a.neff[at] = ne;
+        const double v = wwz_solve(tt[WEIGHTED ? j : 0], ty[j], g.statistic, &ne);
+        const int64_t at = ((q.lt - a.l0 + j) * g.T + jt) * a.F + q.k;
+        if (a.power) a.power[at] = v;
+        if (g.neff) g.neff[at] = ne;
     }
 }
 
@@ -310,9 +267,8 @@ hipError_t mtg_launch_wwz(const MtgWwzArgs &q, const MtgWwzPlan &plan, int64_t l
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     WwzArgs g;
-    g.dxt = ls.dxt; g.yv = ls.yv; g.N = ls.N; g.t_stride = ls.t_stride; g.l0 = l0; g.Ls = Ls;
-    g.stats = reinterpret_cast<const double4 *>(ls.stats); g.F = ls.F; g.T = q.T; g.freqs = ls.freqs; g.taus = q.taus;
-    g.nfb = (int)plan.nfb; g.kc = q.kc; g.statistic = q.statistic; g.near2 = q.nearest; g.out = ls.power; g.neff = q.neff;
+    g.a = mtg_ls_args(ls, l0, Ls, plan.nfb);
+    g.T = q.T; g.taus = q.taus; g.kc = q.kc; g.statistic = q.statistic; g.near2 = q.nearest; g.neff = q.neff;
     if (ls.weighted) {
         if (R == 1) wwz_launch<1, true>(g, blocks, plan.lanes, s);
         else wwz_launch<RW, true>(g, blocks, plan.lanes, s);
