@@ -922,6 +922,70 @@ MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2 /* [M] host
                            double *saa    /* [L][nbins] or NULL */, double *sbb /* [L][nbins] or NULL */);
 
 /*
+ * The interpolated cross-correlation function (ICCF) of Gaskell & Peterson (1987, ApJS 65, 1) and White & Peterson (1994,
+ * PASP 106, 879) of every resident light curve l and a companion series given with the call, on a grid of K lags: the
+ * measure whose peak and centroid above 0.8 of the peak reverberation mapping quotes as the lag (Peterson et al. 1998,
+ * PASP 110, 660).  It is the opposite trade to mtg_cross_sums: the resolution is the lag grid's, not a bin's, and the
+ * price is that one series is LINEARLY INTERPOLATED at the other's shifted times.  Interpolation across a gap invents
+ * data: n_a and n_b tell how many samples each half used, and the statistic is to be calibrated against simulated light
+ * curves on the same sampling (ppp.iccf_significance), not read against a textbook distribution.
+ * The companion has M samples at the ascending times t2 (equal times allowed) and the values y2: one row for every light
+ * curve (L2 == 1) or a row per light curve (L2 == L); it is uploaded for the call and not kept.  The resident times t_i
+ * ascend (equal times allowed, as they are stored).  The lags tau_k are finite, in any order, duplicates allowed; a
+ * positive lag means the companion lags the resident series, as in mtg_cross_sums.
+ *   residuals     r_i = y_i - ybar_l and s_j = y2_j - ybar2, the unweighted pre-pass means of mtg_cross_sums.
+ *                 (Interpolation is linear: interpolating residuals is interpolating values.)
+ *   interpolant   I(series, x) of a series (u_n, z_n), n < P, at u_0 <= x <= u_{P-1}: p = the largest index with u_p <= x
+ *                 (plain double comparisons); p == P - 1: z_p; otherwise w = (x - u_p) / (u_{p+1} - u_p) and the value
+ *                 fma(w, z_{p+1} - z_p, z_p), every operation rounded.  The denominator is positive by construction; at
+ *                 a repeated time the LAST of the group is the left node -- this is the definition.  Outside
+ *                 [u_0, u_{P-1}] there is no value: nothing is extrapolated.
+ *   half A        (the companion interpolated) for every i with x = fl(t_i + tau_k) inside [t2_0, t2_{M-1}]:
+ *                 a_i = r_i, b_i = I(companion residuals, x); i ascending.
+ *   half B        (the resident series interpolated) for every j with x = fl(t2_j - tau_k) inside [t_0, t_{N-1}]:
+ *                 a_j = I(resident residuals, x), b_j = s_j; j ascending.
+ *   sums          over the samples of a half in that order, sequentially from zero: n += 1, Sa = Sa + a, Sb = Sb + b,
+ *                 Saa = fma(a, a, Saa), Sbb = fma(b, b, Sbb), Sab = fma(a, b, Sab).
+ *   r of a half   C = Sab - (Sa Sb) / n, Va = Saa - (Sa Sa) / n, Vb = Sbb - (Sb Sb) / n, r = C / sqrt(Va Vb): each
+ *                 product, quotient, difference and the square root one IEEE operation, n converted exactly.
+ *   NaN rule      n < 2, Va or Vb not positive, or a quotient that is not finite (Va Vb underflowed): NaN.  Never an
+ *                 infinity -- it would be every row's peak (mtg_wwz's rule).  A NaN half makes r NaN.
+ *   mode          MTG_ICCF_BOTH: r = 0.5 (r_A + r_B); MTG_ICCF_COMPANION: r = r_A; MTG_ICCF_RESIDENT: r = r_B.
+ *   ccf           [L][K] or NULL: r.   n_a, n_b [L][K] or NULL: the samples of half A and half B; 0 for a half the
+ *                 mode does not form.
+ *   peak          [L] or NULL: the largest finite ccf[l][k];  peak_index [L] or NULL: the first k attaining it; a row
+ *                 without a finite value: NaN and -1.
+ *   centroid      [L] or NULL: num / den with num = fma(tau_k, r_k, num) and den = den + r_k over the k, ascending, with
+ *                 r_k finite and r_k >= fl(threshold peak); NaN when the row has no finite value or den is not positive.
+ *                 timedomain.lag_peak_and_centroid with lag = tau.  Reduced on the device: with ccf, n_a and n_b NULL
+ *                 nothing of size L K comes back.
+ * Invariance.  Every ccf, n_a, n_b entry depends on (light curve l, its companion row, t2, tau_k, mode) alone, bit for
+ * bit: not on L, K, the order of tau, which light curves share a tile, the slabs, L2 == 1 or L2 == L with identical rows,
+ * whether the resident sampling is stored shared or per light curve, or which outputs were asked for.  peak[l] and
+ * centroid[l] depend on row l of ccf and on tau in the given order.  No floating-point atomics.
+ * One lane owns a lag and walks the samples of a half in ascending order; for a fixed lag x does not decrease, so the
+ * samples inside the other series' span are one run, found by binary search on the rounded x, and the bracket only moves
+ * up: O(N + M) per lag, light curve tile and half.  On shared resident sampling a tile of light curves shares the walk
+ * (csrc/mtg_iccf_plan.h); the device copies of the [L][K] outputs stay within 256 MiB: slabs of light curves.
+ * mtg_last_solver names "mtg_iccf_kernel<R,per,all> lanes 256" (R light curves per lane; per = 1: a companion row per
+ * light curve, taken when L2 == L > 1; all = 0: the kernel that walks half A alone, taken for MTG_ICCF_COMPANION),
+ * mtg_last_kernel_ms runs from the pre-pass through the last reduction.
+ * Against an exact rational evaluation (the square root at 50 digits) each half is within max(10 rho, 64 sqrt(n) u S) with
+ * S = Cabs / sqrt(Va Vb) + |r| (Vaabs / Va + Vbabs / Vb) / 2 what the one-pass formulas' rounding scales with, and the
+ * counts are exact (tests/test_iccf_gpu.py).
+ * MTG_E_STATE without light curves; MTG_E_ARG for M < 2 or M >= 2^28, N < 2, L2 not 1 or L, K outside
+ * 1 .. MTG_ICCF_MAX_LAGS, an unknown mode, a threshold outside (0, 1], all six outputs NULL, a t2 entry that is not finite,
+ * t2 descending, a y2 or tau entry that is not finite -- the message names the offending index; the context works as
+ * before after an error.
+ */
+enum { MTG_ICCF_BOTH = 0, MTG_ICCF_COMPANION = 1, MTG_ICCF_RESIDENT = 2, MTG_ICCF_MAX_LAGS = 65536 };
+MTG_API int mtg_iccf(mtg_ctx *ctx, int64_t M, const double *t2 /* [M] host, ascending */,
+                     int64_t L2 /* 1 or L */, const double *y2 /* [L2][M] host */,
+                     int64_t K, const double *tau /* [K] host */, int mode, double threshold,
+                     double *ccf /* [L][K] or NULL */, int64_t *n_a /* [L][K] or NULL */, int64_t *n_b /* [L][K] or NULL */,
+                     double *peak /* [L] or NULL */, int64_t *peak_index /* [L] or NULL */, double *centroid /* [L] or NULL */);
+
+/*
  * What the periodograms of the resident set say about every frequency: reductions of power[l][k] ACROSS the light
  * curves, without the [L][F] array ever leaving the device.  power[l][k] is, by definition and bit for bit, what
  * mtg_lomb_scargle returns for the same resident set, frequency, normalization and weighting (its launcher computes it).

@@ -2909,6 +2909,79 @@ MTG_API int mtg_cross_sums(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2
     return c.finish();   // (waits for the stream: `pairs` outlives its upload)
 }
 
+MTG_API int mtg_iccf(mtg_ctx *ctx, int64_t M, const double *t2, int64_t L2, const double *y2, int64_t K, const double *tau, int mode,
+                     double threshold, double *ccf, int64_t *n_a, int64_t *n_b, double *peak, int64_t *peak_index, double *centroid)
+{
+    const char *who = "mtg_iccf";
+    ResidentCall c{ctx, who};
+    int rc = c.ready();
+    if (rc) return rc;
+    const int64_t L = ctx->L;
+    if (M < 2 || M >= MTG_ICCF_MAX_M) return fail(ctx, MTG_E_ARG, "%s: M = %lld is outside 2 .. 2^28 - 1", who, (long long)M);
+    if (ctx->N < 2) return fail(ctx, MTG_E_ARG, "%s: N = %lld < 2 samples (nothing to interpolate between)", who, (long long)ctx->N);
+    if (L2 != 1 && L2 != L) return fail(ctx, MTG_E_ARG, "%s: L2 = %lld is neither 1 nor L = %lld", who, (long long)L2, (long long)L);
+    if (!t2 || !y2) return fail(ctx, MTG_E_ARG, "%s: need the companion's M times and L2 x M values", who);
+    if (K < 1 || K > MTG_ICCF_MAX_LAGS || !tau) return fail(ctx, MTG_E_ARG, "%s: K = %lld lags is outside 1 .. %d", who, (long long)K, (int)MTG_ICCF_MAX_LAGS);
+    if (mode < MTG_ICCF_BOTH || mode > MTG_ICCF_RESIDENT) return fail(ctx, MTG_E_ARG, "%s: unknown mode %d", who, mode);
+    if (!(threshold > 0.0 && threshold <= 1.0)) return fail(ctx, MTG_E_ARG, "%s: threshold = %g is outside (0, 1]", who, threshold);
+    const bool want_peak = peak || peak_index || centroid, want_values = ccf || want_peak;
+    if (!want_values && !n_a && !n_b) return fail(ctx, MTG_E_ARG, "%s: every output is NULL", who);
+    for (int64_t j = 0; j < M; ++j) {
+        if (!std::isfinite(t2[j])) return fail(ctx, MTG_E_ARG, "%s: t2[%lld] is not finite", who, (long long)j);
+        if (j > 0 && t2[j] < t2[j - 1])
+            return fail(ctx, MTG_E_ARG, "%s: t2[%lld] = %g is below t2[%lld] = %g (the times must ascend)", who, (long long)j, t2[j],
+                        (long long)(j - 1), t2[j - 1]);
+    }
+    for (int64_t k = 0; k < L2 * M; ++k)
+        if (!std::isfinite(y2[k])) return fail(ctx, MTG_E_ARG, "%s: y2[%lld][%lld] is not finite", who, (long long)(k / M), (long long)(k % M));
+    for (int64_t k = 0; k < K; ++k)
+        if (!std::isfinite(tau[k])) return fail(ctx, MTG_E_ARG, "%s: tau[%lld] is not finite", who, (long long)k);
+    if ((rc = c.begin())) return rc;
+    const int arrays = (want_values ? 1 : 0) + (n_a ? 1 : 0) + (n_b ? 1 : 0);
+    // (a set of one light curve has L2 == 1 == L: the shared-companion kernel, the same arithmetic)
+    const MtgIccfPlan plan = mtg_iccf_plan(K, L, !ctx->t_per_lc, L2 == L && L > 1, mode == MTG_ICCF_COMPANION, arrays);
+    const int64_t Ls = plan.slab;
+    const size_t rows2 = (size_t)L2 * (size_t)M, slab_bytes = (size_t)Ls * (size_t)K * 8;
+    std::vector<double2> pairs(rows2);   // the companion as the pre-pass reads a light curve, as in mtg_cross_sums
+    for (size_t k = 0; k < rows2; ++k) pairs[k] = make_double2(y2[k], 1.0);
+    // neighbouring lanes take neighbouring lags: the lags' ranks, ties in the given order (no output bit depends on it)
+    std::vector<int32_t> order((size_t)K);
+    for (int64_t k = 0; k < K; ++k) order[(size_t)k] = (int32_t)k;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t p, int32_t q) { return tau[p] < tau[q]; });
+    DevBuf d_tau, d_order, d_t2, d_yv2, d_stats2, d_ccf, d_na, d_nb, d_centroid;
+    c.reserve({{d_tau, (size_t)K * 8}, {d_order, (size_t)K * 4}, {d_t2, (size_t)M * 8}, {d_yv2, rows2 * 16}, {d_stats2, (size_t)L2 * 32},
+               {d_ccf, want_values ? slab_bytes : 0}, {d_na, n_a ? slab_bytes : 0}, {d_nb, n_b ? slab_bytes : 0},
+               {d_centroid, centroid ? (size_t)L * 8 : 0}});
+    MtgIccfArgs qa;
+    qa.ls = c.args(1, MTG_LS_STANDARD, 0, 0, nullptr, nullptr, peak || peak_index);
+    c.upload(d_tau.p, tau, (size_t)K * 8);
+    c.upload(d_order.p, order.data(), (size_t)K * 4);
+    c.upload(d_t2.p, t2, (size_t)M * 8);
+    c.upload(d_yv2.p, pairs.data(), rows2 * 16);
+    MtgLombScargleArgs companion = qa.ls;      // the same pre-pass on the companion's rows as light curves of M samples
+    companion.dxt = nullptr; companion.yv = d_yv2.as<double2>(); companion.N = M; companion.t_stride = 0; companion.L = L2;
+    companion.stats = d_stats2.as<double>();
+    qa.M = M; qa.t2 = d_t2.as<double>(); qa.yv2 = d_yv2.as<double2>(); qa.stats2 = d_stats2.as<double>();
+    qa.K = K; qa.tau = d_tau.as<double>(); qa.order = d_order.as<int32_t>(); qa.mode = mode; qa.threshold = threshold;
+    qa.ccf = want_values ? d_ccf.as<double>() : nullptr;
+    qa.n_a = n_a ? d_na.as<int64_t>() : nullptr; qa.n_b = n_b ? d_nb.as<int64_t>() : nullptr;
+    qa.peak = qa.ls.peak_power; qa.peak_index = qa.ls.peak_index;   // (both or neither)
+    qa.centroid = centroid ? d_centroid.as<double>() : nullptr;
+    snprintf(ctx->last_solver, sizeof ctx->last_solver, "mtg_iccf_kernel<%d,%d,%d> lanes %d", plan.tile, plan.per, plan.all,
+             (int)MTG_ICCF_LANES);
+    c.run_slabs(L, Ls, [&] { mtg_launch_lomb_scargle_stats(qa.ls, c.s); mtg_launch_lomb_scargle_stats(companion, c.s); },
+                [&](int64_t l0, int64_t rows) { return mtg_launch_iccf(qa, plan, l0, rows, c.s); },
+                [&](int64_t l0, int64_t rows) {
+                    const size_t bytes = (size_t)rows * (size_t)K * 8;
+                    if (ccf) c.gather(ccf + l0 * K, d_ccf.p, bytes);
+                    if (n_a) c.gather(n_a + l0 * K, d_na.p, bytes);
+                    if (n_b) c.gather(n_b + l0 * K, d_nb.p, bytes);
+                });
+    c.gather_peaks(peak, peak_index);
+    if (centroid) c.gather(centroid, d_centroid.p, (size_t)L * 8);
+    return c.finish();   // (waits for the stream: `pairs` and `order` outlive their uploads)
+}
+
 // mtg_lomb_scargle_envelope (nterms = 1) and mtg_lomb_scargle_envelope_multi
 static int lomb_scargle_envelope_entry(mtg_ctx *ctx, const char *who, int64_t F, const double *freqs, int nterms, int normalization,
                                        int weighted, int Q, const int64_t *ranks, double *order_stat, int64_t *valid,

@@ -411,6 +411,32 @@ struct MtgCrossArgs {
 // these sizes and outputs: mtg_lag_launch_blocks)
 hipError_t mtg_launch_cross(const MtgCrossArgs &, const MtgCrossPlan &, int64_t l0, int64_t Ls, hipStream_t);
 
+// One slab [l0, l0 + Ls) of mtg_iccf (mtg_iccf.hip; instantiation, grid and slab: mtg_iccf_plan.h).  `ls` and the companion
+// as in MtgCrossArgs.  The lags as the caller gave them, and the order the grid's lanes take them in (ascending tau).
+// ccf, n_a and n_b are the SLAB's, each NULL or [Ls][K]; peak, peak_index and centroid are the call's, each NULL or [L],
+// written at l0 (they need ccf).
+#include "mtg_iccf_plan.h"
+struct MtgIccfArgs {
+    MtgLombScargleArgs ls;
+    int64_t M;
+    const double *t2;        // [M] on the device
+    const double2 *yv2;      // [L2][M]
+    const double *stats2;    // [L2][4]
+    int64_t K;
+    const double *tau;       // [K] on the device
+    const int32_t *order;    // [K] on the device: a permutation of 0 .. K - 1
+    int mode;                // MTG_ICCF_*
+    double threshold;
+    double *ccf;
+    int64_t *n_a, *n_b;
+    double *peak;
+    int64_t *peak_index;
+    double *centroid;
+};
+// (hipErrorInvalidValue: more workgroups than a grid holds, a slab outside the set or beyond the plan's, sizes out of
+// range, or a plan that is not mtg_iccf_plan's for these sizes and this mode)
+hipError_t mtg_launch_iccf(const MtgIccfArgs &, const MtgIccfPlan &, int64_t l0, int64_t Ls, hipStream_t);
+
 typedef void (*mtg_solve_launcher)(const MtgSolveArgs &, int64_t nlanes, hipStream_t);
 // Table lookup of the compiled <NR, NC> instantiations (mtg_kernels.hip).
 mtg_solve_launcher mtg_find_solver(int nr, int nc, int last_b0 = 0);

@@ -43,7 +43,7 @@ EXPORTS = (
     "mtg_predict_at", "mtg_gp_draw", "mtg_gp_cond_draw", "mtg_loglike_grad", "mtg_mean_nparams",
     "mtg_predict_terms", "mtg_lomb_scargle", "mtg_lomb_scargle_envelope", "mtg_whiten",
     "mtg_lomb_scargle_multi", "mtg_lomb_scargle_envelope_multi", "mtg_epoch_fold", "mtg_phase_fold",
-    "mtg_wwz", "mtg_lag_sums", "mtg_cross_sums",
+    "mtg_wwz", "mtg_lag_sums", "mtg_cross_sums", "mtg_iccf",
 )
 
 # include/mtg.h, MTG_WHITEN_NSTATS and the slots of a row of whiten's stats
@@ -63,6 +63,10 @@ LAG_MAX_BINS = 128   # include/mtg.h, MTG_LAG_MAX_BINS: the lag bins of lag_sums
 LAG_SUMS = ("count", "lag", "sf", "cf", "cf2", "noise")   # mtg_lag_sums' outputs, in its order
 CROSS_SUMS = ("count", "lag", "cf", "cf2", "sa", "sb", "saa", "sbb")   # mtg_cross_sums' outputs, in its order
 CROSS_MAX_M = 1 << 28   # include/mtg.h: the companion of cross_sums has fewer samples than this
+# include/mtg.h, MTG_ICCF_*: which half iccf forms, and the most lags of one call
+ICCF_BOTH, ICCF_COMPANION, ICCF_RESIDENT = range(3)
+ICCF_MODES = {"both": ICCF_BOTH, "companion": ICCF_COMPANION, "resident": ICCF_RESIDENT}
+ICCF_MAX_LAGS = 65536
 
 # the exchange of a walker-sharded ensemble as a callback (include/mtg.h, mtg_exchange_fn)
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -71,6 +75,7 @@ EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(cty
 
 LombScargleEnvelope = collections.namedtuple("LombScargleEnvelope", "order_stat valid exceed peak_ratio peak_ratio_index")
 PhaseFold = collections.namedtuple("PhaseFold", "count wsum wrsum varsum")
+Iccf = collections.namedtuple("Iccf", "ccf n_a n_b peak peak_index centroid")
 
 
 class EngineUnavailable(RuntimeError):
@@ -366,6 +371,8 @@ def load_library():
     lib.mtg_lag_sums.argtypes = [c_vp, c_int, _dp, _lp, _dp, _dp, _dp, _dp, _dp]
     lib.mtg_cross_sums.restype = c_int
     lib.mtg_cross_sums.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, c_int, _dp, _lp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]
+    lib.mtg_iccf.restype = c_int
+    lib.mtg_iccf.argtypes = [c_vp, c_i64, _dp, c_i64, _dp, c_i64, _dp, c_int, ctypes.c_double, _dp, _lp, _lp, _dp, _lp, _dp]
     lib.mtg_gp_draw.argtypes = [c_vp, c_i64, _dp, _ip, ctypes.c_uint64, _dp, _dp, _ip]
     lib.mtg_whiten.restype = c_int
     lib.mtg_whiten.argtypes = [c_vp, c_i64, _dp, _ip, _dp, _dp, c_int, _dp, _dp, _ip]
@@ -988,6 +995,47 @@ class Engine:
         out, ptrs = _bin_sums(CROSS_SUMS, want, (int(self.L), len(edges) - 1))
         self._check(self._lib.mtg_cross_sums(self._ctx, len(t2), _ptr(t2), L2, _ptr(y2), len(edges) - 1, _ptr(edges), *ptrs))
         return out
+
+    def iccf(self, t2, y2, lags, mode="both", threshold=0.8, values=True, counts=False, peak=False):
+        """The interpolated cross-correlation function (Gaskell & Peterson 1987) of every resident light curve and a
+        companion series -- ``t2`` [M] ascending, ``y2`` [M] (one series for every light curve) or [L][M] (row l goes
+        with light curve l) -- at the ``lags`` [K] (finite, any order, at most 65536; positive: the companion lags).
+        ``mode``: ``"companion"`` interpolates the companion at ``t_i + lag``, ``"resident"`` the resident series at
+        ``t2_j - lag``, ``"both"`` is the mean of the two.  Nothing is extrapolated: a half correlates only the samples
+        whose shifted time lies inside the other series' span.  -> ``Iccf(ccf, n_a, n_b, peak, peak_index, centroid)``,
+        what was not asked for None: ``values`` the function [L][K] (NaN where a half has fewer than two samples or no
+        variance), ``counts`` the samples each half used [L][K] (int64; 0 for a half the mode does not form), ``peak``
+        per light curve the largest finite value, the first lag index attaining it (-1: none) and the centroid
+        ``sum lag ccf / sum ccf`` over the lags at or above ``threshold`` x peak, reduced on the device -- with
+        ``values=False, counts=False`` nothing of size L K comes back.  Linear interpolation across a gap invents data:
+        calibrate against simulations on the same sampling (``ppp.iccf_significance``).  An entry depends on its light
+        curve, its companion row, ``t2``, its lag and the mode alone, bit for bit.  A model need not be set (mtg_iccf)."""
+        lags = _f64(np.atleast_1d(lags)).ravel()
+        t2 = _f64(np.atleast_1d(t2))
+        y2 = _f64(y2)
+        if isinstance(mode, str):
+            if mode not in ICCF_MODES:
+                raise ValueError("mode must be one of %s" % sorted(ICCF_MODES))
+            mode = ICCF_MODES[mode]
+        if not (values or counts or peak):
+            raise ValueError("iccf: nothing asked for (values, counts and peak are all False)")
+        if not 1 <= len(lags) <= ICCF_MAX_LAGS:
+            raise ValueError("iccf: need 1 .. %d lags" % ICCF_MAX_LAGS)
+        if not 0.0 < float(threshold) <= 1.0:
+            raise ValueError("iccf: threshold must lie in (0, 1]")
+        if t2.ndim != 1 or y2.ndim not in (1, 2) or y2.shape[-1] != len(t2):
+            raise ValueError("iccf: t2 must be [M] and y2 [M] or [L][M]")
+        L2 = 1 if y2.ndim == 1 else y2.shape[0]
+        L, K = int(self.L), len(lags)
+        ccf = np.full((L, K), np.nan) if values else None
+        n_a = np.zeros((L, K), dtype=np.int64) if counts else None
+        n_b = np.zeros((L, K), dtype=np.int64) if counts else None
+        pk = np.full(L, np.nan) if peak else None
+        ix = np.full(L, -1, dtype=np.int64) if peak else None
+        ce = np.full(L, np.nan) if peak else None
+        self._check(self._lib.mtg_iccf(self._ctx, len(t2), _ptr(t2), L2, _ptr(y2), K, _ptr(lags), int(mode), float(threshold),
+                                       _ptr(ccf), _lptr(n_a), _lptr(n_b), _ptr(pk), _lptr(ix), _ptr(ce)))
+        return Iccf(ccf, n_a, n_b, pk, ix, ce)
 
     def phase_fold(self, freqs, nbins=10, time_0=None, weighted=True):
         """The folded profiles behind ``epoch_fold``, for the few frequencies one looks at: ``PhaseFold(count, wsum,

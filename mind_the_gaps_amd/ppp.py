@@ -896,6 +896,56 @@ def cross_lag_significance(lightcurve, companion, null_kernel, edges, nsims=100,
     return res
 
 
+def iccf_significance(lightcurve, companion, null_kernel, lags, nsims=100, levels=(0.95, 0.997), mode="both", threshold=0.8,
+                      walkers=12, max_steps=500, sigma_noise=None, extension_factor=2, seed=None, device=0, progress=False,
+                      pdf="Gaussian", max_iter=400):
+    """``cross_lag_significance`` for the interpolated cross-correlation function: is the ICCF of ``lightcurve`` with
+    ``companion`` (``times``, ``y``) at ``lags`` (``timedomain.iccf_lags``; positive: the companion lags) unusual if the
+    light curve is red noise of ``null_kernel``, INDEPENDENT of the companion?  Linear interpolation across the gaps of
+    either sampling invents data; the simulated light curves live on the same gappy sampling and are interpolated the
+    same way, which is what makes the comparison fair.
+
+    1. the observed ICCF, its peak and its centroid (``Engine.iccf``; ``mode``, ``threshold`` as there);
+    2. and 3. the null chain, the ``nsims`` posterior picks and the simulated set of ``cross_lag_significance``: the same
+       ones for the same seed, left resident on the device;
+    4. ONE ``Engine.iccf`` call of that set against the observed companion, and ``np.quantile`` over the [nsims][K]
+       values on the host, lag by lag;
+    5. ``p_global = (1 + #{simulations whose peak r >= the observed peak r}) / (1 + nsims)``.
+
+    Returns dict(lags[K], n_a[K], n_b[K], observed[K], median, lower[len(levels)][K], upper, share_above, share_below as
+    ``lag_significance``; peak, peak_lag, centroid the observation's; sim_peaks[nsims], sim_peak_lags[nsims],
+    sim_centroids[nsims]; p_global; sims[nsims][K], null, samples[nsims][P], sim_seed, lightcurves).  A lag at which a
+    half has fewer than two samples is NaN throughout.  One GPU; the same seed gives the same result bit for bit."""
+    from .engine import ICCF_MODES
+    from .gp import get_engine
+    if mode not in ICCF_MODES:
+        raise ValueError("mode must be one of %s" % sorted(ICCF_MODES))
+    if not 0.0 < threshold <= 1.0:
+        raise ValueError("threshold must lie in (0, 1]")
+    lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.float64).ravel()
+    times = np.asarray(lightcurve.times, dtype=np.float64)
+    y = np.asarray(lightcurve.y, dtype=np.float64)
+    dy = np.ones_like(y) if lightcurve.dy is None else np.asarray(lightcurve.dy, dtype=np.float64)
+    t2 = np.ascontiguousarray(companion.times, dtype=np.float64)
+    y2 = np.ascontiguousarray(companion.y, dtype=np.float64)
+    if t2.ndim != 1 or y2.shape != t2.shape:
+        raise ValueError("the companion must be one series: times [M] and y [M]")
+    lag_at = lambda index: np.where(index >= 0, lags[np.maximum(index, 0)], np.nan)
+    eng = get_engine(device)
+    eng.set_lightcurves(times, y, dy)
+    eng.bound_to = None
+    obs = eng.iccf(t2, y2, lags, mode=mode, threshold=threshold, values=True, counts=True, peak=True)
+    eng, null, samples, sim_seed, out = _simulate_null_set(lightcurve, null_kernel, nsims, walkers, max_steps, sigma_noise,
+                                                           extension_factor, seed, device, progress, pdf, max_iter)
+    sim = eng.iccf(t2, y2, lags, mode=mode, threshold=threshold, values=True, counts=False, peak=True)
+    peak = float(obs.peak[0])
+    res = dict(lags=lags, n_a=obs.n_a[0], n_b=obs.n_b[0], observed=obs.ccf[0], sims=sim.ccf, peak=peak, peak_lag=float(lag_at(obs.peak_index)[0]),
+               centroid=float(obs.centroid[0]), sim_peaks=sim.peak, sim_peak_lags=lag_at(sim.peak_index), sim_centroids=sim.centroid,
+               p_global=_cross_global_p(peak, sim.peak), null=null, samples=samples, sim_seed=sim_seed, lightcurves=out)
+    res.update(_lag_levels(obs.ccf[0], sim.ccf, levels))
+    return res
+
+
 def _seed_schedule(seed, nsims):
     """Every random number protassov_test itself draws, from ONE ``default_rng(seed)``, in the order every bit-for-bit
     guarantee of the sharded run rests on.  A generator of two steps: ``next`` gives the two chain seeds, ``send(null)``

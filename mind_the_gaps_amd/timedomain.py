@@ -16,7 +16,7 @@ The lag between TWO series on different samplings -- one energy band against ano
 """
 import numpy as np
 
-from .engine import LAG_MAX_BINS
+from .engine import ICCF_MAX_LAGS, LAG_MAX_BINS
 
 __all__ = ["lag_bins", "StructureFunction", "DiscreteCorrelation", "model_structure_function", "sf_from_sums", "dcf_from_sums",
            "cross_lag_bins", "ccf_from_sums", "CrossCorrelation", "lag_peak_and_centroid"]
@@ -265,6 +265,69 @@ class CrossCorrelation:
         e2b = np.mean(np.atleast_2d(self.dy2) ** 2, axis=1) if subtract_noise and self.dy2 is not None else 0.0
         out = ccf_from_sums(sums, s2a, s2b, e2a, e2b, normalization)
         return tuple(a.reshape(self.y1.shape[:-1] + a.shape[-1:]) for a in out)
+
+
+def iccf_lags(t1, t2, n=201, max_lag=None):
+    """``n`` uniform lags from ``-max_lag`` to ``max_lag`` for ``Engine.iccf`` (None: half the shorter of the two spans):
+    a symmetric grid, with lag 0 on it when ``n`` is odd."""
+    t1, t2 = (np.asarray(t, dtype=np.float64) for t in (t1, t2))
+    if t1.ndim != 1 or t2.ndim != 1 or len(t1) < 2 or len(t2) < 2:
+        raise ValueError("t1 and t2 must be [N] and [M] with at least two samples each")
+    if n not in range(1, ICCF_MAX_LAGS + 1):
+        raise ValueError("n must lie in 1 .. %d" % ICCF_MAX_LAGS)
+    if max_lag is None:
+        max_lag = 0.5 * min(float(t1.max() - t1.min()), float(t2.max() - t2.min()))
+    if not np.isfinite(max_lag) or not max_lag > 0:
+        raise ValueError("need a finite max_lag > 0, got %r" % (max_lag,))
+    return np.linspace(-max_lag, max_lag, n)
+
+
+class InterpolatedCrossCorrelation:
+    """``InterpolatedCrossCorrelation(t1, y1, t2, y2)``: the interpolated cross-correlation function (Gaskell & Peterson
+    1987; White & Peterson 1994) of two series on their own samplings, on a lag grid finer than any bin of
+    ``CrossCorrelation`` could be.  ``t1`` [N] ascending with ``y1`` [N] or [L][N], ``t2`` [M] ascending with ``y2`` [M]
+    (one companion for every row of ``y1``) or [L][M].  A positive lag means the second series lags the first.  One series
+    is linearly interpolated at the other's shifted times: across a gap that invents data, so read the counts and
+    calibrate with ``ppp.iccf_significance``."""
+
+    def __init__(self, t1, y1, t2, y2, device=0):
+        self.t1, self.y1 = np.ascontiguousarray(t1, dtype=np.float64), np.ascontiguousarray(y1, dtype=np.float64)
+        self.t2, self.y2 = np.ascontiguousarray(t2, dtype=np.float64), np.ascontiguousarray(y2, dtype=np.float64)
+        if self.t1.ndim != 1 or self.y1.ndim not in (1, 2) or self.y1.shape[-1] != len(self.t1):
+            raise ValueError("t1 must be [N] and y1 [N] or [L][N]")
+        if self.t2.ndim != 1 or self.y2.ndim not in (1, 2) or self.y2.shape[-1] != len(self.t2):
+            raise ValueError("t2 must be [M] and y2 [M] or [L][M]")
+        if len(self.t1) < 2 or len(self.t2) < 2:
+            raise ValueError("each series needs at least two samples")
+        if np.any(np.diff(self.t1) < 0) or np.any(np.diff(self.t2) < 0):
+            raise ValueError("t1 and t2 must ascend")
+        if self.y2.ndim == 2 and (self.y1.ndim != 2 or len(self.y2) != len(self.y1)):
+            raise ValueError("y2 [L][M] needs y1 [L][N] with the same L")
+        self.device = device
+
+    def _engine(self):
+        from .gp import get_engine
+        eng = get_engine(self.device)
+        y1 = np.atleast_2d(self.y1)
+        eng.set_lightcurves(self.t1, y1, np.ones_like(y1))
+        eng.bound_to = None      # the process-wide engine holds this object's light curves now, nobody's evaluator's
+        return eng
+
+    def ccf(self, lags, mode="both"):
+        """-> (ccf, n_a, n_b), each [K] or [L][K]: the function at ``lags`` (``iccf_lags``) and the samples each half
+        used; ``mode`` "both", "companion" (the second series interpolated) or "resident" (the first)."""
+        got = self._engine().iccf(self.t2, self.y2, lags, mode=mode, values=True, counts=True)
+        return tuple(a.reshape(self.y1.shape[:-1] + a.shape[-1:]) for a in (got.ccf, got.n_a, got.n_b))
+
+    def lag(self, lags, mode="both", threshold=0.8):
+        """-> (peak lag, centroid, peak value), per row of ``y1`` (floats for one series): the lag of the largest finite
+        value, the centroid of the lags at or above ``threshold`` x peak (Peterson et al. 1998), reduced on the device."""
+        lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.float64).ravel()
+        got = self._engine().iccf(self.t2, self.y2, lags, mode=mode, threshold=threshold, values=False, peak=True)
+        at = np.where(got.peak_index >= 0, lags[np.maximum(got.peak_index, 0)], np.nan)
+        if self.y1.ndim == 1:
+            return float(at[0]), float(got.centroid[0]), float(got.peak[0])
+        return at, got.centroid, got.peak
 
 
 def model_structure_function(kernel, lags, jitter=0.0):
